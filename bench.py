@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mreads/s aligned + ST-typed (BASELINE.json `metric`).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload of the driver line = BASELINE.json configs[2] (cfg3), the configuration the metric is quoted on: the full
 database (synthetic stand-in for metamlstDB_2022, which the reference downloads at run time: 150 species x 7 loci x
 300 alleles) and a 50 M-read mixed metagenome of 20 genomes per GPU.  One "step" = one complete typing pass over one
 resident batch: seed sieve -> exact seeds -> extension against every allele of the hit loci -> hit accumulation ->
-allele choice -> pileup -> consensus -> .nfo lines -> allele match + ST call of every species in the sample.  cfg2
-(10 M reads of one E. coli-like isolate, 7 loci x 1430 alleles) runs afterwards at N=1 and is reported as a secondary
-block of the same JSON line, together with the end-to-end rates (FASTQ text / bgzip on the host -> ST) and the CPU
-oracle on a bounded sample of the cfg3 workload.
+allele choice -> pileup -> consensus -> .nfo lines -> allele match + ST call of every species in the sample.
+
+A plain run does what the headline needs: set-up, warm-up, the K timed steps, the result line.  --full adds the rest at
+N=1: isolated kernel times and rooflines, serial steps, the CPU oracle on a bounded sample of the cfg3 workload (rate and
+parity), the end-to-end rates (FASTQ text / bgzip on the host -> ST), and cfg2 (10 M reads of one E. coli-like isolate,
+7 loci x 1430 alleles) and a PubMLST-shaped database as secondary blocks of the same JSON line.  --dump-outputs DIR
+writes what the last timed step computed (statistics, chosen alleles, consensus, ST calls) as DIR/<name>.npy in float64;
+the inputs are seeded, so two builds can be compared output for output.
 
 --gpus N without a launcher starts the N ranks itself (torch.distributed.run, before this process touches the GPU);
 under `python -m torch.distributed.run ... bench.py --gpus N` it reads RANK / LOCAL_RANK / WORLD_SIZE.  At N > 1 every
@@ -19,9 +23,9 @@ RCCL on the engine's stream, and rank 0 runs the host tail.
 
 Several engines per GPU (--pipeline, default 4: four HIP streams, four sets of sample state) work in turn, each on
 its OWN resident batch (distinct reads: no step re-reads what the step before it read), so that the host part of
-step k overlaps the kernels of the following steps.  Every step is still one complete pass.  The timed region is a
-series of blocks of exactly K steps, each bracketed by barrier + synchronize, repeated until at least --min-seconds have
-been timed; the block with the median duration is the one reported (`ms_per_step`, `value`).
+step k overlaps the kernels of the following steps.  Every step is still one complete pass.  The timed region is one
+block of exactly K steps, bracketed by barrier + synchronize (`ms_per_step`, `value`); with --min-seconds S the block is
+repeated until S seconds have been timed and the block with the median duration is the one reported.
 
 Reads are synthesised on the GPU before the timed region and are resident in HBM in the packed format of
 SURVEY.md 8(d) (2-bit bases + Phred rows); the timed region contains no H2D copy of reads.
@@ -55,7 +59,14 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--host-profile", default=None, help="diagnostics: cProfile of the host loop over 200 extra (untimed) steps, written to this file")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="timed blocks of --steps steps are repeated until this much has been timed")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="timed blocks of --steps steps are repeated until this much has been timed, the median block is reported "
+                         "(default 0: one block, exactly --steps timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: isolated kernel times and rooflines, serial steps, CPU oracle baseline, "
+                         "end-to-end rates, the cfg2 and skewed-database blocks, the second command's set-up")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--workload", default="cfg3", choices=["cfg3", "cfg2", "skewed"], help="workload of the headline line")
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU and batch (default: 50 M for cfg3, 10 M for cfg2)")
     ap.add_argument("--species", type=int, default=150)
@@ -63,7 +74,7 @@ def parse_args():
     ap.add_argument("--genomes", type=int, default=20)
     ap.add_argument("--genome-size", type=int, default=0, help="isolate genome size (default: 2 Mb for cfg3, 4.6 Mb for cfg2)")
     ap.add_argument("--read-len", type=int, default=150)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline time (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline time of --full (0 = skip)")
     ap.add_argument("--pipeline", type=int, default=4,
                     help="engines per GPU, each with its own resident batch: the GPU already works on the next steps while the host "
                          "types step k (every step is still a complete pass); 1 = strictly serial steps")
@@ -72,7 +83,7 @@ def parse_args():
                          "0 = one share per engine, 1 = every engine on the whole device (rounds 1-3)")
     ap.add_argument("--stagger-ms", type=float, default=None,
                     help="time between the first submissions of a block (default: 0.75 ms when the engines have their own CU shares, else 0)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the cfg2 block and the end-to-end rates")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the cfg2 and skewed blocks and the end-to-end rates")
     ap.add_argument("--e2e-reads", type=int, default=48_000_000, help="reads of the end-to-end (host FASTQ text -> ST) measurements (cfg2's legs: its 10 M); 24 M until round 5")
     ap.add_argument("--calibrate", action="store_true",
                     help="before the timed region copy the Phred rows 3x with torch (a known-size wide coalesced stream) "
@@ -135,6 +146,15 @@ def build_workload(name, args, eng_factory, torch, device, rank, n_batches, tmp)
         w.label = ("cfg2: %d x %d bp SE reads per GPU, one E. coli-like isolate (%.1f Mb), synthetic DB 7 loci x %d alleles"
                    % (w.reads, args.read_len, w.genome_size / 1e6, alleles))
     w.t_db = time.time() - t0
+    pending = {}
+    if name in ("cfg3", "skewed", "skewed_nodup"):
+        # the isolate genomes make_metagenome_gpu would make one after the other (make_genome with seed 1000 + k; mostly SQLite
+        # scans for the planted alleles, which release the GIL), made on host threads while the index is loaded
+        from concurrent.futures import ThreadPoolExecutor
+        pool = ThreadPoolExecutor(min(16, len(w.plan)))
+        pending = {sp: pool.submit(synth.make_genome, w.sdb, sp, w.sdb.profiles[sp][st_row], size=w.genome_size, seed=1000 + k)
+                   for k, (sp, _, st_row) in enumerate(w.plan)}
+        pool.shutdown(wait=False)
     t0 = time.time()
     w.idx = load_index(w.sdb.path)
     w.database = mdb.metaMLST_db(w.sdb.path)
@@ -142,7 +162,8 @@ def build_workload(name, args, eng_factory, torch, device, rank, n_batches, tmp)
     t0 = time.time()
     w.engines = [eng_factory() for _ in range(n_batches)]
     w.eng_factory = eng_factory
-    ref_cache = w.sdb.path + ".mlstref"         # the built host index on disk, next to the database (mlst_set_reference_cache)
+    # the built host index on disk, next to the database (mlst_set_reference_cache): written for --full's second command only
+    ref_cache = w.sdb.path + ".mlstref" if getattr(args, "measure_second_command", False) else None
     for e in w.engines:
         e.load_reference(w.idx, cache_path=ref_cache)      # the host index is built once per process (cached inside the library) and stored
     w.t_index_dev = time.time() - t0
@@ -160,7 +181,7 @@ def build_workload(name, args, eng_factory, torch, device, rank, n_batches, tmp)
     from metamlst_amd.engine import load_library as _ll
     _ll().mlst_set_reference_cache(None)
     t0 = time.time()
-    w.batches, w.genomes = [], {}
+    w.batches, w.genomes = [], {sp: f.result()[0] for sp, f in pending.items()}
     for b in range(n_batches):
         if name in ("cfg3", "skewed", "skewed_nodup"):
             packed, qrows, lens, wpr, qstride, n_total = synth.make_metagenome_gpu(
@@ -217,6 +238,7 @@ def run_workload(w, args, torch, dist, device, rank, world, backend):
     cache = mdb.DbCache(database.conn, idx)
     sessions = {sp: SpeciesSession(database, sp, 5, matcher, cache) for sp in w.planted} if rank == 0 else {}
     host_ms = {"submit": 0.0, "wait_device": 0.0, "typing": 0.0, "st_call": 0.0}
+    typed = {}      # choice and consensus of the step whose tail ran last, made on the device (--dump-outputs)
 
     def submit(k):
         """Everything of step k that runs on the GPU, queued without waiting, on engine k % depth and its batch."""
@@ -267,6 +289,7 @@ def run_workload(w, args, torch, dist, device, rank, world, backend):
             res = type_sample(idx, st, None, database, "sample", fast=True, cache=cache, consensus_fn=consensus_fn)
         else:
             st, chosen_dev, letters_dev = got
+            typed["chosen"], typed["letters"] = chosen_dev, letters_dev
             t_c = t_b
             res = type_sample(idx, st, None, database, "sample", fast=True, cache=cache, typed=(chosen_dev, letters_dev))
         t_d = time.perf_counter()
@@ -372,17 +395,21 @@ def run_workload(w, args, torch, dist, device, rank, world, backend):
     run(args.warmup)
     fence()
     # strictly serial steps on one engine, untimed, with HIP events around the kernel groups (on the engine's stream):
-    # every kernel has the GPU to itself, which is what `rocprofv3 --kernel-trace --stats -- python3 bench.py --pipeline 1`
-    # shows as the kernel's average (profiles/round2/kernel_summary_*.md)
+    # every kernel has the GPU to itself, which is what `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --pipeline 1`
+    # shows as the kernel's average (profiles/round2/kernel_summary_*.md).  A plain run takes them only where they decide
+    # whether the engines get shares of the CUs (below).
     from metamlst_amd.engine import KERNELS
     KNAMES = [k for k in KERNELS if k not in ("pack", "sieve_inkernel", "sieve_wg_longest")]
-    engines[0].set_profiling(1)
-    n_iso = 20
+    decide_parts = world == 1 and n_parts > 1 and not args.cu_partitions
+    n_iso = 20 if (args.full or decide_parts) else 0
+    if n_iso:
+        engines[0].set_profiling(1)
     per_launch = {k: [] for k in KNAMES}
     # (the next launch is queued before the host tail of the one just fetched, as in the timed loop: with the GPU idle for
     # the 1.3 ms of every host tail the same kernels ran 3-5 % slower -- clocks -- than rocprofv3 saw them in the timed blocks)
     engines[0].reset_kernel_time()
-    submit(0)
+    if n_iso:
+        submit(0)
     for k in range(n_iso):
         got = None if (world > 1 and not mode["streamed"]) else wait(0)
         if got is None:
@@ -399,16 +426,19 @@ def run_workload(w, args, torch, dist, device, rank, world, backend):
     fence()
     isolated = {k: (float(np.median(v)) if v else 0.0, 1) for k, v in per_launch.items()}      # (median launch, 1): what the rooflines use
     spread = {k: {"min": round(min(v), 4), "median": round(float(np.median(v)), 4), "max": round(max(v), 4), "n": len(v)} for k, v in per_launch.items() if v}
-    engines[0].set_profiling(0)
+    if n_iso:
+        engines[0].set_profiling(0)
     fence()
-    t0 = time.perf_counter()
-    n_serial = 5
-    for k in range(n_serial):
-        submit(0)
-        finish(0)
-    fence()
-    serial_ms = (time.perf_counter() - t0) / n_serial * 1e3
-    if world == 1 and n_parts > 1 and not args.cu_partitions and sum(v[0] for k_, v in isolated.items() if k_ in ("sieve", "seed", "extend", "banded_sw", "accumulate", "pileup")) < 1.0:
+    serial_ms = None
+    if args.full:
+        t0 = time.perf_counter()
+        n_serial = 5
+        for k in range(n_serial):
+            submit(0)
+            finish(0)
+        fence()
+        serial_ms = (time.perf_counter() - t0) / n_serial * 1e3
+    if decide_parts and sum(v[0] for k_, v in isolated.items() if k_ in ("sieve", "seed", "extend", "banded_sw", "accumulate", "pileup")) < 1.0:
         n_parts = 1      # a step of well under a millisecond of kernels (cfg2: 0.35 ms) gains nothing from shares (0.342 -> 0.351 ms)
     if n_parts > 1:      # from here on every engine has its own share of the CUs; graphs are rebuilt, warm-up again
         place(True)
@@ -422,12 +452,13 @@ def run_workload(w, args, torch, dist, device, rank, world, backend):
         fence()
         run(args.warmup)
         fence()
-    # ---- timed region: blocks of exactly K steps, repeated until min-seconds have been timed (at least 3 blocks)
+    # ---- timed region: one block of exactly K steps (repeated until min-seconds have been timed, where that is given)
     blocks, total = [], 0.0
     last = None
-    while len(blocks) < 3 or total < args.min_seconds:
+    while not blocks or total < args.min_seconds:
         for k in host_ms:
             host_ms[k] = 0.0
+        typed.clear()
         fence()
         t0 = time.perf_counter()
         last = run(args.steps)
@@ -441,6 +472,7 @@ def run_workload(w, args, torch, dist, device, rank, world, backend):
         total += dt
         if len(blocks) >= 200:
             break
+    last_typed = dict(typed)
     if args.host_profile and rank == 0 and world == 1:      # where the host thread spends a step (untimed, after the timed blocks)
         import cProfile
         import io
@@ -472,7 +504,7 @@ def run_workload(w, args, torch, dist, device, rank, world, backend):
         st_call = wrong[0]
     return {"ms_per_step": dt / args.steps * 1e3, "value": w.n_reads * world / (dt / args.steps) / 1e6,
             "blocks": len(blocks), "block_ms": [round(b[0] * 1e3, 3) for b in blocks], "timed_s": round(total, 3),
-            "host_ms_per_step": {k: round(v / args.steps, 4) for k, v in hm.items()}, "serial_ms_per_step": serial_ms,
+            "host_ms_per_step": {k: round(v / args.steps, 4) for k, v in hm.items()}, "serial_ms_per_step": serial_ms, "last": last, "typed": last_typed,
             "iso_launch_ms": iso_launch, "iso_launch_spread": spread, "stats": stats, "st_call": st_call, "typed_ok": typed_ok, "batches_checked": len(calls),
             "collectives": ("streamed on a torch stream" if mode["streamed"] else "host-driven") if world > 1 else None,
             "cu_partitions": n_parts,
@@ -898,6 +930,26 @@ def summarize(w, res, eng, world, depth):
             "collectives": res["collectives"], "exchange_per_step": res.get("exchange"), "resident_format": "2-bit bases %d B/read + Phred rows %d B/read" % (w.wpr * 4, w.qstride)}
 
 
+def dump_outputs(path, w, res):
+    """--dump-outputs: what the last timed step computed, as the caller of the path receives it, in float64 -- the step's
+    per-locus statistics and counters, the allele chosen per locus (-1: none) and the consensus letters of the chosen alleles
+    in locus order (both where choice and consensus are made on the device: N = 1, streamed exchange), and the ST called per
+    planted species in name order (NaN: none).  A few MB on cfg3."""
+    st_call, stats = res["last"]
+    out = {"locus_len_sum": stats.locus_len_sum, "locus_first": stats.locus_first, "counters": stats.counters,
+           "st_called": [np.nan if st_call.get(sp) is None else float(st_call[sp]) for sp in sorted(w.planted)]}
+    typed = res["typed"]
+    if typed:
+        chosen = np.full(int(w.idx.n_loci), -1, np.int64)
+        for l, a in typed["chosen"].items():
+            chosen[l] = a
+        out["chosen_allele"] = chosen
+        out["consensus"] = np.frombuffer(b"".join(typed["letters"][a] for _, a in sorted(typed["chosen"].items())), np.uint8)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, np.float64))
+
+
 def main():
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # (this pool's driver shares device memory between processes by dmabuf only: RCCL needs it)
     args = parse_args()
@@ -932,8 +984,20 @@ def main():
 
     depth = max(1, min(8, args.pipeline))
     tmp = tempfile.mkdtemp(prefix="mlst_bench_%d_" % rank)
+    try:
+        run_bench(args, torch, dist, device, rank, local_rank, world, backend, depth, tmp)
+    finally:
+        import shutil
+        shutil.rmtree(tmp, ignore_errors=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def run_bench(args, torch, dist, device, rank, local_rank, world, backend, depth, tmp):
+    from metamlst_amd.engine import Engine
     t_start = time.time()
-    args.measure_second_command = True
+    args.measure_second_command = args.full
     w = build_workload(args.workload, args, lambda: Engine(local_rank), torch, device, rank, depth, tmp)
     if args.calibrate:
         for _ in range(3):
@@ -942,41 +1006,52 @@ def main():
         del _c
     res = run_workload(w, args, torch, dist, device, rank, world, backend)
     if rank != 0:
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, w, res)
     eng = w.engines[0]
-    roof, roof_ext = rooflines(w, res, eng)
     stats = res["stats"]
     conc = {"species_planted": len(w.planted), "species_typed_correctly": int(sum(res["typed_ok"].values())),
             "st_match": all(res["typed_ok"].values()), "batches_checked": res["batches_checked"],
             "not_typed": {sp: {"called": res["st_call"].get(sp), "planted": w.planted[sp]} for sp, ok in res["typed_ok"].items() if not ok}}
+    out = {"metric": "Mreads/s aligned+ST-typed, metamlstDB_2022; ST concordance vs CPU ref",
+           "value": round(res["value"], 2), "unit": "Mreads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(res["ms_per_step"], 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "int32", "data": "synthetic",
+           "config": summarize(w, res, eng, world, depth), "concordance": conc,
+           "timed_region": {"blocks": res["blocks"], "steps_per_block": args.steps, "timed_s": res["timed_s"], "reported": "median block", "block_ms": res["block_ms"][:32]},
+           "host_ms_per_step": res["host_ms_per_step"],
+           "counters": {"records": int(stats.counters[0]), "ignored": int(stats.counters[1]), "candidates": int(stats.counters[3]),
+                        "retained": int(stats.counters[4]), "items": int(stats.counters[5]), "banded_sw_pairs": int(stats.counters[6]),
+                        "routed_filter_passes": int(stats.counters[7])},
+           "index_bytes": dict(zip(("allele_arena_and_haplotype_tables", "sieve", "seed_table"), eng.index_bytes()[:3])), "extend": eng.extend_info(),
+           "setup_s": {"database": round(w.t_db, 1), "index_host": round(w.t_index_host, 1), "index_device_x%d" % depth: round(w.t_index_dev, 1),
+                       "resident_reads_x%d" % depth: round(w.t_reads, 1)},
+           "world_size_reported_by_backend": (dist.get_world_size() if world > 1 else 1)}
+    if args.full:
+        run_full(out, w, res, args, torch, dist, device, rank, local_rank, world, backend, depth, tmp)
+    out["wall_s"] = round(time.time() - t_start, 1)
+    print(json.dumps(out))
+
+
+def run_full(out, w, res, args, torch, dist, device, rank, local_rank, world, backend, depth, tmp):
+    """--full: the figures beside the headline, after its timed steps (into `out`)."""
+    from metamlst_amd.engine import Engine
+    eng = w.engines[0]
+    roof, roof_ext = rooflines(w, res, eng)
     cpu = None
     e2e = None
     secondary = None
     if world == 1:
         if args.cpu_seconds > 0:
             cpu, same = cpu_baseline(w, args, res)
-            conc["gpu_equals_cpu_oracle_on_sample"] = same
+            out["concordance"]["gpu_equals_cpu_oracle_on_sample"] = same
         if not args.no_secondary:
             e2e = end_to_end(w, args, torch, device)
-    out = {"metric": "Mreads/s aligned+ST-typed, metamlstDB_2022; ST concordance vs CPU ref",
-           "value": round(res["value"], 2), "unit": "Mreads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": round(res["ms_per_step"], 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "int32", "data": "synthetic",
-           "config": summarize(w, res, eng, world, depth),
-           "roofline": roof, "roofline_extend": roof_ext, "cpu_baseline": cpu, "concordance": conc, "end_to_end": e2e,
-           "timed_region": {"blocks": res["blocks"], "steps_per_block": args.steps, "timed_s": res["timed_s"], "reported": "median block", "block_ms": res["block_ms"][:32]},
-           "kernel_ms_per_launch_isolated": {k: round(v, 4) for k, v in res["iso_launch_ms"].items()},
-           "host_ms_per_step": res["host_ms_per_step"], "serial_ms_per_step": round(res["serial_ms_per_step"], 4),
-           "counters": {"records": int(stats.counters[0]), "ignored": int(stats.counters[1]), "candidates": int(stats.counters[3]),
-                        "retained": int(stats.counters[4]), "items": int(stats.counters[5]), "banded_sw_pairs": int(stats.counters[6]),
-                        "routed_filter_passes": int(stats.counters[7])},
-           "index_bytes": dict(zip(("allele_arena_and_haplotype_tables", "sieve", "seed_table"), eng.index_bytes()[:3])), "extend": eng.extend_info(),
-           "setup_s": {"database": round(w.t_db, 1), "index_host": round(w.t_index_host, 1), "index_device_x%d" % depth: round(w.t_index_dev, 1),
-                       "resident_reads_x%d" % depth: round(w.t_reads, 1), "second_command": w.t_cached},
-           "world_size_reported_by_backend": (dist.get_world_size() if world > 1 else 1), "literal_parity_bowtie2": None}
+    out.update({"roofline": roof, "roofline_extend": roof_ext, "cpu_baseline": cpu, "end_to_end": e2e,
+                "kernel_ms_per_launch_isolated": {k: round(v, 4) for k, v in res["iso_launch_ms"].items()},
+                "serial_ms_per_step": round(res["serial_ms_per_step"], 4), "literal_parity_bowtie2": None})
+    out["setup_s"]["second_command"] = w.t_cached
     # ---- secondary block: cfg2 (configs[1]) in the same run, N = 1 only
     if world == 1 and not args.no_secondary and args.workload == "cfg3":
         for e in list(w.engines) + list(getattr(w, "folder_engines", []))[len(w.engines):]:      # (the folder legs made two more)
@@ -984,6 +1059,7 @@ def main():
         del w.batches
         torch.cuda.empty_cache()
         a2 = argparse.Namespace(**vars(args)); a2.reads = 0; a2.alleles = 0; a2.genome_size = 0
+        a2.min_seconds = args.min_seconds or 1.0      # (the secondary figures: median block of at least a second of blocks)
         w2 = build_workload("cfg2", a2, lambda: Engine(local_rank), torch, device, rank, depth, tmp)
         r2 = run_workload(w2, a2, torch, dist, device, rank, world, backend)
         roof2, rext2 = rooflines(w2, r2, w2.engines[0])
@@ -1003,6 +1079,7 @@ def main():
         del w2.batches
         torch.cuda.empty_cache()
         a3 = argparse.Namespace(**vars(args)); a3.reads = 0; a3.alleles = 0; a3.genome_size = 0
+        a3.min_seconds = args.min_seconds or 1.0
         w3 = build_workload("skewed", a3, lambda: Engine(local_rank), torch, device, rank, depth, tmp)
         r3 = run_workload(w3, a3, torch, dist, device, rank, world, backend)
         e3 = w3.engines[0]
@@ -1033,11 +1110,6 @@ def main():
                                        "mistyped_loci": mistyped_loci(w4, full_stats(w4)), "ms_per_step": round(r4["ms_per_step"], 4),
                                        "steps_per_block": a4.steps, "blocks": r4["blocks"]}
     out["secondary_skewed"] = skewed
-    out["wall_s"] = round(time.time() - t_start, 1)
-    print(json.dumps(out))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -17,7 +17,7 @@ for n in ("consensus", "stats", "submit_packed_device", "reset_sample", "typing_
     wrap(E.Engine, n, "Engine." + n)
 wrap(M, "parse_nfo_line"); wrap(M.SpeciesSession, "add_sample", "SpeciesSession.add_sample")
 wrap(D.DbCache, "sequenceFind", "DbCache.sequenceFind")
-sys.argv = ["bench.py", "--steps", "200", "--warmup", "5", "--cpu-seconds", "0", "--pipeline", os.environ.get("PIPE", "1")]
+sys.argv = ["bench.py", "--full", "--steps", "200", "--warmup", "5", "--cpu-seconds", "0", "--pipeline", os.environ.get("PIPE", "1")]
 runpy.run_path(os.path.join(ROOT, "bench.py"), run_name="__main__")
 for k, (t, n) in sorted(acc.items(), key=lambda x: -x[1][0]):
     print("%-40s %6d calls  %8.1f us/call" % (k, n, t / n * 1e6))

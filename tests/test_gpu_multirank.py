@@ -195,12 +195,12 @@ def test_cli_mate_files_count_a_pair_once_per_locus():
 
 
 def test_bench_five_ranks_on_one_gpu_reports_the_world():
-    """`bench.py --gpus 5` on a tiny workload: self-launched ranks, both collective forms, one JSON line with the world
+    """`bench.py --full --gpus 5` on a tiny workload: self-launched ranks, both collective forms, one JSON line with the world
     size the backend reported and every planted ST called."""
     import json
     env = dict(os.environ, MLST_BENCH_ONE_GPU="1", MLST_BENCH_BACKEND="gloo")
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "5", "--reads", "400000", "--species", "12", "--genomes", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "5", "--reads", "400000", "--species", "12", "--genomes", "4",
                         "--genome-size", "200000", "--steps", "3", "--warmup", "1", "--min-seconds", "0.05", "--pipeline", "2", "--cpu-seconds", "0",
                         "--no-secondary"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
