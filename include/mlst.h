@@ -148,6 +148,23 @@ int mlst_submit_fastq_pair(mlst_handle* h, const uint8_t* text1, uint64_t n1, co
 int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, int final_chunk, int paired, uint64_t* n_reads_out,
                            uint64_t* n_consumed_out);
 
+/* The two bgzip'd files of a paired-end sample, inflated on the GPU and paired there (mlst_submit_fastq_pair for BGZF).  data1 /
+ * data2 are runs of BGZF blocks of file 1 / file 2, cut as for mlst_submit_fastq_bgzf (with n_consumed1_out / n_consumed2_out
+ * != NULL a non-final buffer may end inside a block: the call takes the whole blocks and reports how many bytes that was).  A
+ * call may carry any number of records of either file, none of one of them included: record k of file 1 and record k of file 2
+ * are mates, counted across calls, and become reads 2k, 2k + 1, submitted as pairs (one QNAME per pair for sequenceBank,
+ * metamlst.py:127, Q3).  The records of the file that is ahead wait on the device for their mates, as does the partial record
+ * at the end of each file's text; a carry that cannot be placed fails with MLST_E_LIMIT.  n_reads_out counts the reads
+ * completed by the call (2 x pairs; over a sample: 2 x records per file).  The last call passes final_chunk != 0: both files
+ * must end with a whole record and hold the same number of records ("mate files hold different numbers of records"); a corrupt
+ * block is reported with the file (1 or 2) it belongs to.  Pipelined as mlst_submit_fastq_bgzf (the blocks of both files of
+ * call k are inflated in one launch sequence while the pieces of call k - 1 are paired, parsed and submitted; every entry that
+ * looks at or adds to the sample's state finishes an open piece first; MLST_BGZF_PIPE=0: serial).  While a paired stream is open
+ * (its final call not made yet) the other mlst_submit_fastq* entries refuse to start, and this one refuses while a single
+ * stream is open; mlst_reset_sample and any error drop both carries. */
+int mlst_submit_fastq_bgzf_pair(mlst_handle* h, const uint8_t* data1, uint64_t n1, const uint8_t* data2, uint64_t n2, int final_chunk,
+                                uint64_t* n_reads_out, uint64_t* n_consumed1_out, uint64_t* n_consumed2_out);
+
 /* Host-packed input: what crosses the link is 2-bit bases + lengths (42 bytes per 150-base read instead of the 316 of its
  * FASTQ text); the Phred rows stay on the host and only those of the reads that pass the seed sieve (one in ~400 of a
  * metagenome) follow.  mlst_pack_fastq_host: FASTQ text (whole 4-line records) -> `packed` in the engine's resident layout

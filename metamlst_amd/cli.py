@@ -261,6 +261,9 @@ def open_sample_reader(paths, paired: bool, chunk_bytes: int):
 
 def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader=None) -> None:
     """All reads of one sample's FASTQ file(s) into one engine (first_reader: open_sample_reader(paths, ...), if opened ahead)."""
+    if paired and is_bgzf(paths[0]) and is_bgzf(paths[1]):      # bgzip'd mates: inflated and paired on the GPU
+        eng.submit_fastq_bgzf_pair_files(paths[0], paths[1])
+        return
     if paired:
         from .fastq import release_buffers
         ring: list = []

@@ -1345,6 +1345,59 @@ __global__ __launch_bounds__(256) void k_fq_records(const u8* __restrict__ text,
     if (mx) atomicMax(&flags[0], mx);
     if (err) atomicOr(&flags[1], err);
 }
+// ---- two mate files side by side in one text slot (mlst_submit_fastq_bgzf_pair): region r holds, from byte s_r on, the text its
+// file carried over (records whose mates have not arrived yet, then a partial record) and the piece's inflated text up to end_r;
+// region 1's cells are [a1, a1 + nb1), region 2's start at cell a2 (behind them), the bytes of a region's cells in front of s_r
+// and the byte at end_r are filler without a newline.  The newline counts per cell are scanned over both regions at once (the
+// cells between them count 0): the exclusive count at cell a2 is the number of newlines in region 1.
+// last call: a region whose text does not end with a newline gets one behind it (its last quality line), counted in its cell
+__global__ void k_fq_pair_end(u8* __restrict__ text, u64 end1, u64 end2, u32* __restrict__ nl) {
+    const u64 e = threadIdx.x == 0 ? end1 : end2;      // (~0: the region is empty)
+    if (threadIdx.x < 2 && e != ~0ull && text[e - 1] != '\n') { text[e] = '\n'; atomicAdd(&nl[e / FQ_BLOCK], 1u); }
+}
+// line starts of both regions in one launch (k_fq_lines per region): workgroups [0, nb1) take region 1's cells, the others region 2's;
+// line j of region r starts at lines_r[j] (offsets in the slot; lines_r[0] = s_r).  blk_excl: the scanned counts from cell a1 on.
+__global__ __launch_bounds__(256) void k_fq_pair_lines(const u8* __restrict__ text, u32 a1, u32 nb1, u64 lim1, u32 a2, u64 lim2, const u32* __restrict__ blk_excl,
+                                                       u64* __restrict__ lines1, u64 s1, u64* __restrict__ lines2, u64 s2, u64 cap1, u64 cap2 /* entries of the tables */) {
+    __shared__ u32 s_w[4];
+    const bool two = blockIdx.x >= nb1;
+    const u32 cell = two ? a2 + (blockIdx.x - nb1) : a1 + blockIdx.x;
+    const u64 lim = two ? lim2 : lim1, cap = two ? cap2 : cap1;
+    u64* const ls = two ? lines2 : lines1;
+    const u64 p = (u64)cell * FQ_BLOCK + (u64)threadIdx.x * 16;
+    const int wv = threadIdx.x >> 6;
+    if (threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == nb1)) ls[0] = two ? s2 : s1;
+    u32 m = p < lim ? fq_nl16(text, p, lim) : 0u;
+    const u32 cnt = (u32)__popc(m), inc = wave_incl_scan_dpp(cnt);
+    if ((threadIdx.x & 63) == 63) s_w[wv] = inc;
+    __syncthreads();
+    u64 line = (u64)blk_excl[cell - a1] - (two ? (u64)blk_excl[a2 - a1] : 0ull) + (inc - cnt) + 1;
+    for (int w = 0; w < wv; w++) line += s_w[w];
+    while (m) { const int k = __ffs((int)m) - 1; m &= m - 1; if (line < cap) ls[line] = p + (u64)k + 1; line++; }      // (the scan counted these lines: cap is never reached)
+}
+// the first n_pairs records of both regions -> reads 2j (region 1) and 2j + 1 (region 2); a record ends at the next line start of
+// ITS region (j < n_pairs <= the region's whole records: that line exists).  ends[0..1]: where record n_pairs starts in each region
+// (the text from there on is carried over).  k_fq_records' checks and CR handling.
+__global__ __launch_bounds__(256) void k_fq_pair_records(const u8* __restrict__ text, const u64* __restrict__ lines1, const u64* __restrict__ lines2, u64 n_pairs,
+                                                          u64* __restrict__ seq_off, u64* __restrict__ qual_off, u16* __restrict__ lens, u32* __restrict__ flags /* [0]=max len, [1]=errors */,
+                                                          u64* __restrict__ ends) {
+    u32 mx = 0, err = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { ends[0] = lines1[4 * n_pairs]; ends[1] = lines2[4 * n_pairs]; }
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < 2 * n_pairs; r += (u64)gridDim.x * blockDim.x) {
+        const u64* ls = (r & 1) ? lines2 : lines1;
+        const u64 j = r >> 1;
+        u64 s0 = ls[4 * j + 1], se = ls[4 * j + 2] - 1, q0 = ls[4 * j + 3], qe = ls[4 * j + 4] - 1;
+        if (se > s0 && text[se - 1] == '\r') se--;
+        if (qe > q0 && text[qe - 1] == '\r') qe--;
+        u64 l_s = se - s0, l_q = qe - q0;
+        if (text[ls[4 * j]] != '@' || l_s != l_q) err = 1;
+        if (l_s > MLST_MAX_READ_LEN) { err |= 2; l_s = MLST_MAX_READ_LEN; }
+        seq_off[r] = s0; qual_off[r] = q0; lens[r] = (u16)l_s;
+        if ((u32)l_s > mx) mx = (u32)l_s;
+    }
+    if (mx) atomicMax(&flags[0], mx);
+    if (err) atomicOr(&flags[1], err);
+}
 // pack from text: same output format as k_pack, reads addressed by separate sequence / quality offsets; lens holds the
 // plain lengths on entry (k_fq_records)
 __global__ __launch_bounds__(256) void k_pack_text(const u8* __restrict__ text, const u64* __restrict__ seq_off, const u64* __restrict__ qual_off,
@@ -3442,6 +3495,10 @@ struct mlst_handle {
     struct BzChunk { u8* d = nullptr; u64 cap = 0; hipEvent_t ev[BZ_SUB] = {}; u64 upto[BZ_SUB] = {}; int n_ev = 0; hipEvent_t ev_used = nullptr; bool used = false; };
     BzChunk bzc[2]; int bz_chunk = 0;
     struct { bool on = false, counted = false; int slot = 0, tslot = 0, paired = 0; u64 text_bytes = 0; } bz_pend;
+    // bgzip'd mate files (mlst_submit_fastq_bgzf_pair): per file the text behind its last record whose mate has been seen (records
+    // waiting for their mates, then a partial record), on the device; `bzp` is the piece whose two regions are being inflated
+    u8* d_pc[2] = {nullptr, nullptr}; u64 cap_pc[2] = {0, 0}, pc_len[2] = {0, 0}; bool pair_open = false; u64* d_pr_meta = nullptr;
+    struct BzPair { bool on = false, counted = false; int slot = 0, tslot = 0; u32 nblk1 = 0; u64 base[2] = {0, 0}, head[2] = {0, 0}, text[2] = {0, 0}; } bzp;
     u32 depth_cap = 0; u64* d_capbuf = nullptr; u64 cap_capcols = 0;      // depth-capped pile-up (mlst_set_depth_cap): lo, hi, thr (u64 each) and cnt (u32) per column
     u32* d_counts = nullptr; u64 cap_counts = 0;
     // device-side typing (mlst_typing_enqueue / mlst_typing_fetch): fixed column layout, one slot of loc_maxlen columns per locus
@@ -3486,6 +3543,7 @@ static int fail(mlst_handle* h, int code, const char* fmt, ...) {
 #define HIPCHK(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(h, MLST_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
 
 static int bz_flush(mlst_handle* h);      // BGZF input: the piece still being inflated is parsed and submitted (defined with mlst_submit_fastq_bgzf)
+static int bzp_finish(mlst_handle* h, bool whole, uint64_t* n_reads_out);      // the same for a piece of two mate files (mlst_submit_fastq_bgzf_pair)
 static void bz_free(mlst_handle* h);
 template <typename T> static hipError_t dmalloc(T** p, u64 n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
 template <typename T> static hipError_t dmalloc(GP<T>* p, u64 n) { return hipMalloc((void**)&p->p, (n ? n : 1) * sizeof(T)); }
@@ -3637,6 +3695,7 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     if (h->copy_stream) hipStreamDestroy(h->copy_stream);
     hipFree(h->d_cand); hipFree(h->d_in_bases); hipFree(h->d_in_quals); hipFree(h->d_in_off);
     hipFree(h->d_fq_slot[0]); hipFree(h->d_fq_slot[1]); hipFree(h->d_fq_nl[0]); hipFree(h->d_fq_nl[1]); hipFree(h->d_fq_blk); hipFree(h->d_fq_lines); hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); hipFree(h->d_fq_meta);
+    hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta);
     hipFree(h->d_bgzf); hipFree(h->d_bgzf_blk); hipFree(h->d_fq_carry); h->d_bgzf = nullptr; h->d_bgzf_blk = nullptr; h->d_fq_carry = nullptr; h->cap_bgzf = h->cap_bgzf_blk = h->cap_fq_carry = h->fq_carry_len = 0;
     hipFree(h->d_packed); hipFree(h->d_qrows); hipFree(h->d_lens); hipFree(h->d_counts); hipFree(h->d_dist); hipFree(h->d_query);
     for (auto* g : {&h->g_submit, &h->g_typing}) if (g->exec) hipGraphExecDestroy(g->exec);
@@ -3653,6 +3712,7 @@ static int reset_sample_state(mlst_handle* h) {
     HIPCHK(h, hipMemsetAsync(h->d_stats + h->off_first, 0xFF, h->stats_bytes - h->off_first, h->stream));
     if (h->d_acc64 && h->n_alleles) HIPCHK(h, hipMemsetAsync(h->d_acc64, 0, (u64)h->n_alleles * 8, h->stream));      // (zero after every complete submission already: k_accumulate; this is for one that was cut short)
     h->reads_seen = 0; h->fq_carry_len = 0; h->max_wpr = 0;
+    h->pc_len[0] = h->pc_len[1] = 0; h->pair_open = false;      // (mlst_submit_fastq_bgzf_pair: both files' carries)
     return MLST_OK;
 }
 
@@ -4178,7 +4238,7 @@ extern "C" int mlst_reset_sample(mlst_handle* h) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     hipSetDevice(h->device);
     drain_events(h);
-    if (h->bz_pend.on) { if (h->infl_stream) hipStreamSynchronize(h->infl_stream); h->bz_pend.on = false; }      // a BGZF piece still open belongs to the sample that is dropped
+    if (h->bz_pend.on || h->bzp.on) { if (h->infl_stream) hipStreamSynchronize(h->infl_stream); h->bz_pend.on = false; h->bzp.on = false; }      // a BGZF piece still open belongs to the sample that is dropped
     return reset_sample_state(h);
 }
 
@@ -4445,6 +4505,7 @@ static int next_text_slot(mlst_handle* h, u64 bytes) {
     return MLST_OK;
 }
 
+static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, int paired, uint64_t* n_reads_out);
 // FASTQ text in h->d_fq_text[0 .. n_bytes) -> packed reads -> pass 1.  whole: the text consists of whole records; else
 // the partial record at its end is kept (h->d_fq_carry) for the next chunk.
 // pair_boundary != 0 (whole text only): the text is two mate files back to back, the second starting at that byte; both
@@ -4508,7 +4569,12 @@ static int fastq_pipeline(mlst_handle* h, u64 n_bytes, int paired, bool whole, u
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (flags[1] & 2) return fail(h, MLST_E_LIMIT, "a FASTQ read is longer than %d bases", MLST_MAX_READ_LEN);
     if (flags[1] & 1) return fail(h, MLST_E_INVALID, "malformed FASTQ: a record does not start with '@' or its sequence and quality lengths differ");
-    u32 max_len = flags[0];
+    return fq_pack_submit(h, n_reads, flags[0], tslot, paired, n_reads_out);
+}
+// the tail of a FASTQ parse: k_fq_records (or k_fq_pair_records) wrote n_reads lengths into d_lens, the longest is max_len;
+// the reads of h->d_fq_text are packed and submitted, and the text slot tslot is free again for its next piece
+static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, int paired, uint64_t* n_reads_out) {
+    int rc = MLST_OK;
     u32 wpr = (max_len + 15) / 16; if (wpr < 2) wpr = 2; wpr = (wpr + 1) & ~1u;
     u32 qstride = (max_len + 7) & ~7u; if (qstride < 8) qstride = 8;
     {   // k_fq_records wrote the lengths into d_lens; growing the pack buffers must keep them
@@ -4699,6 +4765,7 @@ extern "C" int mlst_free_host(void* p) {
 extern "C" int mlst_submit_fastq(mlst_handle* h, const uint8_t* text, uint64_t n_bytes, int paired, uint64_t* n_reads_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
     if (n_reads_out) *n_reads_out = 0;
     if (n_bytes == 0) return MLST_OK;
     if (!text) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -4715,6 +4782,7 @@ extern "C" int mlst_submit_fastq(mlst_handle* h, const uint8_t* text, uint64_t n
 extern "C" int mlst_submit_fastq_stream(mlst_handle* h, const uint8_t* text, uint64_t n_bytes, int final_chunk, int paired, uint64_t* n_reads_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
     if (n_reads_out) *n_reads_out = 0;
     if (n_bytes && !text) return fail(h, MLST_E_INVALID, "NULL argument");
     const u64 total = h->fq_carry_len + n_bytes;
@@ -4732,6 +4800,7 @@ extern "C" int mlst_submit_fastq_stream(mlst_handle* h, const uint8_t* text, uin
 extern "C" int mlst_submit_fastq_pair(mlst_handle* h, const uint8_t* text1, uint64_t n1, const uint8_t* text2, uint64_t n2, uint64_t* n_reads_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
     if (n_reads_out) *n_reads_out = 0;
     if (n1 == 0 && n2 == 0) return MLST_OK;
     if (!text1 || !text2 || n1 == 0 || n2 == 0) return fail(h, MLST_E_INVALID, "mate files hold different numbers of records (one chunk is empty)");
@@ -4874,7 +4943,10 @@ static int bz_finish(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
     return fastq_pipeline(h, skip + carry + h->bz_pend.text_bytes, h->bz_pend.paired, whole, n_reads_out, 0, h->bz_pend.tslot, skip, counts, FQ_HEAD - base);
 }
 // a piece that is still open is finished (its trailing partial record stays in the carry, as after any non-final chunk)
-static int bz_flush(mlst_handle* h) { return h->bz_pend.on ? bz_finish(h, false, nullptr) : MLST_OK; }
+static int bz_flush(mlst_handle* h) {
+    if (h->bzp.on) { int rc = bzp_finish(h, false, nullptr); if (rc) return rc; }      // (a piece of mate files: its unpaired records stay in the carries)
+    return h->bz_pend.on ? bz_finish(h, false, nullptr) : MLST_OK;
+}
 static void bz_free(mlst_handle* h) {
     if (h->infl_stream) hipStreamSynchronize(h->infl_stream);
     for (auto& B : h->bz) {
@@ -4890,7 +4962,7 @@ static void bz_free(mlst_handle* h) {
         C = mlst_handle::BzChunk();
     }
     if (h->infl_stream) { hipStreamDestroy(h->infl_stream); h->infl_stream = nullptr; }
-    h->bz_pend.on = false;
+    h->bz_pend.on = false; h->bzp.on = false;
 }
 // The inflate stream is NOT tied to the engine's CU share (mlst_set_cu_partition): k_inflate_tok decodes one block per LANE and
 // is bound by the latency of one wave per CU -- on a quarter of the CUs a piece of 16,384 blocks takes four turns instead of one.
@@ -4953,6 +5025,7 @@ static int bz_piece(mlst_handle* h, mlst_handle::BzChunk& C, u64 lo, u64 hi, con
 extern "C" int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, int final_chunk, int paired, uint64_t* n_reads_out,
                                       uint64_t* n_consumed_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
     if (n_reads_out) *n_reads_out = 0;
     if (n_consumed_out) *n_consumed_out = 0;
     if (n_bytes && !data) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -5074,6 +5147,232 @@ extern "C" int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint6
         if (err[0]) return fail(h, MLST_E_INVALID, "corrupt deflate data in BGZF block %u of the chunk (code %u)", err[0] - 1, err[1]);
     }
     return fastq_pipeline(h, text_bytes, paired, final_chunk != 0, n_reads_out);
+}
+
+// ---- bgzip'd mate files (mlst_submit_fastq_bgzf_pair).  A call's blocks of BOTH files go into one block list and one inflate
+// launch sequence, written into two regions of one text slot; the piece is then finished as in bz_piece / bz_finish (copy stream,
+// inflate stream, the piece before parsed on the engine's stream meanwhile), except that the parse cuts the two regions at the
+// same record number k = min(records of region 1, records of region 2): record j of each becomes reads 2j / 2j + 1, and what lies
+// behind record k in each region (records of the file that is ahead, then its partial record) is copied device to device into that
+// file's carry, to go in front of the file's text in the next piece.  A region's head room is sized when its piece is queued,
+// before the piece in front of it has been cut: by what its carry can be at most (the carry now + that piece's text of the file).
+// Slot layout: region 1 = [0, end1]: head room head[0], then the text; region 2 starts at the cell behind end1 (so the newline
+// counts k_inflate_ptr keeps per FQ_BLOCK cell belong to one region each).
+static void bzp_clear(mlst_handle* h) {
+    if (h->infl_stream) hipStreamSynchronize(h->infl_stream);
+    hipStreamSynchronize(h->stream);      // (a piece cut short may have left copies out of its slot queued)
+    h->bzp.on = false; h->pc_len[0] = h->pc_len[1] = 0; h->pair_open = false;
+}
+static int bzp_finish_impl(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
+    if (n_reads_out) *n_reads_out = 0;
+    if (!h->bzp.on) return MLST_OK;
+    const mlst_handle::BzPair P = h->bzp;
+    h->bzp.on = false;
+    mlst_handle::BzSlot& B = h->bz[P.slot];
+    HIPCHK(h, hipEventSynchronize(B.ev_inflated));
+    if (B.h_err[0]) {
+        const u32 b = B.h_err[0] - 1; const int f = b < P.nblk1 ? 1 : 2;
+        return fail(h, MLST_E_INVALID, "corrupt deflate data in BGZF block %u of file %d in the chunk (code %u)", f == 1 ? b : b - P.nblk1, f, B.h_err[1]);
+    }
+    u8* const slot = h->d_fq_slot[P.tslot];
+    u32* const nl = h->d_fq_nl[P.tslot];
+    u64 s[2], e[2]; u32 a[2], hc[2], ce[2];
+    for (int r = 0; r < 2; r++) {
+        const u64 c = h->pc_len[r];
+        if (c > P.head[r]) return fail(h, MLST_E_LIMIT, "the records of mate file %d waiting for their mates (%llu bytes) do not fit in front of its next piece", r + 1, (unsigned long long)c);
+        s[r] = P.base[r] + P.head[r] - c; e[r] = P.base[r] + P.head[r] + P.text[r];
+        a[r] = (u32)(s[r] / FQ_BLOCK);                                  // the region's first cell
+        hc[r] = (u32)((P.base[r] + P.head[r]) / FQ_BLOCK) - a[r];      // its cells without inflated text (filler + carry)
+        ce[r] = (u32)(e[r] / FQ_BLOCK) + 1;                            // behind its last cell (the one of byte end_r)
+        if (c) HIPCHK(h, hipMemcpyAsync(slot + s[r], h->d_pc[r], c, hipMemcpyDeviceToDevice, h->stream));
+        if (s[r] > (u64)a[r] * FQ_BLOCK) HIPCHK(h, hipMemsetAsync(slot + (u64)a[r] * FQ_BLOCK, 'X', s[r] - (u64)a[r] * FQ_BLOCK, h->stream));
+        HIPCHK(h, hipMemsetAsync(slot + e[r], 'X', 1, h->stream));
+    }
+    if (whole) hipLaunchKernelGGL(k_fq_pair_end, dim3(1), dim3(64), 0, h->stream, slot, e[0] > s[0] ? e[0] : ~0ull, e[1] > s[1] ? e[1] : ~0ull, nl);
+    Prof pf(h, 6);
+    for (int r = 0; r < 2; r++) {      // the cells the inflate did not count (all of them when it counted none)
+        const u32 n = P.counted ? hc[r] : ce[r] - a[r];
+        if (n) hipLaunchKernelGGL(k_fq_count, dim3(n), dim3(256), 0, h->stream, slot + (u64)a[r] * FQ_BLOCK, P.counted ? (u64)n * FQ_BLOCK : e[r] + 1 - (u64)a[r] * FQ_BLOCK, nl + a[r]);
+    }
+    HIPCHK(h, hipMemsetAsync(h->d_pr_meta, 0, 32, h->stream));
+    hipLaunchKernelGGL(k_fq_scan, dim3(1), dim3(1024), 0, h->stream, nl + a[0], ce[1] - a[0], h->d_pr_meta, (u64)0, (const u8*)slot, 0);
+    u64 n_lines = 0; u32 n1 = 0;      // newlines of both regions, of region 1 (one host synchronisation for both)
+    HIPCHK(h, hipMemcpyAsync(&n_lines, h->d_pr_meta, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&n1, nl + a[1], 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (n_lines >= (1ull << 32)) return fail(h, MLST_E_LIMIT, "more than 2^32 lines in one FASTQ chunk");
+    if (n1 > n_lines) return fail(h, MLST_E_HIP, "FASTQ line counts inconsistent");
+    const u64 nn[2] = {n1, n_lines - n1}, rec[2] = {nn[0] / 4, nn[1] / 4};
+    if (whole) {
+        for (int r = 0; r < 2; r++)
+            if (nn[r] % 4) return fail(h, MLST_E_INVALID, "mate file %d does not end with a whole record (%llu lines behind the last record paired)", r + 1, (unsigned long long)nn[r]);
+        if (rec[0] != rec[1]) return fail(h, MLST_E_INVALID, "mate files hold different numbers of records (file %d holds %llu more)", rec[0] > rec[1] ? 1 : 2,
+                                          (unsigned long long)(rec[0] > rec[1] ? rec[0] - rec[1] : rec[1] - rec[0]));
+    }
+    const u64 k = std::min(rec[0], rec[1]);
+    u64 cut[2] = {s[0], s[1]};      // where record k starts in each region
+    h->d_fq_text = slot;
+    if (h->cap_fq_lines < n_lines + 4) { hipFree(h->d_fq_lines); h->d_fq_lines = nullptr; HIPCHK(h, dmalloc(&h->d_fq_lines, n_lines + 4)); h->cap_fq_lines = n_lines + 4; }
+    u64* const lines1 = h->d_fq_lines; u64* const lines2 = h->d_fq_lines + n1 + 2;
+    u32 flags[2] = {0, 0};
+    if (k) {
+        hipLaunchKernelGGL(k_fq_pair_lines, dim3((ce[0] - a[0]) + (ce[1] - a[1])), dim3(256), 0, h->stream, (const u8*)slot, a[0], ce[0] - a[0], e[0] + 1, a[1], e[1] + 1,
+                           (const u32*)(nl + a[0]), lines1, s[0], lines2, s[1], (u64)n1 + 1, nn[1] + 1);
+        const u64 n_reads = 2 * k;
+        if (h->cap_fq_reads < n_reads) { hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); h->d_fq_soff = h->d_fq_qoff = nullptr;
+                                         HIPCHK(h, dmalloc(&h->d_fq_soff, n_reads)); HIPCHK(h, dmalloc(&h->d_fq_qoff, n_reads)); h->cap_fq_reads = n_reads; }
+        int rc = ensure_pack_buffers(h, n_reads, 2, 8); if (rc) return rc;
+        hipLaunchKernelGGL(k_fq_pair_records, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)slot, (const u64*)lines1, (const u64*)lines2, k,
+                           h->d_fq_soff, h->d_fq_qoff, h->d_lens, reinterpret_cast<u32*>(h->d_pr_meta + 1), h->d_pr_meta + 2);
+        u64 back[3] = {0, 0, 0};      // flags, then the two cuts
+        HIPCHK(h, hipMemcpyAsync(back, h->d_pr_meta + 1, 24, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        memcpy(flags, &back[0], 8); cut[0] = back[1]; cut[1] = back[2];
+        if (flags[1] & 2) return fail(h, MLST_E_LIMIT, "a FASTQ read is longer than %d bases", MLST_MAX_READ_LEN);
+        if (flags[1] & 1) return fail(h, MLST_E_INVALID, "malformed FASTQ: a record does not start with '@' or its sequence and quality lengths differ");
+    }
+    for (int r = 0; r < 2; r++) {      // the text behind record k waits for the next piece of its file
+        if (cut[r] < s[r] || cut[r] > e[r] + 1) return fail(h, MLST_E_HIP, "FASTQ line table inconsistent");
+        const u64 c = cut[r] < e[r] ? e[r] - cut[r] : 0;
+        if (c > h->cap_pc[r]) {
+            HIPCHK(h, hipStreamSynchronize(h->stream));      // (the old carry was copied into this slot above)
+            hipFree(h->d_pc[r]); h->d_pc[r] = nullptr; h->cap_pc[r] = 0;
+            const u64 cap = c + c / 4 + 4096;
+            if (dmalloc(&h->d_pc[r], cap) != hipSuccess) { (void)hipGetLastError(); return fail(h, MLST_E_LIMIT, "the records of mate file %d waiting for their mates (%llu bytes) cannot be kept on the device", r + 1, (unsigned long long)c); }
+            h->cap_pc[r] = cap;
+        }
+        if (c) HIPCHK(h, hipMemcpyAsync(h->d_pc[r], slot + cut[r], c, hipMemcpyDeviceToDevice, h->stream));
+        h->pc_len[r] = c;
+    }
+    if (!k) { HIPCHK(h, hipEventRecord(h->ev_packed[P.tslot], h->stream)); return MLST_OK; }
+    return fq_pack_submit(h, 2 * k, flags[0], P.tslot, 1, n_reads_out);
+}
+static int bzp_finish(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
+    const int rc = bzp_finish_impl(h, whole, n_reads_out);
+    if (rc) bzp_clear(h);      // an error ends the stream: neither carry outlives it
+    return rc;
+}
+// the whole BGZF blocks of one file's buffer -> blks (in_off + in_base, out_off from 0 on in the file's region); n_bytes is cut back
+// to the last whole block when may_cut (a non-final buffer whose caller asked how much was taken)
+static int bzp_list(mlst_handle* h, const u8* data, u64& n_bytes, bool may_cut, u64 in_base, int file, std::vector<BgzfBlk>& blks, u64& text) {
+    text = 0;
+    std::vector<BzHdr> hdr; u64 walked = 0;
+    bgzf_walk_parallel(data, n_bytes, hdr, walked, nullptr);
+    size_t hi_ = 0;
+    for (u64 off = 0; off < n_bytes; ) {
+        u64 total, coff, clen; u32 isize;
+        if (hi_ < hdr.size()) { const BzHdr& q = hdr[hi_++]; off = q.off; total = q.total; coff = q.coff; clen = q.clen; isize = q.isize; }
+        else if (off < walked) { off = walked; continue; }
+        else if (!bgzf_block(data + off, n_bytes - off, total, coff, clen, isize)) {
+            const bool cut = n_bytes - off < 18 || (data[off] == 0x1f && data[off + 1] == 0x8b && data[off + 2] == 8 && (data[off + 3] & 4));
+            if (may_cut && cut) { n_bytes = off; break; }
+            return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu of file %d in the chunk", (unsigned long long)off, file);
+        }
+        if (isize > 65536) return fail(h, MLST_E_INVALID, "BGZF block at byte %llu of file %d claims %u bytes of data", (unsigned long long)off, file, isize);
+        if (isize) { BgzfBlk b; b.in_off = in_base + off + coff; b.in_len = (u32)clen; b.out_off = text; b.out_len = isize; blks.push_back(b); text += isize; }
+        off += total;
+    }
+    if (text >= (1ull << 38)) return fail(h, MLST_E_LIMIT, "FASTQ chunk too large");
+    return MLST_OK;
+}
+static int bzp_submit(mlst_handle* h, const u8* data1, u64 n1, const u8* data2, u64 n2, bool final_chunk, uint64_t* n_reads_out, uint64_t* n_consumed1_out, uint64_t* n_consumed2_out) {
+    const bool piped = bz_mode(h) != 0;
+    if (piped) { int rc = bz_stream(h); if (rc) return rc; if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking)); }
+    hipStream_t const st = piped ? h->infl_stream : h->stream, cs = piped ? h->copy_stream : h->stream;      // (serial: everything on the engine's stream)
+    // both buffers on their way before their block headers are walked (file 2's from a 256-byte boundary on)
+    const u64 off2 = (n1 + 255) & ~(u64)255, n_all = off2 + n2;
+    mlst_handle::BzChunk* C = nullptr;
+    if (n_all) {
+        C = &h->bzc[h->bz_chunk ^= 1];
+        if (!C->ev_used) { HIPCHK(h, hipEventCreateWithFlags(&C->ev_used, hipEventDisableTiming)); for (auto& ev : C->ev) HIPCHK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming)); }
+        if (C->cap < n_all) {
+            if (C->used) HIPCHK(h, hipEventSynchronize(C->ev_used));
+            hipFree(C->d); C->d = nullptr; C->cap = 0;
+            HIPCHK(h, dmalloc(&C->d, n_all + n_all / 8 + 32)); C->cap = n_all + n_all / 8;
+        }
+        if (C->used) HIPCHK(h, hipStreamWaitEvent(cs, C->ev_used, 0));
+        if (n1) HIPCHK(h, hipMemcpyAsync(C->d, data1, n1, hipMemcpyHostToDevice, cs));
+        if (n2) HIPCHK(h, hipMemcpyAsync(C->d + off2, data2, n2, hipMemcpyHostToDevice, cs));
+        HIPCHK(h, hipEventRecord(C->ev[0], cs)); C->upto[0] = n_all; C->n_ev = 1;
+    }
+    struct CopyGuard { hipStream_t s; bool on; ~CopyGuard() { if (on) hipStreamSynchronize(s); } } copy_guard{cs, C != nullptr};
+    std::vector<BgzfBlk> blks; u64 t1 = 0, t2 = 0;
+    { int rc = bzp_list(h, data1, n1, n_consumed1_out && !final_chunk, 0, 1, blks, t1); if (rc) return rc; }
+    const u32 nblk1 = (u32)blks.size();
+    { int rc = bzp_list(h, data2, n2, n_consumed2_out && !final_chunk, off2, 2, blks, t2); if (rc) return rc; }
+    if (n_consumed1_out) *n_consumed1_out = n1;
+    if (n_consumed2_out) *n_consumed2_out = n2;
+    if (!h->d_pr_meta) HIPCHK(h, dmalloc(&h->d_pr_meta, (u64)4));
+    uint64_t done = 0, got = 0;
+    h->pair_open = true;
+    if (blks.empty() && !final_chunk) {      // nothing new: the open piece (if any) is finished
+        { int rc = bzp_finish(h, false, &got); if (rc) return rc; }
+        if (n_reads_out) *n_reads_out = got;
+        return MLST_OK;
+    }
+    // the new piece: head room per region for the most its file can carry into it
+    mlst_handle::BzPair P;
+    for (int r = 0; r < 2; r++) { const u64 most = h->pc_len[r] + (h->bzp.on ? h->bzp.text[r] : 0); P.head[r] = (most + FQ_BLOCK - 1) & ~(u64)(FQ_BLOCK - 1); }
+    P.text[0] = t1; P.text[1] = t2; P.nblk1 = nblk1;
+    P.base[0] = 0; P.base[1] = (P.head[0] + t1 + 1 + FQ_BLOCK - 1) & ~(u64)(FQ_BLOCK - 1);
+    const u64 slot_bytes = P.base[1] + P.head[1] + t2 + 1 + FQ_BLOCK;
+    if (slot_bytes >= (1ull << 40)) return fail(h, MLST_E_LIMIT, "FASTQ chunk too large (the records waiting for their mates included)");
+    for (u32 i = 0; i < (u32)blks.size(); i++) blks[i].out_off += i < nblk1 ? P.head[0] : P.base[1] + P.head[1];
+    const int sl = h->bz_slot ^= 1;
+    mlst_handle::BzSlot& B = h->bz[sl];
+    if (!B.ev_copied) { HIPCHK(h, hipEventCreateWithFlags(&B.ev_copied, hipEventDisableTiming)); HIPCHK(h, hipEventCreateWithFlags(&B.ev_inflated, hipEventDisableTiming));
+                        HIPCHK(h, dmalloc(&B.d_err, (u64)16)); HIPCHK(h, hipHostMalloc((void**)&B.h_err, 64, hipHostMallocDefault)); }
+    if (B.cap_blk < blks.size()) {
+        hipFree(B.d_blk); B.d_blk = nullptr; if (B.h_blk) { hipHostFree(B.h_blk); B.h_blk = nullptr; }
+        const u64 cap = blks.size() + blks.size() / 8;
+        BgzfBlk* pb = nullptr; HIPCHK(h, dmalloc(&pb, cap)); B.d_blk = pb;
+        HIPCHK(h, hipHostMalloc(&B.h_blk, cap * sizeof(BgzfBlk), hipHostMallocDefault));
+        B.cap_blk = cap;
+    }
+    {   int rc = next_text_slot(h, slot_bytes);
+        if (rc && (h->pc_len[0] || h->pc_len[1]))
+            return fail(h, MLST_E_LIMIT, "no room on the device for a piece of mate files with the records waiting for their mates (%llu + %llu bytes carried)",
+                        (unsigned long long)h->pc_len[0], (unsigned long long)h->pc_len[1]);
+        if (rc) return rc; }
+    P.tslot = h->fq_slot; P.slot = sl;
+    if (!h->inflate_mode) { const char* ev = getenv("MLST_INFLATE_MODE"); h->inflate_mode = ev ? atoi(ev) : 2; if (h->inflate_mode != 1 && h->inflate_mode != 2) h->inflate_mode = 2; }
+    P.counted = h->inflate_mode == 2 && !getenv("MLST_BGZF_NOCOUNT");
+    if (!blks.empty()) {
+        memcpy(B.h_blk, blks.data(), blks.size() * sizeof(BgzfBlk));
+        HIPCHK(h, hipMemcpyAsync(B.d_blk, B.h_blk, blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice, st));
+    }
+    if (C && piped) HIPCHK(h, hipStreamWaitEvent(st, C->ev[0], 0));
+    HIPCHK(h, hipStreamWaitEvent(st, h->ev_packed[P.tslot], 0));      // the text slot's last reader
+    HIPCHK(h, hipMemsetAsync(B.d_err, 0, 64, st));
+    HIPCHK(h, hipMemsetAsync(h->d_fq_nl[P.tslot], 0, (slot_bytes / FQ_BLOCK + 2) * 4, st));
+    if (!blks.empty()) { int rc = launch_inflate(h, C->d, C->cap + 16, (const BgzfBlk*)B.d_blk, (u32)blks.size(), h->d_fq_slot[P.tslot], B.d_err, nullptr, st,
+                                                 P.counted ? h->d_fq_nl[P.tslot] : nullptr); if (rc) return rc; }
+    HIPCHK(h, hipMemcpyAsync(B.h_err, B.d_err, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipEventRecord(B.ev_inflated, st));
+    if (C) { HIPCHK(h, hipEventRecord(C->ev_used, st)); C->used = true; }
+    // the piece before this one while the GPU inflates this one (serial: there is none), then this one if it is the last
+    { int rc = bzp_finish(h, false, &got); if (rc) return rc; done += got; }
+    P.on = true; h->bzp = P;
+    if (final_chunk || !piped) { int rc = bzp_finish(h, final_chunk, &got); if (rc) return rc; done += got; }
+    if (final_chunk) h->pair_open = false;
+    if (n_reads_out) *n_reads_out = done;
+    copy_guard.on = false;
+    HIPCHK(h, hipStreamSynchronize(cs));      // data1 / data2 may be released by the caller after this
+    return MLST_OK;
+}
+extern "C" int mlst_submit_fastq_bgzf_pair(mlst_handle* h, const uint8_t* data1, uint64_t n1, const uint8_t* data2, uint64_t n2, int final_chunk,
+                                           uint64_t* n_reads_out, uint64_t* n_consumed1_out, uint64_t* n_consumed2_out) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    if (n_reads_out) *n_reads_out = 0;
+    if (n_consumed1_out) *n_consumed1_out = 0;
+    if (n_consumed2_out) *n_consumed2_out = 0;
+    if ((n1 && !data1) || (n2 && !data2)) return fail(h, MLST_E_INVALID, "NULL argument");
+    if (n1 >= (1ull << 36) || n2 >= (1ull << 36)) return fail(h, MLST_E_LIMIT, "BGZF chunk too large");
+    hipSetDevice(h->device);
+    if (h->bz_pend.on || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    const int rc = bzp_submit(h, data1, n1, data2, n2, final_chunk != 0, n_reads_out, n_consumed1_out, n_consumed2_out);
+    if (rc) bzp_clear(h);
+    return rc;
 }
 
 // k_inflate itself on whole BGZF blocks, text back to the host: the test hook of the DEVICE decoder (tests/test_inflate.py

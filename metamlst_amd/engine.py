@@ -89,6 +89,8 @@ def load_library(path: str | None = None):
         "mlst_submit_reads": (C.c_int, [H, u8p, u8p, u64p, C.c_uint64, C.c_int]),
         "mlst_submit_fastq": (C.c_int, [H, u8p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
         "mlst_submit_fastq_bgzf": (C.c_int, [H, u8p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mlst_submit_fastq_bgzf_pair": (C.c_int, [H, u8p, C.c_uint64, u8p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64)]),
         "mlst_selftest_inflate": (C.c_int, [u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "mlst_selftest_inflate_canon": (C.c_int, [u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
         "mlst_debug_bgzf_walk": (C.c_int, [u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
@@ -199,6 +201,25 @@ def pinned_array(n_bytes: int) -> np.ndarray:
     return arr
 
 
+def pair_file_cuts(size1: int, size2: int, chunk_bytes: int) -> list[tuple[int, int, int, int]]:
+    """Byte ranges (lo1, hi1, lo2, hi2) of two mate files, one per call of Engine.submit_fastq_bgzf_pair_files: together about
+    chunk_bytes a call, the same fraction of each file (so both files reach the same record at about the same call however
+    differently they compress), the first call a quarter of the others.  The ranges of a file follow each other without gaps."""
+    total = size1 + size2
+    if total == 0:
+        return [(0, 0, 0, 0)]
+    chunk = max(1, int(chunk_bytes))
+    marks = [0.0]
+    step = min(1.0, chunk / 4 / total)
+    while marks[-1] < 1.0:
+        marks.append(min(1.0, marks[-1] + step))
+        step = min(1.0, chunk / total)
+    cuts = []
+    for a, b in zip(marks, marks[1:]):
+        cuts.append((int(size1 * a), int(size1 * b) if b < 1.0 else size1, int(size2 * a), int(size2 * b) if b < 1.0 else size2))
+    return cuts
+
+
 class Engine:
     """One GPU's typing engine.  Mirrors the reference's per-sample flow:
     load_reference (index) -> submit_reads* (alignment + hit accumulation) -> stats ->
@@ -304,6 +325,69 @@ class Engine:
         three waves per CU (k_inflate_tok2 holds four: 65,536 blocks a turn), and the chunk behind it is copied and inflated
         meanwhile; the library cuts a first chunk's head and a last chunk's tail off as pieces of their own (mlst_submit_fastq_bgzf)."""
         return self._submit_bgzf_pieces(path, 0, os.path.getsize(path), chunk_bytes, paired, True)
+
+    def submit_fastq_bgzf_pair(self, data1, data2, final: bool) -> int:
+        """Pass 1 from the two bgzip'd files of a paired-end sample: whole BGZF blocks of file 1 and of file 2 (any number of
+        records of either), inflated and paired on the GPU (record k of one file is the mate of record k of the other, across
+        calls).  final marks the last call.  Returns the number of reads completed by this call (2 x pairs)."""
+        b1 = np.frombuffer(data1, dtype=np.uint8) if not isinstance(data1, np.ndarray) else np.ascontiguousarray(data1, np.uint8)
+        b2 = np.frombuffer(data2, dtype=np.uint8) if not isinstance(data2, np.ndarray) else np.ascontiguousarray(data2, np.uint8)
+        n = C.c_uint64()
+        self._check(self.lib.mlst_submit_fastq_bgzf_pair(self._h, _ptr(b1) if b1.size else None, b1.size, _ptr(b2) if b2.size else None, b2.size,
+                                                         int(final), C.byref(n), None, None), "mlst_submit_fastq_bgzf_pair")
+        return int(n.value)
+
+    def submit_fastq_bgzf_pair_files(self, path1: str, path2: str, chunk_bytes: int = (512 << 20) - (1 << 18)) -> int:
+        """Two bgzip'd mate files (mlst_submit_fastq_bgzf_pair), read as _submit_bgzf_pieces reads one: a reader thread stays two
+        calls ahead (fastq.raw_chunks into pooled page-locked buffers), and each file's cut-off block goes in front of its next
+        piece.  A call takes about chunk_bytes compressed bytes of the two files together, the same fraction of each file's
+        size, so that the records one file is ahead by -- which wait on the device for their mates -- stay few even when the
+        two files compress differently.  The first call takes a quarter of that: its inflate has nothing to hide behind."""
+        from .fastq import prefetch, raw_chunks, release_buffers
+        margin = 1 << 17
+        s1, s2 = os.path.getsize(path1), os.path.getsize(path2)
+        n, used1, used2 = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        if s1 + s2 == 0:
+            self._check(self.lib.mlst_submit_fastq_bgzf_pair(self._h, None, 0, None, 0, 1, C.byref(n), None, None), "mlst_submit_fastq_bgzf_pair")
+            return int(n.value)
+        cuts = pair_file_cuts(s1, s2, chunk_bytes)
+        ring1: list = []
+        ring2: list = []
+
+        def span(path, lo, hi, ring):
+            for buf, got in raw_chunks(path, hi - lo, lo, hi, margin, reuse=True, ring=ring):      # (one piece: [lo, hi))
+                return buf, got
+            return None, 0
+
+        def pieces():
+            for a1, b1, a2, b2 in cuts:
+                yield span(path1, a1, b1, ring1), span(path2, a2, b2, ring2)
+
+        total = 0
+        carry = [None, None]
+        for k, (p1, p2) in enumerate(prefetch(pieces())):
+            last = k == len(cuts) - 1
+            views = []
+            for f, (buf, got) in enumerate((p1, p2)):
+                c = 0 if carry[f] is None else carry[f].size
+                if c > margin:
+                    raise MlstError("a BGZF block of more than %d bytes?" % margin)
+                if buf is None:
+                    views.append(carry[f] if c else np.empty(0, np.uint8))
+                    continue
+                if c:
+                    buf[margin - c:margin] = carry[f]
+                views.append(buf[margin - c:margin + got])
+            v1, v2 = views
+            self._check(self.lib.mlst_submit_fastq_bgzf_pair(self._h, _ptr(v1) if v1.size else None, v1.size, _ptr(v2) if v2.size else None, v2.size,
+                                                             int(last), C.byref(n), None if last else C.byref(used1), None if last else C.byref(used2)),
+                        "mlst_submit_fastq_bgzf_pair")
+            total += int(n.value)
+            if not last:
+                carry = [v1[int(used1.value):].copy(), v2[int(used2.value):].copy()]      # (cut-off blocks: under 64 KB each)
+        release_buffers(ring1)
+        release_buffers(ring2)
+        return total
 
     def inflate_bgzf(self, data) -> bytes:
         """Test hook: whole BGZF blocks -> their text, inflated by the device kernel."""

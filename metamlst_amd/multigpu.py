@@ -122,7 +122,10 @@ def submit_fastq_shard(eng, paths: list[str], rank: int, world: int, chunk_bytes
     bgzip'd FASTQ: the same by whole BGZF blocks (fastq.bgzf_range_plan); the inflated text is resynchronised on the GPU side
     of the boundary (mlst_submit_fastq_bgzf's resync flags).
     Mate files (pairs are matched by record number): rank 0 walks the two files once and broadcasts the byte offsets of the
-    chunk pairs (fastq.pair_cuts); every rank reads the chunks whose number is its rank modulo N by offset.
+    chunk pairs (fastq.pair_cuts); every rank reads the chunks whose number is its rank modulo N by offset.  bgzip'd mate
+    files take this path too (host inflate and pairing), not the GPU pairing of one process (mlst_submit_fastq_bgzf_pair):
+    sharding them by block would need the record number at a block boundary, which only an inflate of everything in front
+    of it can give.
     gzip (one deflate stream, no random access): every rank walks the file and submits the chunks whose number is its rank
     modulo N -- the wall time of the decompression is that of one rank doing it alone either way, only host CPU is spent N
     times; bgzip the file to shard it by blocks.
