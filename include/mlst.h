@@ -134,8 +134,8 @@ int mlst_submit_fastq_pair(mlst_handle* h, const uint8_t* text1, uint64_t n1, co
  * cross PCIe, the blocks are inflated on the GPU (csrc/inflate_lane.h: one lane per block decodes the codes into tokens,
  * one workgroup per block turns tokens into bytes; csrc/inflate_wave.h for oversized blocks), the text is parsed as above.  A chunk is
  * a run of whole BGZF blocks cut anywhere between blocks; a record that straddles two chunks is completed by the next
- * call; the last chunk of a file is passed with final_chunk != 0 and must end with a whole record.  Block CRCs are
- * not verified (the inflated size is).  With n_consumed_out != NULL a non-final buffer may also end inside a block:
+ * call; the last chunk of a file is passed with final_chunk != 0 and must end with a whole record.  The inflated size of
+ * every block is checked always; its CRC-32 is checked when mlst_set_bgzf_verify is on (below; off by default).  With n_consumed_out != NULL a non-final buffer may also end inside a block:
  * the call takes the whole blocks, reports their size, and the caller passes the rest again in front of the next
  * buffer (so a reader never has to walk the block headers itself).  Plain gzip has no block structure to parallelise:
  * inflate it on the host and use mlst_submit_fastq.
@@ -164,6 +164,17 @@ int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint64_t n_bytes
  * stream is open; mlst_reset_sample and any error drop both carries. */
 int mlst_submit_fastq_bgzf_pair(mlst_handle* h, const uint8_t* data1, uint64_t n1, const uint8_t* data2, uint64_t n2, int final_chunk,
                                 uint64_t* n_reads_out, uint64_t* n_consumed1_out, uint64_t* n_consumed2_out);
+
+/* The CRC-32 in the trailer of every BGZF block (RFC 1952) against the text the block inflated to, computed on the GPU behind the
+ * decoders (csrc/bgzf_crc.h) for mlst_submit_fastq_bgzf and mlst_submit_fastq_bgzf_pair: on != 0 switches the check on.  Off by
+ * default (MLST_BGZF_CRC=1 in the environment: on for a new handle): nothing is queued for it then, and a block that inflates to
+ * the right length with wrong bytes is typed as it is.  A mismatch fails the call that finishes the block's piece, before any of
+ * the piece's reads are submitted, with MLST_E_INVALID and "CRC mismatch in BGZF block <n> of the chunk (stored 0x..., computed
+ * 0x...)" (" of file <1|2> in the chunk" on the paired entry; n counts the chunk's blocks with data); the stream ends there as
+ * after corrupt deflate data.  Blocks without data (the EOF marker) hold nothing to check.  The switch may change only while
+ * no FASTQ stream of any kind (text, BGZF, paired) is open on the handle: MLST_E_INVALID "a FASTQ stream is open" otherwise. */
+int mlst_set_bgzf_verify(mlst_handle* h, int on);
+int mlst_get_bgzf_verify(mlst_handle* h, int* on);
 
 /* Host-packed input: what crosses the link is 2-bit bases + lengths (42 bytes per 150-base read instead of the 316 of its
  * FASTQ text); the Phred rows stay on the host and only those of the reads that pass the seed sieve (one in ~400 of a

@@ -20,8 +20,14 @@ extern "C" {
 int mlst_selftest_inflate(const uint8_t* in, uint64_t n_in, uint8_t* out, uint64_t cap, uint64_t* produced);
 
 /* Test hook of the DEVICE decoder (csrc/inflate_wave.h): whole BGZF blocks in, their inflated text out (host buffers);
- * kernel_ms (optional) receives the duration of the inflate kernel alone (HIP events). */
+ * kernel_ms (optional) receives the duration of the inflate kernels alone (HIP events) -- with mlst_set_bgzf_verify on, which this
+ * hook obeys too (a mismatch fails it with the block's number), of the inflate kernels and the CRC kernel behind them. */
 int mlst_selftest_inflate_device(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, uint8_t* out, uint64_t cap, uint64_t* produced, double* kernel_ms);
+
+/* Test hook of the CRC stage (csrc/bgzf_crc.h): whole BGZF blocks in; they are inflated as by the call above and the CRC-32 that
+ * k_bgzf_crc computes of every block with data comes out, in file order, whatever the trailers say (nothing is compared).
+ * cap: room in crc_out (values); *n_blocks: values written; kernel_ms (optional): the CRC kernel alone (HIP events). */
+int mlst_selftest_bgzf_crc(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, uint32_t* crc_out, uint64_t cap, uint64_t* n_blocks, double* kernel_ms);
 
 /* The decoder of k_inflate_tok2 (csrc/inflate_canon.h: canonical limits, 800 bytes of state per stream) run on the HOST on one
  * raw deflate stream, its tokens replayed into bytes.  *left_to_other_kernel = 1: the literal / length code of a block holds

@@ -16,7 +16,7 @@ import sys
 import time
 
 from . import db as mdb
-from .engine import Engine, default_params
+from .engine import CorruptInput, Engine, crc_checked, default_params
 from .fastq import is_bgzf, mates_share_names, pair_chunks, prefetch, text_chunks, tile_fasta
 from .index import load_index
 from .merge import EngineMatcher, merge_folder
@@ -60,6 +60,10 @@ def _type_parser(sub):
     p.add_argument("--gpus", default=1, type=int,
                    help="type the sample on N GPUs of this node: one process per GPU, FASTQ chunks dealt to the ranks, the statistics "
                         "and pileup counts all-reduced over RCCL (plain or .gz FASTQ; the .nfo is byte-identical to --gpus 1)")
+    p.add_argument("--no-verify-crc", dest="verify_crc", action="store_false",
+                   help="bgzip'd input: do not check the CRC-32 of the BGZF blocks.  By default every block's text is checked against "
+                        "the CRC in its trailer before its reads are typed (on the GPU; the boundary blocks of a --gpus N shard on the "
+                        "host), as zlib, htslib and `bgzip -d` do; a mismatch ends the sample with an error and no .nfo")
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -166,6 +170,7 @@ def run_type(a, argv=None) -> int:
         print("--depth-cap orders the records of the whole sample by read index: one sample on several GPUs cannot apply it (use --gpus 1)")
         return 1
     eng = Engine(a.device, prm)
+    eng.set_bgzf_verify(a.verify_crc)
     # the built host index is kept next to the database (as the reference keeps <idx>.1.bt2: metamlst-index.py:224-225) unless a
     # species filter made this index a one-off or MLST_INDEX_CACHE=0
     ref_cache = (a.database + ".mlstref") if (not a.filter and os.environ.get("MLST_INDEX_CACHE", "1") != "0") else ""
@@ -184,6 +189,7 @@ def run_type(a, argv=None) -> int:
         for _ in range(max(0, min(int(os.environ.get("MLST_PIPELINE_DEPTH", "6")), n_mine) - 1)):
             e2 = Engine(a.device, prm)
             e2.load_reference(idx)      # (the host index is cached inside the library: an upload, not a build)
+            e2.set_bgzf_verify(a.verify_crc)
             if a.depth_cap:
                 e2.set_depth_cap(a.depth_cap)
             engines.append(e2)
@@ -211,7 +217,11 @@ def run_type(a, argv=None) -> int:
     paths = [a.READS] + extra_files + ([a.mates] if a.mates else [])
     if world > 1:      # this rank's share of the files, then the two all-reduces; rank 0 writes (metamlst_amd/multigpu.py)
         from .multigpu import submit_fastq_shard, type_sharded
-        submit_fastq_shard(eng, paths, rank, world, chunk_bytes, paired=paired)
+        try:
+            submit_fastq_shard(eng, paths, rank, world, chunk_bytes, paired=paired, verify_crc=a.verify_crc)
+        except CorruptInput as e:      # (this rank ends with an error: the command ends the others and returns its status)
+            print("rank %d: %s" % (rank, e), file=sys.stderr, flush=True)
+            os._exit(1)      # the other ranks wait in a collective: no orderly shutdown of the process group
         fileName = sample_name(a.READS)
         if rank == 0 and not os.path.isdir(a.o):
             os.mkdir(a.o)
@@ -224,7 +234,12 @@ def run_type(a, argv=None) -> int:
         dist.destroy_process_group()
         return 0
     # FASTQ text goes to the GPU as is and is parsed there (mlst_submit_fastq); a reader thread stays two chunks ahead
-    submit_sample_files(eng, paths, paired, chunk_bytes)
+    try:
+        submit_sample_files(eng, paths, paired, chunk_bytes)
+    except CorruptInput as e:      # nothing of the sample is typed: no .nfo
+        print(e, file=sys.stderr)
+        database.closeConnection()
+        return 1
     return _finish_type_device(a, eng, idx, database, targs)
 
 
@@ -262,7 +277,7 @@ def open_sample_reader(paths, paired: bool, chunk_bytes: int):
 def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader=None) -> None:
     """All reads of one sample's FASTQ file(s) into one engine (first_reader: open_sample_reader(paths, ...), if opened ahead)."""
     if paired and is_bgzf(paths[0]) and is_bgzf(paths[1]):      # bgzip'd mates: inflated and paired on the GPU
-        eng.submit_fastq_bgzf_pair_files(paths[0], paths[1])
+        crc_checked(paths, lambda: eng.submit_fastq_bgzf_pair_files(paths[0], paths[1]))
         return
     if paired:
         from .fastq import release_buffers
@@ -273,7 +288,7 @@ def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader
         return
     for k, path in enumerate(paths):
         if is_bgzf(path):      # bgzip'd FASTQ: the compressed blocks go to the GPU and are inflated there
-            eng.submit_fastq_bgzf_file(path, paired=False)
+            crc_checked([path], lambda: eng.submit_fastq_bgzf_file(path, paired=False))
             continue
         reader = first_reader if (k == 0 and first_reader is not None) else _FileReader(path, chunk_bytes)
         for chunk in reader:

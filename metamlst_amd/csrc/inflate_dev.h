@@ -18,7 +18,8 @@
 
 namespace mlst_inflate {
 
-enum { OK = 0, E_INPUT = -1, E_BLOCKTYPE = -2, E_STORED = -3, E_LENGTHS = -4, E_OUTPUT = -5, E_DISTANCE = -6, E_SYMBOL = -7, E_SHORT = -8 };
+enum { OK = 0, E_INPUT = -1, E_BLOCKTYPE = -2, E_STORED = -3, E_LENGTHS = -4, E_OUTPUT = -5, E_DISTANCE = -6, E_SYMBOL = -7, E_SHORT = -8,
+       E_CRC = -9 /* the text does not have the CRC-32 of the BGZF block's trailer (k_bgzf_crc; no decoder returns it) */ };
 
 struct Bits {
     const uint8_t* in; uint64_t n, pos;

@@ -34,6 +34,7 @@
 #include "inflate_wave.h"
 #include "inflate_lane.h"
 #include "inflate_canon.h"
+#include "bgzf_crc.h"
 #include "mlst_policy.h"
 
 typedef unsigned long long u64;
@@ -1236,6 +1237,59 @@ __global__ __launch_bounds__(1024) void k_inflate_ptr(const u8* __restrict__ com
     __shared__ __attribute__((aligned(16))) u16 s_ptr[65536];
     __shared__ u32 s_part[16]; __shared__ u32 s_nl[20];
     inflate_lane::ptr_body<1024>(comp, blk, n_blk, err_base, tok, INFL_TOK_CAP, n_tok, out, err, s_ptr, s_part, s_nl, nl, nl_shift);
+#endif
+}
+// CRC-32 of the inflated text of every block against the value in the block's trailer (csrc/bgzf_crc.h): a stage of its own behind
+// the decoders, one wave per block, four waves per workgroup sharing 16 KB of tables in LDS.  Once a decoder has reported a block
+// (err[0] set) that report stands and the WHOLE launch checks nothing -- the skip is per launch, not per block: the piece fails either
+// way, and a mismatch found by a wave that is already past the look loses the atomicCAS, as intended.  crc_out (the test hook): the
+// computed values instead of the comparison.
+__device__ const bgzf_crc::Tables g_crc_tab = bgzf_crc::make_tables();
+__global__ __launch_bounds__(256) void k_bgzf_crc(const u8* __restrict__ comp, const BgzfBlk* __restrict__ blk, u32 n_blk, const u8* __restrict__ out,
+                                                  u32* __restrict__ err /* [0] = 1 + first bad block, [1] = E_CRC, [2] = stored, [3] = computed */, u32* __restrict__ crc_out) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    using namespace bgzf_crc;
+    __shared__ u32 s_far[CHUNK * 256];
+    for (u32 k = threadIdx.x; k < CHUNK * 256; k += 256) s_far[k] = g_crc_tab.far[k];
+    __syncthreads();
+    if (!crc_out && __hip_atomic_load(&err[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    const u32 lane = threadIdx.x & 63u;
+    const u32 my_mul = g_crc_tab.lane_mul[lane];
+    const __attribute__((address_space(3))) u32* far = (const __attribute__((address_space(3))) u32*)s_far;
+    for (u32 i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6)); i < n_blk; i += gridDim.x * 4u) {
+        const u64 out_off = blk[i].out_off; const u32 n = blk[i].out_len;
+        if (n == 0 || n > 65536u) continue;
+        const u8* text = out + out_off;
+        const u32 K = (n + STRIDE - 1) / STRIDE;
+        int p = (int)n - (int)(K * STRIDE) + (int)(CHUNK * lane);      // this lane's chunk of step 0, from the block's start
+        u32 acc = 0, k = 0;
+        // the steps in which a lane's chunk lies in front of the block's fifth byte (the first, and the second of a block of 1 .. 3 bytes mod STRIDE)
+        for (; k < K && (int)n - (int)((K - k) * STRIDE) < 4; k++, p += STRIDE) {
+            if (p <= -(int)CHUNK) continue;
+            Chunk c;
+            if (p < 4) c = head_chunk(text, p); else __builtin_memcpy(&c, text + p, 16);
+            acc = step(far, acc, c);
+        }
+        for (; k + 4 <= K; k += 4, p += 4 * STRIDE) {      // four loads in flight per lane
+            Chunk c0, c1, c2, c3;
+            __builtin_memcpy(&c0, text + p, 16); __builtin_memcpy(&c1, text + p + STRIDE, 16);
+            __builtin_memcpy(&c2, text + p + 2 * STRIDE, 16); __builtin_memcpy(&c3, text + p + 3 * STRIDE, 16);
+            acc = step(far, acc, c0); acc = step(far, acc, c1); acc = step(far, acc, c2); acc = step(far, acc, c3);
+        }
+        for (; k < K; k++, p += STRIDE) { Chunk c; __builtin_memcpy(&c, text + p, 16); acc = step(far, acc, c); }
+        u32 v = mul(acc, my_mul);
+        #pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v ^= (u32)__shfl_xor((int)v, d, 64);
+        if (lane == 0) {
+            const u32 crc = finish(v, n);
+            if (crc_out) crc_out[i] = crc;
+            else {
+                const u8* t = comp + blk[i].in_off + blk[i].in_len;      // the trailer: CRC32 then ISIZE, little endian, unaligned
+                const u32 stored = (u32)t[0] | ((u32)t[1] << 8) | ((u32)t[2] << 16) | ((u32)t[3] << 24);
+                if (crc != stored && atomicCAS(&err[0], 0u, i + 1u) == 0u) { err[1] = (u32)(-mlst_inflate::E_CRC); err[2] = stored; err[3] = crc; }
+            }
+        }
+    }
 #endif
 }
 // ------------------------------------------------------------------ FASTQ text -> packed reads (GPU parser)
@@ -3488,13 +3542,16 @@ struct mlst_handle {
     // (or has been) and has not been parsed yet.
     struct BzSlot { void* d_blk = nullptr; void* h_blk = nullptr; u64 cap_blk = 0; hipEvent_t ev_copied = nullptr, ev_inflated = nullptr; u32* d_err = nullptr; u32* h_err = nullptr; };
     BzSlot bz[2]; int bz_slot = 0, bz_mode = -1; hipStream_t infl_stream = nullptr;
+    // mlst_set_bgzf_verify (MLST_BGZF_CRC sets it for a new handle): k_bgzf_crc behind the decoders of every launch_inflate.
+    // crc_hook (mlst_selftest_bgzf_crc, for the duration of its launch): the values instead of the comparison, and the kernel's two events
+    bool bgzf_verify = false; struct { u32* d_out = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr; } crc_hook;
     // the compressed bytes of a CHUNK (one call of mlst_submit_fastq_bgzf), two buffers used in turn: the copy is queued in BZ_SUB parts
     // before the chunk's block headers are walked (a cache miss per block: 8 ms for 49,152 blocks, now beside the copy), a piece's
     // inflate waits for the part that holds its last byte; ev_used: the last inflate that read the buffer
     enum { BZ_SUB = 8 };
     struct BzChunk { u8* d = nullptr; u64 cap = 0; hipEvent_t ev[BZ_SUB] = {}; u64 upto[BZ_SUB] = {}; int n_ev = 0; hipEvent_t ev_used = nullptr; bool used = false; };
     BzChunk bzc[2]; int bz_chunk = 0;
-    struct { bool on = false, counted = false; int slot = 0, tslot = 0, paired = 0; u64 text_bytes = 0; } bz_pend;
+    struct { bool on = false, counted = false; int slot = 0, tslot = 0, paired = 0; u64 text_bytes = 0; u32 blk_base = 0 /* the piece's first block in its chunk's list */; } bz_pend;
     // bgzip'd mate files (mlst_submit_fastq_bgzf_pair): per file the text behind its last record whose mate has been seen (records
     // waiting for their mates, then a partial record), on the device; `bzp` is the piece whose two regions are being inflated
     u8* d_pc[2] = {nullptr, nullptr}; u64 cap_pc[2] = {0, 0}, pc_len[2] = {0, 0}; bool pair_open = false; u64* d_pr_meta = nullptr;
@@ -3630,6 +3687,7 @@ extern "C" int mlst_create(int device, const mlst_params* p, mlst_handle** out) 
     if (hipStreamCreate(&h->stream) != hipSuccess) { delete h; return fail(nullptr, MLST_E_HIP, "cannot initialise device %d", device); }
     h->own_stream = h->stream;
     { const char* g = getenv("MLST_GRAPHS"); if (g && g[0] == '0') h->use_graphs = false; }
+    { const char* g = getenv("MLST_BGZF_CRC"); h->bgzf_verify = g && g[0] == '1'; }      // initial value of mlst_set_bgzf_verify
     { int khz = 0; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) h->wall_khz = (double)khz; }
     KParams& k = h->kp;
     k.minscore = prm.minscore; k.max_xm = prm.max_xm; k.min_read_len = prm.min_read_len; k.minqual = prm.minqual;
@@ -4711,6 +4769,15 @@ extern "C" int mlst_submit_packed_host(mlst_handle* h, const uint32_t* packed, c
 #define INFL_PASS 16384u          /* blocks per pass with k_inflate_tok: one wave (64 blocks) per CU is all its 160 KB of tables allow */
 #define INFL_PASS2 65536u         /* with k_inflate_tok2: four waves per CU (the token buffer holds 96 KB per block of a pass: 6.3 GB) */
 // d_nl (optional; two-kernel path only): newline counts per FQ_BLOCK bytes of d_out, added up while the text is written (zeroed by the caller)
+// With verification on (mlst_set_bgzf_verify) k_bgzf_crc follows the last decoder on the same stream: it reads the text whichever of
+// them wrote it, and reports through d_err like them (words 2 and 3: the stored and the computed value), so the callers' hand-over
+// (the copy of d_err, ev_inflated) covers it.  Off: nothing is queued for it.
+static void launch_bgzf_crc(mlst_handle* h, const u8* d_comp, const BgzfBlk* d_blk, u32 n_blk, const u8* d_out, u32* d_err, hipStream_t st) {
+    if (!h->bgzf_verify && !h->crc_hook.d_out) return;
+    if (h->crc_hook.e0) hipEventRecord(h->crc_hook.e0, st);
+    hipLaunchKernelGGL(k_bgzf_crc, dim3(std::min((n_blk + 3u) / 4u, 2048u)), dim3(256), 0, st, d_comp, d_blk, n_blk, d_out, d_err, h->crc_hook.d_out);
+    if (h->crc_hook.e1) hipEventRecord(h->crc_hook.e1, st);
+}
 static int launch_inflate(mlst_handle* h, const u8* d_comp, u64 comp_bytes_padded, const BgzfBlk* d_blk, u32 n_blk, u8* d_out, u32* d_err, unsigned long long* d_st, hipStream_t st = nullptr, u32* d_nl = nullptr) {
     if (n_blk == 0) return MLST_OK;
     if (!st) st = h->stream;
@@ -4718,6 +4785,7 @@ static int launch_inflate(mlst_handle* h, const u8* d_comp, u64 comp_bytes_padde
     if (h->inflate_mode == 1 || d_st) {
         if (d_nl) return fail(h, MLST_E_INVALID, "newline counts come with the two-kernel inflate only");
         hipLaunchKernelGGL(k_inflate, dim3((u32)std::min<u64>(((u64)n_blk + INFLATE_NG - 1) / INFLATE_NG, 1u << 20)), dim3(64), 0, st, d_comp, comp_bytes_padded, d_blk, n_blk, d_out, d_err, d_st, (const u32*)nullptr, 0u);
+        launch_bgzf_crc(h, d_comp, d_blk, n_blk, d_out, d_err, st);
         return MLST_OK;
     }
     // Phase 1: k_inflate_tok (tables of 9 / 8 bits, 2.3 KB per stream: ONE wave of 64 blocks per CU, 0.58 us per symbol step) or
@@ -4742,6 +4810,7 @@ static int launch_inflate(mlst_handle* h, const u8* d_comp, u64 comp_bytes_padde
         hipLaunchKernelGGL(k_inflate, dim3((u32)std::min<u64>(((u64)n + INFLATE_NG - 1) / INFLATE_NG, 1u << 20)), dim3(64), 0, st, d_comp, comp_bytes_padded, d_blk + at, n, d_out, d_err, (unsigned long long*)nullptr, (const u32*)h->d_intok, at);
         if (d_nl) hipLaunchKernelGGL(k_nl_blocks, dim3(std::min(n, 2048u)), dim3(256), 0, st, d_blk + at, n, (const u32*)h->d_intok, (const u8*)d_out, d_nl, 12u);
     }
+    launch_bgzf_crc(h, d_comp, d_blk, n_blk, d_out, d_err, st);
     return MLST_OK;
 }
 
@@ -4918,6 +4987,11 @@ extern "C" int mlst_debug_bgzf_walk(const uint8_t* data, uint64_t n_bytes, uint6
 //   (3) waits for the copy of piece k (the caller owns `data` again on return).
 // The last call (final_chunk) finishes its own piece as well; every other entry that looks at the sample's state finishes a
 // piece that is still open first (bz_flush).  n_reads_out counts the records completed by the call (those of piece k - 1).
+// what a piece's error words say (d_err of launch_inflate): a decoder's code, or k_bgzf_crc's with the two values.  where: " of the chunk", ...
+static int bz_fail(mlst_handle* h, const u32* e, u32 block, const char* where) {
+    if (e[1] == (u32)(-mlst_inflate::E_CRC)) return fail(h, MLST_E_INVALID, "CRC mismatch in BGZF block %u%s (stored 0x%08x, computed 0x%08x)", block, where, e[2], e[3]);
+    return fail(h, MLST_E_INVALID, "corrupt deflate data in BGZF block %u%s (code %u)", block, where, e[1]);
+}
 #define FQ_HEAD (1ull << 20)      /* room in front of an inflated piece for the partial record of the piece before it */
 static int bz_mode(mlst_handle* h) {
     if (h->bz_mode < 0) { const char* e = getenv("MLST_BGZF_PIPE"); h->bz_mode = (e && e[0] == '0') ? 0 : 1; }
@@ -4930,7 +5004,7 @@ static int bz_finish(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
     h->bz_pend.on = false;
     mlst_handle::BzSlot& B = h->bz[h->bz_pend.slot];
     HIPCHK(h, hipEventSynchronize(B.ev_inflated));
-    if (B.h_err[0]) { h->fq_carry_len = 0; return fail(h, MLST_E_INVALID, "corrupt deflate data in BGZF block %u of the chunk (code %u)", B.h_err[0] - 1, B.h_err[1]); }
+    if (B.h_err[0]) { h->fq_carry_len = 0; return bz_fail(h, B.h_err, h->bz_pend.blk_base + B.h_err[0] - 1, " of the chunk"); }
     const u64 carry = h->fq_carry_len;
     if (carry + 256 > FQ_HEAD) { h->fq_carry_len = 0; return fail(h, MLST_E_LIMIT, "a FASTQ record of more than %llu bytes", (unsigned long long)(FQ_HEAD - 256)); }
     u8* slot = h->d_fq_slot[h->bz_pend.tslot];
@@ -4974,7 +5048,7 @@ static int bz_stream(mlst_handle* h) {
 
 // One piece through the three stages: its copy and inflate are queued, the piece before it is finished meanwhile (and, for the last
 // piece of a stream, the piece itself).  blks: the piece's blocks, in_off relative to `data`, out_off from FQ_HEAD on.
-static int bz_piece(mlst_handle* h, mlst_handle::BzChunk& C, u64 lo, u64 hi, const std::vector<BgzfBlk>& blks, u64 text_end, int paired, bool final_piece, uint64_t* done) {
+static int bz_piece(mlst_handle* h, mlst_handle::BzChunk& C, u64 lo, u64 hi, const std::vector<BgzfBlk>& blks, u32 blk_base, u64 text_end, int paired, bool final_piece, uint64_t* done) {
     static const bool bz_trace = getenv("MLST_BGZF_TRACE") != nullptr;      // host-side time stamps of a piece's steps (stderr)
     auto bz_now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double bt0 = bz_trace ? bz_now() : 0.0;
@@ -5006,7 +5080,7 @@ static int bz_piece(mlst_handle* h, mlst_handle::BzChunk& C, u64 lo, u64 hi, con
     if (counted) HIPCHK(h, hipMemsetAsync(h->d_fq_nl[tslot], 0, (text_end / FQ_BLOCK + 2) * 4, h->infl_stream));
     { int rc = launch_inflate(h, C.d + lo, C.cap + 16 - lo, (const BgzfBlk*)B.d_blk, (u32)blks.size(), h->d_fq_slot[tslot], B.d_err, nullptr, h->infl_stream,
                               counted ? h->d_fq_nl[tslot] : nullptr); if (rc) return rc; }
-    HIPCHK(h, hipMemcpyAsync(B.h_err, B.d_err, 8, hipMemcpyDeviceToHost, h->infl_stream));
+    HIPCHK(h, hipMemcpyAsync(B.h_err, B.d_err, h->bgzf_verify ? 16 : 8, hipMemcpyDeviceToHost, h->infl_stream));
     HIPCHK(h, hipEventRecord(B.ev_inflated, h->infl_stream));
     HIPCHK(h, hipEventRecord(C.ev_used, h->infl_stream)); C.used = true;
     // piece k - 1 while the GPU inflates piece k
@@ -5014,7 +5088,7 @@ static int bz_piece(mlst_handle* h, mlst_handle::BzChunk& C, u64 lo, u64 hi, con
     const double bt1 = bz_trace ? bz_now() : 0.0;
     if (h->bz_pend.on) { rc = bz_finish(h, false, &n1); *done += n1; }
     const double bt2 = bz_trace ? bz_now() : 0.0;
-    h->bz_pend.on = true; h->bz_pend.counted = counted; h->bz_pend.slot = sl; h->bz_pend.tslot = tslot; h->bz_pend.paired = paired; h->bz_pend.text_bytes = text_end - FQ_HEAD;
+    h->bz_pend.on = true; h->bz_pend.counted = counted; h->bz_pend.slot = sl; h->bz_pend.tslot = tslot; h->bz_pend.paired = paired; h->bz_pend.text_bytes = text_end - FQ_HEAD; h->bz_pend.blk_base = blk_base;
     if (!rc && final_piece) { rc = bz_finish(h, true, &n1); *done += n1; }
     if (bz_trace) fprintf(stderr, "bgzf piece of %zu blocks at %.3f: queueing %.3f ms, piece before %.3f ms, own piece (final) %.3f ms\n",
                           blks.size(), bt0, bt1 - bt0, bt2 - bt1, bz_now() - bt2);
@@ -5120,7 +5194,7 @@ extern "C" int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint6
             const u64 t0 = sub[0].out_off - FQ_HEAD;
             for (auto& q : sub) { q.in_off -= lo; q.out_off -= t0; }
             const u64 text_end = sub.back().out_off + sub.back().out_len;
-            const int rc = bz_piece(h, *C, lo, hi, sub, text_end, paired, final_chunk != 0 && b1 == nb, &done);
+            const int rc = bz_piece(h, *C, lo, hi, sub, (u32)b0, text_end, paired, final_chunk != 0 && b1 == nb, &done);
             if (rc) return rc;
         }
         if (n_reads_out) *n_reads_out = done;
@@ -5141,10 +5215,10 @@ extern "C" int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint6
         u32* d_err = reinterpret_cast<u32*>(h->d_fq_meta + 2);
         HIPCHK(h, hipMemsetAsync(d_err, 0, 8, h->stream));
         { int rc = launch_inflate(h, h->d_bgzf, (u64)h->cap_bgzf + 16, (const BgzfBlk*)h->d_bgzf_blk, (u32)blks.size(), h->d_fq_text, d_err, nullptr); if (rc) return rc; }
-        u32 err[2] = {0, 0};
-        HIPCHK(h, hipMemcpyAsync(err, d_err, 8, hipMemcpyDeviceToHost, h->stream));
+        u32 err[4] = {0, 0, 0, 0};
+        HIPCHK(h, hipMemcpyAsync(err, d_err, h->bgzf_verify ? 16 : 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));      // also: blks / data may be released by the caller after this
-        if (err[0]) return fail(h, MLST_E_INVALID, "corrupt deflate data in BGZF block %u of the chunk (code %u)", err[0] - 1, err[1]);
+        if (err[0]) return bz_fail(h, err, err[0] - 1, " of the chunk");
     }
     return fastq_pipeline(h, text_bytes, paired, final_chunk != 0, n_reads_out);
 }
@@ -5172,7 +5246,7 @@ static int bzp_finish_impl(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
     HIPCHK(h, hipEventSynchronize(B.ev_inflated));
     if (B.h_err[0]) {
         const u32 b = B.h_err[0] - 1; const int f = b < P.nblk1 ? 1 : 2;
-        return fail(h, MLST_E_INVALID, "corrupt deflate data in BGZF block %u of file %d in the chunk (code %u)", f == 1 ? b : b - P.nblk1, f, B.h_err[1]);
+        return bz_fail(h, B.h_err, f == 1 ? b : b - P.nblk1, f == 1 ? " of file 1 in the chunk" : " of file 2 in the chunk");
     }
     u8* const slot = h->d_fq_slot[P.tslot];
     u32* const nl = h->d_fq_nl[P.tslot];
@@ -5347,7 +5421,7 @@ static int bzp_submit(mlst_handle* h, const u8* data1, u64 n1, const u8* data2, 
     HIPCHK(h, hipMemsetAsync(h->d_fq_nl[P.tslot], 0, (slot_bytes / FQ_BLOCK + 2) * 4, st));
     if (!blks.empty()) { int rc = launch_inflate(h, C->d, C->cap + 16, (const BgzfBlk*)B.d_blk, (u32)blks.size(), h->d_fq_slot[P.tslot], B.d_err, nullptr, st,
                                                  P.counted ? h->d_fq_nl[P.tslot] : nullptr); if (rc) return rc; }
-    HIPCHK(h, hipMemcpyAsync(B.h_err, B.d_err, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(B.h_err, B.d_err, h->bgzf_verify ? 16 : 8, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipEventRecord(B.ev_inflated, st));
     if (C) { HIPCHK(h, hipEventRecord(C->ev_used, st)); C->used = true; }
     // the piece before this one while the GPU inflates this one (serial: there is none), then this one if it is the last
@@ -5395,7 +5469,7 @@ extern "C" int mlst_selftest_inflate_device(mlst_handle* h, const uint8_t* data,
     if (produced) *produced = text_bytes;
     if (blks.empty()) return MLST_OK;
     u8* d_in = nullptr; u8* d_out = nullptr; BgzfBlk* d_blk = nullptr; u32* d_err = nullptr; unsigned long long* d_st = nullptr;
-    int rc = MLST_OK; u32 err[2] = {0, 0};
+    int rc = MLST_OK; u32 err[4] = {0, 0, 0, 0};
 #if defined(MLST_INFLATE_STATS)
     const bool want_stats = getenv("MLST_INFLATE_STATS") != nullptr;      // (diagnostic builds: hipcc -DMLST_INFLATE_STATS)
 #else
@@ -5415,9 +5489,9 @@ extern "C" int mlst_selftest_inflate_device(mlst_handle* h, const uint8_t* data,
         float ms = 0; if (se == hipSuccess) hipEventElapsedTime(&ms, e0, e1);
         if (kernel_ms) *kernel_ms = (double)ms;
         h->ev_pool.push_back(e0); h->ev_pool.push_back(e1);
-        if (se != hipSuccess || hipMemcpy(err, d_err, 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out, d_out, text_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        if (se != hipSuccess || hipMemcpy(err, d_err, 16, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out, d_out, text_bytes, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(h, MLST_E_HIP, "k_inflate failed: %s", hipGetErrorString(hipGetLastError()));
-        else if (err[0]) rc = fail(h, MLST_E_INVALID, "corrupt deflate data in BGZF block %u (code %u)", err[0] - 1, err[1]);
+        else if (err[0]) rc = bz_fail(h, err, err[0] - 1, "");
 #if defined(MLST_PTR_TRACE)
         { u32 tr[8] = {0}; if (hipMemcpy(tr, d_err, 32, hipMemcpyDeviceToHost) == hipSuccess)
             fprintf(stderr, "k_inflate_ptr phases over %zu blocks (units of 64 cycles): fill %u, pointer jumping %u (%u rounds), gather %u\n", blks.size(), tr[2], tr[3], tr[5], tr[4]); }
@@ -5431,6 +5505,63 @@ extern "C" int mlst_selftest_inflate_device(mlst_handle* h, const uint8_t* data,
     }
     hipFree(d_in); hipFree(d_out); hipFree(d_blk); hipFree(d_err); hipFree(d_st);
     return rc;
+}
+
+// the CRC-32 of every block with data as k_bgzf_crc computes it behind the decoders (whatever the trailers say): test hook
+extern "C" int mlst_selftest_bgzf_crc(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, uint32_t* crc_out, uint64_t cap, uint64_t* n_blocks, double* kernel_ms) {
+    if (!h) return MLST_E_INVALID;
+    if (n_blocks) *n_blocks = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (!data || !crc_out) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    std::vector<BgzfBlk> blks; u64 text_bytes = 0;
+    for (u64 off = 0; off < n_bytes; ) {
+        u64 total, coff, clen; u32 isize;
+        if (!bgzf_block(data + off, n_bytes - off, total, coff, clen, isize)) return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu", (unsigned long long)off);
+        if (isize > 65536) return fail(h, MLST_E_INVALID, "BGZF block claims %u bytes of data", isize);
+        if (isize) { BgzfBlk b; b.in_off = off + coff; b.in_len = (u32)clen; b.out_off = text_bytes; b.out_len = isize; blks.push_back(b); text_bytes += isize; }
+        off += total;
+    }
+    if (blks.size() > cap) return fail(h, MLST_E_LIMIT, "output buffer too small (%llu values needed)", (unsigned long long)blks.size());
+    if (blks.size() >= (1ull << 31)) return fail(h, MLST_E_LIMIT, "BGZF chunk too large");
+    if (n_blocks) *n_blocks = blks.size();
+    if (blks.empty()) return MLST_OK;
+    u8* d_in = nullptr; u8* d_out = nullptr; BgzfBlk* d_blk = nullptr; u32* d_err = nullptr; u32* d_crc = nullptr;
+    int rc = MLST_OK; u32 err[4] = {0, 0, 0, 0};
+    if (dmalloc(&d_in, n_bytes + 16) != hipSuccess || dmalloc(&d_out, text_bytes + 16) != hipSuccess || dmalloc(&d_blk, (u64)blks.size()) != hipSuccess || dmalloc(&d_err, (u64)8) != hipSuccess
+        || dmalloc(&d_crc, (u64)blks.size()) != hipSuccess) rc = fail(h, MLST_E_HIP, "device allocation failed");
+    if (!rc && (hipMemcpy(d_in, data, n_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_blk, blks.data(), blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice) != hipSuccess
+                || hipMemset(d_err, 0, 32) != hipSuccess || hipMemset(d_crc, 0, blks.size() * 4) != hipSuccess)) rc = fail(h, MLST_E_HIP, "copy to the device failed");
+    if (!rc) {
+        h->crc_hook.d_out = d_crc; h->crc_hook.e0 = ev_get(h); h->crc_hook.e1 = ev_get(h);
+        rc = launch_inflate(h, d_in, (u64)n_bytes + 16, (const BgzfBlk*)d_blk, (u32)blks.size(), d_out, d_err, nullptr);
+        hipError_t se = hipStreamSynchronize(h->stream);
+        float ms = 0; if (!rc && se == hipSuccess) hipEventElapsedTime(&ms, h->crc_hook.e0, h->crc_hook.e1);
+        if (kernel_ms) *kernel_ms = (double)ms;
+        h->ev_pool.push_back(h->crc_hook.e0); h->ev_pool.push_back(h->crc_hook.e1);
+        h->crc_hook.d_out = nullptr; h->crc_hook.e0 = h->crc_hook.e1 = nullptr;
+        if (rc) {}
+        else if (se != hipSuccess || hipMemcpy(err, d_err, 16, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(crc_out, d_crc, blks.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(h, MLST_E_HIP, "k_bgzf_crc failed: %s", hipGetErrorString(hipGetLastError()));
+        else if (err[0]) rc = bz_fail(h, err, err[0] - 1, "");
+    }
+    hipFree(d_in); hipFree(d_out); hipFree(d_blk); hipFree(d_err); hipFree(d_crc);
+    return rc;
+}
+
+// BGZF block CRCs (include/mlst.h): the switch may change only between streams -- a piece in flight was queued with or without the check
+// (any open stream counts, a text stream of mlst_submit_fastq_stream and a paired stream that failed and was not reset included)
+extern "C" int mlst_set_bgzf_verify(mlst_handle* h, int on) {
+    if (!h) return MLST_E_INVALID;
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    h->bgzf_verify = on != 0;
+    return MLST_OK;
+}
+extern "C" int mlst_get_bgzf_verify(mlst_handle* h, int* on) {
+    if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
+    *on = h->bgzf_verify ? 1 : 0;
+    return MLST_OK;
 }
 
 // the decoder of k_inflate_tok2 (csrc/inflate_canon.h) run on the host, its tokens replayed into bytes: a test hook

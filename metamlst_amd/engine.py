@@ -57,6 +57,35 @@ class MlstError(RuntimeError):
     pass
 
 
+class BgzfCrcMismatch(MlstError):
+    """The library's "CRC mismatch in BGZF block <n> ..." (mlst_set_bgzf_verify): file = 1 / 2 on the paired entry, else None.
+    The one place that reads the library's text for it (Engine._check); callers go by the type."""
+
+    def __init__(self, text: str, file: int | None):
+        super().__init__(text)
+        self.file = file
+
+
+class CorruptInput(Exception):
+    """a BGZF block of the file `path` does not have the CRC-32 of its trailer: the device's report or the host's, with the file's name"""
+
+    def __init__(self, path: str, message: str):
+        super().__init__("%s: %s" % (path, message))
+        self.path = path
+
+
+def crc_checked(paths, fn):
+    """fn(), with a CRC mismatch of a BGZF block -- the library's (BgzfCrcMismatch) or the host's for the blocks it inflates itself
+    (fastq.BgzfCrcError) -- turned into CorruptInput naming the file (the paired entry says which of the two)"""
+    from .fastq import BgzfCrcError
+    try:
+        return fn()
+    except BgzfCrcMismatch as e:
+        raise CorruptInput(paths[1] if e.file == 2 else paths[0], str(e)) from e
+    except BgzfCrcError as e:
+        raise CorruptInput(paths[0], str(e)) from e
+
+
 _lib = None
 
 
@@ -95,6 +124,9 @@ def load_library(path: str | None = None):
         "mlst_selftest_inflate_canon": (C.c_int, [u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
         "mlst_debug_bgzf_walk": (C.c_int, [u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
         "mlst_selftest_inflate_device": (C.c_int, [H, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+        "mlst_selftest_bgzf_crc": (C.c_int, [H, u8p, C.c_uint64, u32p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+        "mlst_set_bgzf_verify": (C.c_int, [H, C.c_int]),
+        "mlst_get_bgzf_verify": (C.c_int, [H, C.POINTER(C.c_int)]),
         "mlst_submit_reads_device": (C.c_int, [H, u8p, u8p, u64p, C.c_uint64, C.c_uint32, C.c_int]),
         "mlst_pack_reads_device": (C.c_int, [H, u8p, u8p, u64p, C.c_uint64, u32p, u8p, u16p, C.c_uint32, C.c_uint32]),
         "mlst_submit_packed_device": (C.c_int, [H, u32p, u8p, u16p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int]),
@@ -251,7 +283,10 @@ class Engine:
     def _check(self, rc: int, what: str):
         if rc != 0:
             msg = self.lib.mlst_last_error(self._h)
-            raise MlstError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else "?"))
+            text = msg.decode() if msg else "?"
+            if rc == -1 and text.startswith("CRC mismatch in BGZF block"):      # MLST_E_INVALID with k_bgzf_crc's report (include/mlst.h)
+                raise BgzfCrcMismatch("%s failed (%d): %s" % (what, rc, text), 1 if " of file 1 " in text else 2 if " of file 2 " in text else None)
+            raise MlstError("%s failed (%d): %s" % (what, rc, text))
 
     # ---- reference ----
     def load_reference(self, index: AlleleIndex, cache_path: str | None = None):
@@ -398,6 +433,31 @@ class Engine:
         self.last_inflate_ms = float(ms.value)
         return out[:int(n.value)].tobytes()
 
+    def bgzf_block_crcs(self, data) -> np.ndarray:
+        """Test hook: whole BGZF blocks -> the CRC-32 the device computes of every block with data (uint32, file order), whatever
+        the trailers say.  last_crc_ms: the CRC kernel alone."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+        out = np.zeros(max(1, buf.size // 26 + 1), np.uint32)      # (a block is at least 26 bytes)
+        n, ms = C.c_uint64(), C.c_double()
+        self._check(self.lib.mlst_selftest_bgzf_crc(self._h, _ptr(buf), buf.size, _ptr(out), out.size, C.byref(n), C.byref(ms)), "mlst_selftest_bgzf_crc")
+        self.last_crc_ms = float(ms.value)
+        return out[:int(n.value)].copy()
+
+    def set_bgzf_verify(self, on: bool) -> None:
+        """Check the CRC-32 of every BGZF block on the GPU before its reads are typed (mlst_set_bgzf_verify; off by default,
+        MLST_BGZF_CRC=1 switches it on for new engines).  Only while no stream is open."""
+        self._check(self.lib.mlst_set_bgzf_verify(self._h, int(bool(on))), "mlst_set_bgzf_verify")
+
+    @property
+    def bgzf_verify(self) -> bool:
+        on = C.c_int()
+        self._check(self.lib.mlst_get_bgzf_verify(self._h, C.byref(on)), "mlst_get_bgzf_verify")
+        return bool(on.value)
+
+    @bgzf_verify.setter
+    def bgzf_verify(self, on: bool) -> None:
+        self.set_bgzf_verify(on)
+
     def submit_fastq_stream(self, text, final: bool, paired: bool = False) -> int:
         """One chunk of an open FASTQ stream (cut anywhere; a partial record at its end is completed by the next chunk, text or
         BGZF); final marks the last one.  Returns the number of records completed."""
@@ -417,12 +477,13 @@ class Engine:
                     "mlst_submit_fastq_pair")
         return int(n.value)
 
-    def submit_fastq_bgzf_range(self, path: str, lo: int, hi: int, chunk_bytes: int = 256 << 20) -> int:
+    def submit_fastq_bgzf_range(self, path: str, lo: int, hi: int, chunk_bytes: int = 256 << 20, verify_crc: bool = False) -> int:
         """The records of a bgzip'd FASTQ that start in the BGZF blocks starting in compressed bytes [lo, hi): the boundary
         blocks are inflated on the host to find the record boundaries (fastq.bgzf_range_plan), everything between goes to
-        the GPU compressed.  N ranks given consecutive ranges read every record exactly once."""
+        the GPU compressed.  N ranks given consecutive ranges read every record exactly once.  verify_crc: the host checks the
+        CRC-32 of the blocks it inflates (ValueError); the blocks between are the device's (set_bgzf_verify)."""
         from .fastq import bgzf_range_plan
-        plan = bgzf_range_plan(path, lo, hi)
+        plan = bgzf_range_plan(path, lo, hi, verify_crc)
         total = 0
         first, end = plan["mid"]
         if plan["head"]:

@@ -685,8 +685,17 @@ def bgzf_find_block(f, pos: int, size: int) -> int:
     return size
 
 
-def _bgzf_read_block(f, off: int):
-    """(total compressed size, inflated text) of the block at `off`; (0, b"") at the end of the file."""
+class BgzfCrcError(ValueError):
+    """the text of the BGZF block at file offset `offset` does not have the CRC-32 of the block's trailer (host-inflated blocks)"""
+
+    def __init__(self, offset: int, stored: int, computed: int):
+        super().__init__("CRC mismatch in the BGZF block at byte %d (stored 0x%08x, computed 0x%08x)" % (offset, stored, computed))
+        self.offset, self.stored, self.computed = offset, stored, computed
+
+
+def _bgzf_read_block(f, off: int, verify_crc: bool = False):
+    """(total compressed size, inflated text) of the block at `off`; (0, b"") at the end of the file.  verify_crc: the text
+    must have the CRC-32 of the block's trailer (the raw inflate checks nothing): BgzfCrcError (a ValueError) with the block's offset."""
     import zlib
     f.seek(off)
     head = f.read(18)
@@ -702,18 +711,23 @@ def _bgzf_read_block(f, off: int):
     f.seek(off)
     blk = f.read(n)
     xlen = blk[10] | (blk[11] << 8)
-    return n, zlib.decompress(blk[12 + xlen:n - 8], -15)
+    text = zlib.decompress(blk[12 + xlen:n - 8], -15)
+    if verify_crc:
+        stored, got = int.from_bytes(blk[n - 8:n - 4], "little"), zlib.crc32(text) & 0xFFFFFFFF
+        if stored != got:
+            raise BgzfCrcError(off, stored, got)
+    return n, text
 
 
-def bgzf_split(f, block_off: int, size: int):
+def bgzf_split(f, block_off: int, size: int, verify_crc: bool = False):
     """Where the records of two neighbouring byte ranges part, for the range boundary at the block that starts at
     `block_off`: -> (end, text, p).  `text` is the inflated text of the blocks block_off .. end, `p` the offset in it of
     the first record that starts behind the first line break (record_start(text, 1)): text[:p] completes the last record
     of the range before, text[p:] opens the range behind.  Both ranks evaluate this same function, so they agree.  At
-    the end of the file p = len(text)."""
+    the end of the file p = len(text).  verify_crc: as _bgzf_read_block, for every block inflated here."""
     text, at = b"", block_off
     while at < size:
-        n, t = _bgzf_read_block(f, at)
+        n, t = _bgzf_read_block(f, at, verify_crc)
         if n == 0:
             break
         at += n
@@ -724,10 +738,12 @@ def bgzf_split(f, block_off: int, size: int):
     return at, text, len(text)
 
 
-def bgzf_range_plan(path: str, lo: int, hi: int):
+def bgzf_range_plan(path: str, lo: int, hi: int, verify_crc: bool = False):
     """What the rank owning compressed bytes [lo, hi) of a bgzip'd FASTQ submits: {head: text to submit first (host
     inflated), mid: (first, end) compressed byte range of whole blocks to submit as BGZF, tail: text that completes the
-    last record}.  A range without a block start owns nothing."""
+    last record}.  A range without a block start owns nothing.  verify_crc: every block inflated here (the boundary blocks,
+    which never reach the device's check) must have the CRC-32 of its trailer: ValueError naming the block's file offset.
+    With the device's check on for `mid`, every block of a sharded file is checked by whoever inflates it."""
     size = os.path.getsize(path)
     hi = min(hi, size)
     with open(path, "rb") as f:
@@ -736,11 +752,11 @@ def bgzf_range_plan(path: str, lo: int, hi: int):
         if b_lo >= b_hi:
             return {"head": b"", "mid": (b_lo, b_lo), "tail": b""}
         if lo > 0:
-            e_lo, t_lo, p_lo = bgzf_split(f, b_lo, size)
+            e_lo, t_lo, p_lo = bgzf_split(f, b_lo, size, verify_crc)
         else:
             e_lo, t_lo, p_lo = b_lo, b"", 0
         if b_hi < size:
-            e_hi, t_hi, p_hi = bgzf_split(f, b_hi, size)
+            e_hi, t_hi, p_hi = bgzf_split(f, b_hi, size, verify_crc)
         else:
             e_hi, t_hi, p_hi = size, b"", 0
         if e_lo > b_hi:
@@ -748,14 +764,14 @@ def bgzf_range_plan(path: str, lo: int, hi: int):
             # text position of block b_hi inside t_lo = inflated size of the blocks b_lo .. b_hi
             pos, at = 0, b_lo
             while at < b_hi:
-                n, t = _bgzf_read_block(f, at)
+                n, t = _bgzf_read_block(f, at, verify_crc)
                 at += n
                 pos += len(t)
             cut = pos + p_hi if b_hi < size else len(t_lo)
             if e_hi > e_lo:                       # the next boundary's record start lies beyond what the head inflated
                 f_text, at = t_lo, e_lo
                 while at < e_hi:
-                    n, t = _bgzf_read_block(f, at)
+                    n, t = _bgzf_read_block(f, at, verify_crc)
                     at += n
                     f_text += t
                 t_lo = f_text

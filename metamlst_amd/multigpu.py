@@ -114,7 +114,7 @@ def init_from_env():
 ORDER_SHIFT = 40      # read-index bases of the shards: (file number * ranks + rank) << 40 -- see submit_fastq_shard
 
 
-def submit_fastq_shard(eng, paths: list[str], rank: int, world: int, chunk_bytes: int, paired: bool = False) -> None:
+def submit_fastq_shard(eng, paths: list[str], rank: int, world: int, chunk_bytes: int, paired: bool = False, verify_crc: bool = False) -> None:
     """Submit this rank's share of the sample's FASTQ files.
 
     Plain FASTQ: rank r reads only the byte range [size r / N, size (r + 1) / N) of every file, resynchronised on a
@@ -160,7 +160,9 @@ def submit_fastq_shard(eng, paths: list[str], rank: int, world: int, chunk_bytes
         if is_bgzf(path):
             size = os.path.getsize(path)
             eng.set_read_index_base((f * world + rank) << ORDER_SHIFT)
-            eng.submit_fastq_bgzf_range(path, size * rank // world, size * (rank + 1) // world if rank + 1 < world else size, chunk_bytes)
+            from .engine import crc_checked
+            crc_checked([path], lambda: eng.submit_fastq_bgzf_range(path, size * rank // world, size * (rank + 1) // world if rank + 1 < world else size,
+                                                                    chunk_bytes, verify_crc=verify_crc))
         elif path.endswith(".gz"):
             for chunk in prefetch(text_chunks(path, chunk_bytes)):
                 if k % world == rank:
@@ -243,8 +245,18 @@ def type_many_samples(engines, idx, database, targs, samples: list[list[str]], r
 
     # every engine is fed by a thread of its own (pipeline.feed_threads): the file reads, the copies and -- for bgzip'd files --
     # the inflate the library waits for overlap across the engines instead of holding up the loop one after the other
+    # A sample with a damaged BGZF block (CorruptInput: the engines check the CRCs when the command says so) is reported and left
+    # out -- its engine goes on with an empty sample, which writes nothing -- and the others are typed; the run's status says so.
+    from .engine import CorruptInput
+    corrupt: set = set()
+
     def feed(e, job):
-        submit_sample_files(e, job[1], False, chunk_bytes)
+        try:
+            submit_sample_files(e, job[1], False, chunk_bytes)
+        except CorruptInput as ex:
+            print(ex, file=sys.stderr, flush=True)
+            corrupt.add(job[0])
+            e.reset_sample()
 
     # The per-allele table (metamlst.py:133-151 over every allele with a hit: `cel`) is display -- the closest-allele listing of
     # metamlst.py:213-230 and the --log table; the .nfo line needs the device's choice and consensus only.  A quiet run
@@ -258,7 +270,7 @@ def type_many_samples(engines, idx, database, targs, samples: list[list[str]], r
         i, files = job
         name = sample_name(files[0])
         res = type_sample(idx, st, None, database, name, targs, out_dir=None, fast=not show, cache=cache, typed=(chosen, letters))
-        return {"i": i, "name": name, "nfo": [r.nfo_line for r in res if r.written],
+        return {"i": i, "name": name, "corrupt": i in corrupt, "nfo": [r.nfo_line for r in res if r.written and i not in corrupt],
                 "log": log_table(idx, st, targs, files[0]) if log else None, "results": res if show else None}
 
     t_run = time.perf_counter()
@@ -283,6 +295,8 @@ def type_many_samples(engines, idx, database, targs, samples: list[list[str]], r
     if not os.path.isdir(out_dir):
         os.mkdir(out_dir)
     for x in sorted(mine, key=lambda x: x["i"]):
+        if x["corrupt"]:
+            continue
         if x["log"] is not None:
             with open(out_dir + "/" + x["name"] + "_" + str(int(time.time())) + ".out", "w", newline="") as f:
                 f.write(x["log"])
@@ -296,4 +310,4 @@ def type_many_samples(engines, idx, database, targs, samples: list[list[str]], r
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
-    return 0
+    return 1 if any(x["corrupt"] for x in mine) else 0

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Throughput of the device inflate kernel alone (HIP events around k_inflate): bgzip'd FASTQ of N reads, level 1 and 6.
+"""Throughput of the device inflate kernel alone (HIP events around k_inflate) and of the CRC stage behind it (k_bgzf_crc): bgzip'd
+FASTQ of N reads, level 1 and 6.
     python profiles/inflate_rate.py [reads] [levels, e.g. 6 or 1,6]"""
 import os, struct, sys, time, zlib
 from concurrent.futures import ThreadPoolExecutor
@@ -32,4 +33,9 @@ for level in [int(x) for x in (sys.argv[2] if len(sys.argv) > 2 else "1,6").spli
     ms = []
     for _ in range(3):
         eng.inflate_bgzf(comp); ms.append(eng.last_inflate_ms)
-    print("level %d: %d blocks, %.1f MB -> %.1f MB, k_inflate %.3f ms = %.1f GB/s of text" % (level, len(blocks), len(comp) / 1e6, len(text) / 1e6, min(ms), len(text) / min(ms) / 1e6), flush=True)
+    crc_ms = []
+    for _ in range(4):      # the CRC stage alone (k_bgzf_crc behind the same inflate: mlst_selftest_bgzf_crc), values checked against zlib once
+        crcs = eng.bgzf_block_crcs(comp); crc_ms.append(eng.last_crc_ms)
+    assert crcs.tolist() == [zlib.crc32(text[i:i + 65280]) & 0xFFFFFFFF for i in range(0, len(text), 65280)]
+    print("level %d: %d blocks, %.1f MB -> %.1f MB, k_inflate %.3f ms = %.1f GB/s of text, k_bgzf_crc %.3f ms = %.1f GB/s of text" % (
+        level, len(blocks), len(comp) / 1e6, len(text) / 1e6, min(ms), len(text) / min(ms) / 1e6, min(crc_ms[1:]), len(text) / min(crc_ms[1:]) / 1e6), flush=True)
