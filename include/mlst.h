@@ -281,6 +281,42 @@ int mlst_pileup_alignments(mlst_handle* h, const uint32_t* chosen_allele_idx, ui
                            const uint8_t* seq, const uint8_t* qual, int32_t minscore, int32_t max_xm, int32_t minqual,
                            uint32_t* counts);
 
+/* ---- ready-made alignments straight from a BGZF BAM (the reference's one input, metamlst.py:34) ------------------------------
+ * The file is streamed twice, as the reference reads it twice (samtools view, then pysam): pass 1 is the hit accumulation of
+ * metamlst.py:101-130 (what mlst_submit_* do for reads), pass 2 the pile-up of the chosen contigs (mlst_pileup_alignments).  The
+ * blocks are inflated on the GPU and the records are split, read and counted there, in place: device memory is the text of two
+ * pieces plus the sequenceBank list, whatever the file's size.
+ * mlst_bam_open: the BAM header is the caller's (metamlst_amd/samin.py reads it on the host, and checks the blocks it inflates
+ *   itself -- they never reach mlst_set_bgzf_verify's kernel); it yields, per reference sequence,
+ *   ref_allele (index into the loaded alleles or -1), ref_locus (locus index or -1), ref_flags (bit 0: the species passes
+ *   --filter, bit 1: the name does not split in three at '_'), and skip_bytes: the inflated bytes of the first block submitted
+ *   that still belong to the header.  pass = 1 accumulates into the sample's statistics (mlst_get_allele_stats, mlst_typing_*
+ *   and mlst_reset_sample work as after reads); pass = 2 piles the records of the chosen alleles up (chosen_allele_idx,
+ *   n_chosen; pass 1 ignores them).
+ * mlst_submit_bam_bgzf: compressed bytes as for mlst_submit_fastq_bgzf (whole blocks, cut anywhere between them; with
+ *   n_consumed_out a non-final buffer may end inside a block); records may straddle blocks and calls.  The 12th and the 15th
+ *   column are the 1st and the 4th optional field BY POSITION (Q1); len(SEQ) of a record without SEQ is 1; sequenceBank holds one
+ *   length per (locus, QNAME), the last record's -- a QNAME is identified by a 128-bit hash of its bytes (MLST_BAM_QNAME_KEY,
+ *   mlst_policy.h).  The order of the records does not matter.  A call's piece is finished by the next call on the handle (as
+ *   for mlst_submit_fastq_bgzf; MLST_BGZF_PIPE=0: by the call itself): n_records_out counts the records completed by the call, a
+ *   corrupt block (or, with mlst_set_bgzf_verify, a CRC mismatch: same message, nothing of the piece is counted) is reported
+ *   by the call that finishes its piece.  The last call passes final_chunk != 0; the file must end with a whole record.
+ *   A record larger than the 1 MiB head room of a piece: MLST_E_LIMIT.  A record the device cannot treat the way the reference
+ *   would -- no reference sequence, a contig name that does not split in three, fewer than four optional fields, a non-integer
+ *   1st / 4th field (integer types c C s S i I), an unknown field type, a non-integer AS / XM (pass 2) -- ends the stream with
+ *   MLST_E_INVALID "host path needed: <reason> at record <n>": the caller runs the host reader, which raises or answers as the
+ *   reference would.  After any error the stream is closed and the sample's state is undefined (mlst_reset_sample).
+ *   While a BAM stream is open the mlst_submit_* entries for reads refuse to start, and mlst_bam_open refuses while a FASTQ
+ *   stream is open.
+ * mlst_bam_set_capacity: most accepted records on known loci a pass-1 stream may list for sequenceBank (32 bytes each, allocated
+ *   as the file needs them; 0 = default 2^26); MLST_E_CAPACITY beyond it.
+ * mlst_bam_pileup_fetch: the counts of a finished pass-2 stream, layout of mlst_pileup (alleles in the order given). */
+int mlst_bam_open(mlst_handle* h, int pass, const int32_t* ref_allele, const int32_t* ref_locus, const uint8_t* ref_flags, uint32_t n_ref,
+                  uint32_t skip_bytes, const uint32_t* chosen_allele_idx, uint32_t n_chosen);
+int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, int final_chunk, uint64_t* n_records_out, uint64_t* n_consumed_out);
+int mlst_bam_set_capacity(mlst_handle* h, uint64_t max_entries);
+int mlst_bam_pileup_fetch(mlst_handle* h, uint32_t* counts);
+
 /* ---- whole typing tail on the device, without a host round trip between the passes ----------------------
  * mlst_typing_enqueue queues, behind the pass-1 work already submitted on the engine's stream:
  *   the allele choice of metamlst.py:133-151 + :244 (per locus the allele with the highest

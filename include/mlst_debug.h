@@ -52,6 +52,11 @@ int mlst_debug_bgzf_walk(const uint8_t* data, uint64_t n_bytes, uint64_t* n_bloc
 int mlst_get_route_trace(mlst_handle* h, uint64_t* out, uint64_t cap_words, uint64_t* n_words);
 int mlst_debug_route_realloc(mlst_handle* h, uint64_t pad_bytes);
 
+/* The record split of BAM input (csrc/bam_dev.h): force_miss_every = n > 0 throws the guessed record start of every n-th cell
+ * of the streams that follow away, so that the chain walk has to enter those cells from their true entry (the path a wrong guess
+ * takes); 0 = off.  *cells_rewalked_out: cells walked again during the last stream.  Only while no BAM stream is open. */
+int mlst_debug_bam_split(mlst_handle* h, uint32_t force_miss_every, uint64_t* cells_rewalked_out);
+
 #ifdef __cplusplus
 }
 #endif

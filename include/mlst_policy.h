@@ -53,6 +53,13 @@
                                        file; 0 = not applied.  As a switch it is "the first n records that span a column,
                                        in (read index, strand) order" -- oracle: orc_pileup_capped */
 
+/* ---- BAM input (mlst_submit_bam_bgzf) ---- */
+#define MLST_BAM_QNAME_KEY    128   /* sequenceBank[locus][QNAME] (metamlst.py:127) on the device: a read name IS its 128-bit key (two
+                                       independent 64-bit hashes of its bytes, and its length).  Two different names of one
+                                       sample with the same key would count as one read for the locus' average length; at 10^9
+                                       names the chance is ~10^-21.  The host path (samin.AlignmentSample) keeps the names. */
+#define MLST_BAM_MAX_RECORD (1048576 - 64)   /* largest BAM record (block_size): the head room of a piece, MLST_E_LIMIT beyond */
+
 /* ---- hard limits of the packed formats ---- */
 #define MLST_MAX_READ_LEN     320   /* 20 packed words; xm field of the packed score is 8 bits */
 #define MLST_MAX_ALLELE_LEN  4095   /* 12-bit position in a seed posting */

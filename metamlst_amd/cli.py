@@ -203,7 +203,28 @@ def run_type(a, argv=None) -> int:
         database.closeConnection()
         return rc
     if a.alignments:
-        from .samin import AlignmentSample
+        from .engine import HostPathNeeded
+        from .samin import AlignmentSample, BamSample, is_bgzf_bam
+        if is_bgzf_bam(a.READS):      # inflate, record split, accumulation and pile-up on the device (two passes over the file)
+            def said(e):      # which path typed the sample is the user's to know: the host reader is ~10^3 times slower
+                print("%s: %s -- reading the file on the host instead" % (a.READS, str(e).split(": ", 1)[-1]), file=sys.stderr)
+
+            def device_pileup(chosen):
+                try:
+                    return crc_checked([a.READS], lambda: bam.pileup(eng, chosen))
+                except HostPathNeeded as e:      # (pass 2 only: an AS / XM tag by name that is no integer.  The statistics stay the
+                    said(e)                      # device's -- pass 1 treated every record; the host reader is built for the pile-up alone)
+                    return AlignmentSample(idx, targs).add_file(a.READS).pileup(eng, chosen)
+            try:
+                bam = crc_checked([a.READS], lambda: BamSample(idx, targs, eng).add_file(a.READS))
+                return _finish_type(a, idx, database, targs, bam.stats(), device_pileup)
+            except HostPathNeeded as e:      # a record only the host reader treats: today's path, which raises or answers as the reference
+                said(e)
+                eng.reset_sample()
+            except CorruptInput as e:   # nothing of the sample is typed: no .nfo
+                print(e, file=sys.stderr)
+                database.closeConnection()
+                return 1
         smp = AlignmentSample(idx, targs).add_file(a.READS)
         return _finish_type(a, idx, database, targs, smp.stats(), lambda chosen: smp.pileup(eng, chosen))
     if a.contigs:

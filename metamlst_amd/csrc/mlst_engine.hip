@@ -36,6 +36,7 @@
 #include "inflate_canon.h"
 #include "bgzf_crc.h"
 #include "mlst_policy.h"
+#include <rocprim/device/device_radix_sort.hpp>      // the sequenceBank list of BAM input (bam_dev.h) is sorted with it
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -3484,6 +3485,8 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) p[i] = v;
 }
 
+#include "bam_dev.h"
+
 // ================================================================== host side
 struct EvPair { hipEvent_t a, b; int which; };
 
@@ -3588,6 +3591,8 @@ struct mlst_handle {
     std::vector<hipEvent_t> ev_pool;
     double k_ms[16] = {0}; u64 k_n[16] = {0};      // see mlst_get_kernel_time
     double wall_khz = 100000.0;                  // wall_clock64 rate (hipDeviceAttributeWallClockRate)
+    struct BamStream* bam = nullptr;             // BAM input (mlst_bam_open / mlst_submit_bam_bgzf), allocated by the first stream
+    u32 bam_force_miss = 0; u64 bam_max_entries = 0;      // mlst_debug_bam_split, mlst_bam_set_capacity
 };
 
 static std::string g_create_err;
@@ -3602,6 +3607,9 @@ static int fail(mlst_handle* h, int code, const char* fmt, ...) {
 static int bz_flush(mlst_handle* h);      // BGZF input: the piece still being inflated is parsed and submitted (defined with mlst_submit_fastq_bgzf)
 static int bzp_finish(mlst_handle* h, bool whole, uint64_t* n_reads_out);      // the same for a piece of two mate files (mlst_submit_fastq_bgzf_pair)
 static void bz_free(mlst_handle* h);
+static int bam_flush(mlst_handle* h);     // BAM input: the piece in flight is finished (its errors are this call's)
+static void bam_drop(mlst_handle* h, bool release);      // the BAM stream is closed and forgotten (release: its buffers too)
+static bool bam_is_open(const mlst_handle* h);
 template <typename T> static hipError_t dmalloc(T** p, u64 n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
 template <typename T> static hipError_t dmalloc(GP<T>* p, u64 n) { return hipMalloc((void**)&p->p, (n ? n : 1) * sizeof(T)); }
 
@@ -3744,6 +3752,7 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
     bz_free(h);
+    bam_drop(h, true);
     for (auto& e : h->events) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
     for (auto& e : h->ev_pool) hipEventDestroy(e);
     free_ref(h); free_state(h);
@@ -3771,6 +3780,7 @@ static int reset_sample_state(mlst_handle* h) {
     if (h->d_acc64 && h->n_alleles) HIPCHK(h, hipMemsetAsync(h->d_acc64, 0, (u64)h->n_alleles * 8, h->stream));      // (zero after every complete submission already: k_accumulate; this is for one that was cut short)
     h->reads_seen = 0; h->fq_carry_len = 0; h->max_wpr = 0;
     h->pc_len[0] = h->pc_len[1] = 0; h->pair_open = false;      // (mlst_submit_fastq_bgzf_pair: both files' carries)
+    bam_drop(h, false);
     return MLST_OK;
 }
 
@@ -4514,6 +4524,7 @@ static int h2d_overlapped(mlst_handle* h, void* d_dst, const void* src, u64 n, h
 extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, const uint8_t* d_quals, const uint64_t* d_off,
                                         uint64_t n_reads, uint32_t max_len, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     hipSetDevice(h->device);
     if (n_reads == 0) return MLST_OK;
@@ -4528,6 +4539,7 @@ extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, 
 extern "C" int mlst_submit_reads(mlst_handle* h, const uint8_t* bases, const uint8_t* quals, const uint64_t* off,
                                  uint64_t n_reads, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (n_reads == 0) return MLST_OK;
     if (!bases || !quals || !off) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -4728,6 +4740,7 @@ extern "C" int mlst_pack_fastq_host(const uint8_t* text, uint64_t n_bytes, uint3
 extern "C" int mlst_submit_packed_host(mlst_handle* h, const uint32_t* packed, const uint8_t* qrows, const uint16_t* lens, uint64_t n_reads,
                                        uint32_t wpr, uint32_t qstride, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (!packed || !qrows || !lens) return fail(h, MLST_E_INVALID, "NULL argument");
     hipSetDevice(h->device);
@@ -4835,6 +4848,7 @@ extern "C" int mlst_submit_fastq(mlst_handle* h, const uint8_t* text, uint64_t n
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
     if (n_reads_out) *n_reads_out = 0;
     if (n_bytes == 0) return MLST_OK;
     if (!text) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -4852,6 +4866,7 @@ extern "C" int mlst_submit_fastq_stream(mlst_handle* h, const uint8_t* text, uin
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
     if (n_reads_out) *n_reads_out = 0;
     if (n_bytes && !text) return fail(h, MLST_E_INVALID, "NULL argument");
     const u64 total = h->fq_carry_len + n_bytes;
@@ -4870,6 +4885,7 @@ extern "C" int mlst_submit_fastq_pair(mlst_handle* h, const uint8_t* text1, uint
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
     if (n_reads_out) *n_reads_out = 0;
     if (n1 == 0 && n2 == 0) return MLST_OK;
     if (!text1 || !text2 || n1 == 0 || n2 == 0) return fail(h, MLST_E_INVALID, "mate files hold different numbers of records (one chunk is empty)");
@@ -5018,6 +5034,7 @@ static int bz_finish(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
 }
 // a piece that is still open is finished (its trailing partial record stays in the carry, as after any non-final chunk)
 static int bz_flush(mlst_handle* h) {
+    { int rc = bam_flush(h); if (rc) return rc; }
     if (h->bzp.on) { int rc = bzp_finish(h, false, nullptr); if (rc) return rc; }      // (a piece of mate files: its unpaired records stay in the carries)
     return h->bz_pend.on ? bz_finish(h, false, nullptr) : MLST_OK;
 }
@@ -5100,6 +5117,7 @@ extern "C" int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint6
                                       uint64_t* n_consumed_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
     if (n_reads_out) *n_reads_out = 0;
     if (n_consumed_out) *n_consumed_out = 0;
     if (n_bytes && !data) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -5437,6 +5455,7 @@ static int bzp_submit(mlst_handle* h, const u8* data1, u64 n1, const u8* data2, 
 extern "C" int mlst_submit_fastq_bgzf_pair(mlst_handle* h, const uint8_t* data1, uint64_t n1, const uint8_t* data2, uint64_t n2, int final_chunk,
                                            uint64_t* n_reads_out, uint64_t* n_consumed1_out, uint64_t* n_consumed2_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
     if (n_reads_out) *n_reads_out = 0;
     if (n_consumed1_out) *n_consumed1_out = 0;
     if (n_consumed2_out) *n_consumed2_out = 0;
@@ -5550,11 +5569,301 @@ extern "C" int mlst_selftest_bgzf_crc(mlst_handle* h, const uint8_t* data, uint6
     return rc;
 }
 
+// ================================================================== BAM input (mlst_bam_open / mlst_submit_bam_bgzf; kernels: csrc/bam_dev.h)
+// A call's whole blocks are one piece: its compressed bytes are copied on the copy stream into one of two slots, inflated into
+// the slot's text (launch_inflate, with k_bgzf_crc behind it when verification is on) and split, accumulated / piled up on the
+// engine's stream.  Everything a piece hands to the next one (the partial record at its end, the record count, the list fill)
+// stays on the device, so nothing waits for the host: the call returns once its bytes have left the caller's buffer, and the
+// piece's errors are looked at by the next call on the handle (bam_flush) -- MLST_BGZF_PIPE=0: by the call itself.
+struct BamSlot {
+    u8* d_comp = nullptr; u64 cap_comp = 0; BgzfBlk* d_blk = nullptr; BgzfBlk* h_blk = nullptr; u64 cap_blk = 0;
+    u8* d_text = nullptr; u64 cap_text = 0; u32* d_cells = nullptr; u32* d_list = nullptr; u64 cap_cells = 0;
+    u32* d_err = nullptr; u8* h_res = nullptr;      // h_res (pinned): 4 error words of the inflate, then the BamMeta after the piece
+    hipEvent_t ev_copied = nullptr, ev_done = nullptr;
+    u64 bound = 0;      // pass 1: most list entries the piece in this slot can add (a record per 37 bytes), counted in BamStream::bound_pend while it is in flight
+};
+struct BamStream {
+    bool open = false, pend = false, first = true; int pass = 0, cur = 0; u32 n_ref = 0, skip = 0;
+    int* d_ref_allele = nullptr; int* d_ref_locus = nullptr; u8* d_ref_flags = nullptr; u64 cap_ref = 0;
+    BamSlot s[2]; u8* d_carry = nullptr; BamMeta* d_meta = nullptr;
+    BamEntry* d_entries = nullptr; u64 cap_entries = 0, entries_done = 0, bound_pend = 0; u32 last_carry = 0;
+    int* d_allele_slot = nullptr; u64 cap_slot = 0; u32* d_counts = nullptr; u64 cap_counts = 0, n_cols = 0; bool counts_ready = false;
+    u64 rewalked = 0;
+    u64* d_sort_k[2] = {nullptr, nullptr}; u32* d_sort_v[2] = {nullptr, nullptr}; void* d_sort_tmp = nullptr; u64 cap_sort = 0, cap_sort_tmp = 0;      // bam_bank's buffers, kept between streams
+};
+static_assert(MLST_BAM_MAX_RECORD == BAM_REC_MAX, "mlst_policy.h and csrc/bam_dev.h state the largest BAM record differently");
+#define BAM_DEFAULT_ENTRIES (1ull << 26)      /* sequenceBank list: 32 bytes an entry, allocated as the file needs it */
+static bool bam_is_open(const mlst_handle* h) { return h->bam && h->bam->open; }
+static void bam_drop(mlst_handle* h, bool release) {
+    BamStream* B = h->bam;
+    if (!B) return;
+    if (B->pend || B->open) { if (h->copy_stream) hipStreamSynchronize(h->copy_stream); if (h->stream) hipStreamSynchronize(h->stream); }
+    B->open = false; B->pend = false; B->counts_ready = false;
+    if (!release) return;
+    for (auto& S : B->s) {
+        hipFree(S.d_comp); hipFree(S.d_blk); if (S.h_blk) hipHostFree(S.h_blk); hipFree(S.d_text); hipFree(S.d_cells); hipFree(S.d_list); hipFree(S.d_err);
+        if (S.h_res) hipHostFree(S.h_res); if (S.ev_copied) hipEventDestroy(S.ev_copied); if (S.ev_done) hipEventDestroy(S.ev_done);
+    }
+    hipFree(B->d_ref_allele); hipFree(B->d_ref_locus); hipFree(B->d_ref_flags); hipFree(B->d_carry); hipFree(B->d_meta); hipFree(B->d_entries);
+    hipFree(B->d_allele_slot); hipFree(B->d_counts);
+    for (int k = 0; k < 2; k++) { hipFree(B->d_sort_k[k]); hipFree(B->d_sort_v[k]); } hipFree(B->d_sort_tmp);
+    delete B; h->bam = nullptr;
+}
+static const char* bam_reason(u32 r) {
+    switch (r) {
+        case BAM_FLAG_UNMAPPED: return "a record without a reference (RNAME *)";
+        case BAM_FLAG_NAME: return "a contig name that does not split in three at '_'";
+        case BAM_FLAG_FEWTAGS: return "fewer than four optional fields";
+        case BAM_FLAG_NONINT: return "a non-integer 1st / 4th optional field";
+        case BAM_FLAG_AUX: return "an optional field the reader does not know";
+        case BAM_FLAG_TAGTYPE: return "an AS / XM tag that is not an integer";
+        default: return "?";
+    }
+}
+// the piece in flight: wait for it, report what it met.  whole: the file ends with it.
+static int bam_finish(mlst_handle* h, uint64_t* n_records_out) {
+    BamStream* B = h->bam;
+    if (!B || !B->pend) return MLST_OK;
+    B->pend = false;
+    BamSlot& S = B->s[B->cur];
+    HIPCHK(h, hipEventSynchronize(S.ev_done));
+    const u32* e = (const u32*)S.h_res; BamMeta m; memcpy(&m, S.h_res + 16, sizeof m);
+    B->bound_pend -= std::min(B->bound_pend, S.bound); S.bound = 0;      // (the piece queued behind this one keeps its share)
+    if (e[0]) { bam_drop(h, false); return bz_fail(h, e, e[0] - 1, " of the chunk"); }
+    if (m.err) {
+        bam_drop(h, false);
+        switch (m.err) {
+            case BAM_ERR_LIMIT: return fail(h, MLST_E_LIMIT, "a BAM record of more than %u bytes", (unsigned)BAM_REC_MAX);
+            case BAM_ERR_LIST: return fail(h, MLST_E_CAPACITY, "more than %llu accepted records on known loci (mlst_bam_set_capacity)", (unsigned long long)B->cap_entries);
+            case BAM_ERR_TRUNC: return fail(h, MLST_E_INVALID, "truncated BAM: the file ends inside a record (after record %llu)", (unsigned long long)(m.rec_total));
+            default: return fail(h, MLST_E_INVALID, "malformed BAM record behind record %llu", (unsigned long long)m.rec_total);
+        }
+    }
+    if (m.flag_key != ~0ull) { bam_drop(h, false); return fail(h, MLST_E_INVALID, "host path needed: %s at record %llu", bam_reason((u32)(m.flag_key & 15u)), (unsigned long long)(m.flag_key >> 4)); }
+    B->entries_done = m.n_entries; B->last_carry = m.carry_len; B->rewalked = m.rewalked;
+    if (n_records_out) *n_records_out += m.n_rec;
+    return MLST_OK;
+}
+static int bam_flush(mlst_handle* h) { return (h->bam && h->bam->pend) ? bam_finish(h, nullptr) : MLST_OK; }
+
+extern "C" int mlst_bam_set_capacity(mlst_handle* h, uint64_t max_entries) {
+    if (!h) return MLST_E_INVALID;
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    h->bam_max_entries = max_entries;
+    return MLST_OK;
+}
+
+extern "C" int mlst_bam_open(mlst_handle* h, int pass, const int32_t* ref_allele, const int32_t* ref_locus, const uint8_t* ref_flags, uint32_t n_ref,
+                             uint32_t skip_bytes, const uint32_t* chosen_allele_idx, uint32_t n_chosen) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if ((pass != 1 && pass != 2) || (n_ref && (!ref_allele || !ref_locus || !ref_flags)) || (n_chosen && !chosen_allele_idx)) return fail(h, MLST_E_INVALID, "bad argument");
+    if (n_ref >= 0x7FFFFFFFu || skip_bytes >= 65536u) return fail(h, MLST_E_INVALID, "bad argument");
+    hipSetDevice(h->device);
+    if (!h->bam) h->bam = new BamStream();
+    BamStream* B = h->bam;
+    for (u32 i = 0; i < n_ref; i++) if (ref_allele[i] >= (int)h->n_alleles || ref_locus[i] >= (int)h->n_loci) return fail(h, MLST_E_INVALID, "reference table entry %u out of range", i);
+    if (B->cap_ref < n_ref || !B->d_ref_allele) {
+        hipFree(B->d_ref_allele); hipFree(B->d_ref_locus); hipFree(B->d_ref_flags); B->d_ref_allele = B->d_ref_locus = nullptr; B->d_ref_flags = nullptr; B->cap_ref = 0;
+        HIPCHK(h, dmalloc(&B->d_ref_allele, (u64)n_ref)); HIPCHK(h, dmalloc(&B->d_ref_locus, (u64)n_ref)); HIPCHK(h, dmalloc(&B->d_ref_flags, (u64)n_ref)); B->cap_ref = n_ref;
+    }
+    if (n_ref) {
+        HIPCHK(h, hipMemcpyAsync(B->d_ref_allele, ref_allele, (u64)n_ref * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(B->d_ref_locus, ref_locus, (u64)n_ref * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(B->d_ref_flags, ref_flags, (u64)n_ref, hipMemcpyHostToDevice, h->stream));
+    }
+    if (!B->d_carry) HIPCHK(h, dmalloc(&B->d_carry, (u64)BAM_HEAD));
+    if (!B->d_meta) HIPCHK(h, dmalloc(&B->d_meta, (u64)1));
+    BamMeta m; memset(&m, 0, sizeof m); m.flag_key = ~0ull;
+    HIPCHK(h, hipMemcpyAsync(B->d_meta, &m, sizeof m, hipMemcpyHostToDevice, h->stream));
+    B->counts_ready = false;
+    if (pass == 2) {
+        std::vector<int> slot(h->n_alleles, -1); u64 cols = 0;
+        for (u32 i = 0; i < n_chosen; i++) {
+            const u32 a = chosen_allele_idx[i];
+            if (a >= h->n_alleles) return fail(h, MLST_E_INVALID, "chosen allele out of range");
+            if (slot[a] >= 0) return fail(h, MLST_E_INVALID, "an allele chosen twice");
+            slot[a] = (int)cols; cols += h->aoff[a + 1] - h->aoff[a];
+        }
+        if (cols >= (1ull << 29)) return fail(h, MLST_E_LIMIT, "too many pile-up columns");
+        if (B->cap_slot < h->n_alleles) { hipFree(B->d_allele_slot); B->d_allele_slot = nullptr; HIPCHK(h, dmalloc(&B->d_allele_slot, (u64)h->n_alleles)); B->cap_slot = h->n_alleles; }
+        if (B->cap_counts < cols * 4) { hipFree(B->d_counts); B->d_counts = nullptr; HIPCHK(h, dmalloc(&B->d_counts, cols * 4)); B->cap_counts = cols * 4; }
+        if (h->n_alleles) HIPCHK(h, hipMemcpyAsync(B->d_allele_slot, slot.data(), (u64)h->n_alleles * 4, hipMemcpyHostToDevice, h->stream));
+        if (cols) HIPCHK(h, hipMemsetAsync(B->d_counts, 0, cols * 16, h->stream));
+        B->n_cols = cols;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (the tables came from the caller's pageable memory)
+    B->open = true; B->pend = false; B->first = true; B->pass = pass; B->n_ref = n_ref; B->skip = skip_bytes;
+    B->entries_done = B->bound_pend = 0; B->s[0].bound = B->s[1].bound = 0; B->last_carry = 0;
+    return MLST_OK;
+}
+
+// sequenceBank from the list of pass 1 (see k_bam_bank_*), at the end of the stream
+static int bam_bank(mlst_handle* h) {
+    BamStream* B = h->bam; const u64 n = B->entries_done;
+    if (!n) return MLST_OK;
+    if (n >= (1ull << 32)) return fail(h, MLST_E_CAPACITY, "sequenceBank list too long");
+    size_t tmp = 0;
+    if (rocprim::radix_sort_pairs(nullptr, tmp, (u64*)nullptr, (u64*)nullptr, (u32*)nullptr, (u32*)nullptr, (size_t)n, 0, 64, h->stream) != hipSuccess) return fail(h, MLST_E_HIP, "radix sort (size query) failed");
+    if (B->cap_sort < n) {
+        for (int k = 0; k < 2; k++) { hipFree(B->d_sort_k[k]); hipFree(B->d_sort_v[k]); B->d_sort_k[k] = nullptr; B->d_sort_v[k] = nullptr; }
+        B->cap_sort = 0; const u64 cap = n + n / 4;
+        for (int k = 0; k < 2; k++) if (dmalloc(&B->d_sort_k[k], cap) != hipSuccess || dmalloc(&B->d_sort_v[k], cap) != hipSuccess) return fail(h, MLST_E_HIP, "out of device memory for the sequenceBank sort");
+        B->cap_sort = cap;
+    }
+    if (B->cap_sort_tmp < tmp || !B->d_sort_tmp) {
+        hipFree(B->d_sort_tmp); B->d_sort_tmp = nullptr; B->cap_sort_tmp = 0;
+        if (hipMalloc(&B->d_sort_tmp, tmp + tmp / 4 + 256) != hipSuccess) return fail(h, MLST_E_HIP, "out of device memory for the sequenceBank sort");
+        B->cap_sort_tmp = tmp + tmp / 4 + 256;
+    }
+    u64** d_k = B->d_sort_k; u32** d_v = B->d_sort_v; void* d_tmp = B->d_sort_tmp;
+    int rc = MLST_OK;
+    auto done = [&](int r) { return r; };
+    const int g = grid_for(n, 256, 4096);
+    hipLaunchKernelGGL(k_bam_bank_keys, dim3(g), dim3(256), 0, h->stream, (const BamEntry*)B->d_entries, n, d_k[0], d_v[0]);
+    if (rocprim::radix_sort_pairs(d_tmp, tmp, d_k[0], d_k[1], d_v[0], d_v[1], (size_t)n, 0, 64, h->stream) != hipSuccess) return done(fail(h, MLST_E_HIP, "radix sort failed"));
+    hipLaunchKernelGGL(k_bam_bank_mix, dim3(g), dim3(256), 0, h->stream, (const BamEntry*)B->d_entries, n, (const u32*)d_v[1], d_k[0]);
+    if (rocprim::radix_sort_pairs(d_tmp, tmp, d_k[0], d_k[1], d_v[1], d_v[0], (size_t)n, 0, 64, h->stream) != hipSuccess) return done(fail(h, MLST_E_HIP, "radix sort failed"));
+    hipLaunchKernelGGL(k_bam_bank_sum, dim3(g), dim3(256), 0, h->stream, (const EngineDev*)h->d_E, (const BamEntry*)B->d_entries, n, (const u32*)d_v[0], (const u64*)d_k[1]);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, MLST_E_HIP, "the sequenceBank kernels failed: %s", hipGetErrorString(hipGetLastError()));
+    return done(rc);
+}
+
+extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, int final_chunk, uint64_t* n_records_out, uint64_t* n_consumed_out) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    if (n_records_out) *n_records_out = 0;
+    if (n_consumed_out) *n_consumed_out = 0;
+    if (!bam_is_open(h)) return fail(h, MLST_E_INVALID, "no BAM stream is open (mlst_bam_open)");
+    if (n_bytes && !data) return fail(h, MLST_E_INVALID, "NULL argument");
+    if (n_bytes >= (1ull << 30)) return fail(h, MLST_E_LIMIT, "BGZF chunk too large");
+    hipSetDevice(h->device);
+    BamStream* B = h->bam;
+    const bool piped = bz_mode(h) != 0;
+    std::vector<BgzfBlk> blks; u64 text_bytes = BAM_HEAD;
+    for (u64 off = 0; off < n_bytes; ) {
+        u64 total, coff, clen; u32 isize;
+        if (!bgzf_block(data + off, n_bytes - off, total, coff, clen, isize)) {
+            const bool cut = n_bytes - off < 18 || (data[off] == 0x1f && data[off + 1] == 0x8b && data[off + 2] == 8 && (data[off + 3] & 4));
+            if (n_consumed_out && !final_chunk && cut) { n_bytes = off; break; }
+            bam_drop(h, false);
+            return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu of the chunk", (unsigned long long)off);
+        }
+        if (isize > 65536) { bam_drop(h, false); return fail(h, MLST_E_INVALID, "BGZF block at byte %llu claims %u bytes of data", (unsigned long long)off, isize); }
+        if (isize) { BgzfBlk b; b.in_off = off + coff; b.in_len = (u32)clen; b.out_off = text_bytes; b.out_len = isize; blks.push_back(b); text_bytes += isize; }
+        off += total;
+    }
+    if (text_bytes >= (1ull << 31) - (1ull << 21)) { bam_drop(h, false); return fail(h, MLST_E_LIMIT, "BGZF chunk inflates to more than 2 GiB"); }
+    if (n_consumed_out) *n_consumed_out = n_bytes;
+    uint64_t done = 0;
+    if (blks.empty()) {
+        { int rc = bam_finish(h, &done); if (rc) return rc; }
+        if (n_records_out) *n_records_out = done;
+        if (!final_chunk) return MLST_OK;
+        if (B->last_carry || B->first) { const bool never = B->first; bam_drop(h, false); return fail(h, MLST_E_INVALID, never ? "truncated BAM: no records block" : "truncated BAM: the file ends inside a record"); }
+    } else {
+        // (slot `cur` holds the piece in flight; this piece takes the other one, whose last user was finished by the call before)
+        const int sl = B->pend ? (B->cur ^ 1) : B->cur;
+        BamSlot& S = B->s[sl];
+        if (!S.ev_done) {
+            HIPCHK(h, hipEventCreateWithFlags(&S.ev_copied, hipEventDisableTiming)); HIPCHK(h, hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming));
+            HIPCHK(h, dmalloc(&S.d_err, (u64)16)); HIPCHK(h, hipHostMalloc((void**)&S.h_res, 16 + sizeof(BamMeta), hipHostMallocDefault));
+        }
+        if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+        const u32 n_cells = (u32)((text_bytes + BAM_CELL - 1) / BAM_CELL);
+        if (S.cap_comp < n_bytes) { hipFree(S.d_comp); S.d_comp = nullptr; S.cap_comp = 0; HIPCHK(h, dmalloc(&S.d_comp, n_bytes + n_bytes / 8 + 32)); S.cap_comp = n_bytes + n_bytes / 8; }
+        if (S.cap_blk < blks.size()) {
+            hipFree(S.d_blk); S.d_blk = nullptr; if (S.h_blk) { hipHostFree(S.h_blk); S.h_blk = nullptr; } S.cap_blk = 0;
+            const u64 cap = blks.size() + blks.size() / 8 + 16;
+            HIPCHK(h, dmalloc(&S.d_blk, cap)); HIPCHK(h, hipHostMalloc((void**)&S.h_blk, cap * sizeof(BgzfBlk), hipHostMallocDefault)); S.cap_blk = cap;
+        }
+        if (S.cap_text < text_bytes) { hipFree(S.d_text); S.d_text = nullptr; S.cap_text = 0; const u64 cap = text_bytes + text_bytes / 8; HIPCHK(h, dmalloc(&S.d_text, cap + 2 * BAM_CELL + 65536)); S.cap_text = cap; }
+        if (S.cap_cells < n_cells) {
+            hipFree(S.d_cells); hipFree(S.d_list); S.d_cells = S.d_list = nullptr; S.cap_cells = 0;
+            const u64 cap = (u64)n_cells + n_cells / 8 + 8;
+            HIPCHK(h, dmalloc(&S.d_cells, cap * 4)); HIPCHK(h, dmalloc(&S.d_list, cap * BAM_CELL_CAP)); S.cap_cells = cap;
+        }
+        if (B->pass == 1) {      // the list grows with the file: what the finished pieces filled, plus at most a record per 37 bytes of the pieces in flight
+            const u64 bound = (text_bytes - BAM_HEAD + B->last_carry + BAM_HEAD) / 37 + 1, cap_max = h->bam_max_entries ? h->bam_max_entries : BAM_DEFAULT_ENTRIES;
+            const u64 need = std::min(cap_max, B->entries_done + B->bound_pend + bound);
+            if (B->cap_entries < need) {
+                const u64 cap = std::min(cap_max, std::max(need, B->cap_entries * 2));
+                BamEntry* d_new = nullptr; HIPCHK(h, dmalloc(&d_new, cap));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                if (B->d_entries && B->cap_entries) HIPCHK(h, hipMemcpy(d_new, B->d_entries, B->cap_entries * sizeof(BamEntry), hipMemcpyDeviceToDevice));
+                hipFree(B->d_entries); B->d_entries = d_new; B->cap_entries = cap;
+            }
+            B->bound_pend += bound; S.bound = bound;
+        }
+        memcpy(S.h_blk, blks.data(), blks.size() * sizeof(BgzfBlk));
+        HIPCHK(h, hipMemcpyAsync(S.d_comp, data, n_bytes, hipMemcpyHostToDevice, h->copy_stream));
+        HIPCHK(h, hipEventRecord(S.ev_copied, h->copy_stream));
+        struct CopyGuard { mlst_handle* h; ~CopyGuard() { hipStreamSynchronize(h->copy_stream); } } copy_guard{h};      // `data` is the caller's again on return
+        hipStream_t st = h->stream;
+        HIPCHK(h, hipMemcpyAsync(S.d_blk, S.h_blk, blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemsetAsync(S.d_err, 0, 64, st));
+        HIPCHK(h, hipStreamWaitEvent(st, S.ev_copied, 0));
+        { int rc = launch_inflate(h, S.d_comp, S.cap_comp + 16, S.d_blk, (u32)blks.size(), S.d_text, S.d_err, nullptr, st); if (rc) { bam_drop(h, false); return rc; } }
+        const u32 text_end = (u32)text_bytes; const bool last = final_chunk != 0;
+        u32* d_first = S.d_cells; u32* d_exit = d_first + S.cap_cells; u32* d_count = d_exit + S.cap_cells; u32* d_base = d_count + S.cap_cells;
+        hipLaunchKernelGGL(k_bam_carry_in, dim3(64), dim3(256), 0, st, S.d_text, (const u8*)B->d_carry, B->d_meta, B->first ? B->skip : 0u);
+        hipLaunchKernelGGL(k_bam_cells, dim3(std::min(n_cells, 16384u)), dim3(256), 0, st, (const u8*)S.d_text, text_end, n_cells, (int)B->n_ref, (const BamMeta*)B->d_meta,
+                           d_first, d_exit, d_count, S.d_list, h->bam_force_miss);
+        hipLaunchKernelGGL(k_bam_link, dim3(1), dim3(64), 0, st, (const u8*)S.d_text, text_end, n_cells, (int)B->n_ref, B->d_meta, (const u32*)S.d_err,
+                           (const u32*)d_first, (const u32*)d_exit, d_count, d_base, S.d_list, last ? 1 : 0);
+        if (B->pass == 1)
+            hipLaunchKernelGGL(k_bam_accumulate, dim3(std::min(n_cells, 8192u)), dim3(256), 0, st, (const EngineDev*)h->d_E, h->kp, (const u8*)S.d_text, n_cells, B->d_meta,
+                               (const u32*)d_count, (const u32*)d_base, (const u32*)S.d_list, (const int*)B->d_ref_allele, (const int*)B->d_ref_locus, (const u8*)B->d_ref_flags,
+                               B->d_entries, B->cap_entries);
+        else
+            hipLaunchKernelGGL(k_bam_pileup, dim3(std::min(n_cells, 8192u)), dim3(256), 0, st, (const u8*)S.d_text, n_cells, B->d_meta, (const u32*)d_count, (const u32*)d_base,
+                               (const u32*)S.d_list, (const int*)B->d_ref_allele, (const int*)B->d_allele_slot, (const u64*)h->d_aoff, h->kp.minscore, h->kp.max_xm, h->kp.minqual, B->d_counts);
+        hipLaunchKernelGGL(k_bam_carry_out, dim3(64), dim3(256), 0, st, (const u8*)S.d_text, B->d_carry, B->d_meta);
+        HIPCHK(h, hipMemcpyAsync(S.h_res, S.d_err, 16, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(S.h_res + 16, B->d_meta, sizeof(BamMeta), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipEventRecord(S.ev_done, st));
+        if (hipGetLastError() != hipSuccess) { bam_drop(h, false); return fail(h, MLST_E_HIP, "a BAM kernel could not be launched"); }
+        // the piece before, while the GPU works on this one
+        if (B->pend) { const int rc = bam_finish(h, &done); if (rc) return rc; }
+        B->cur = sl; B->pend = true; B->first = false;
+        if (last || !piped) { const int rc = bam_finish(h, &done); if (rc) return rc; }
+        if (n_records_out) *n_records_out = done;
+        if (!last) return MLST_OK;
+    }
+    // the stream ends here
+    int rc = MLST_OK;
+    if (B->pass == 1) rc = bam_bank(h); else B->counts_ready = true;
+    B->open = false;
+    return rc;
+}
+
+extern "C" int mlst_bam_pileup_fetch(mlst_handle* h, uint32_t* counts) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    BamStream* B = h->bam;
+    if (!B || B->open || !B->counts_ready) return fail(h, MLST_E_INVALID, "no finished pass-2 BAM stream");
+    if (B->n_cols && !counts) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    if (B->n_cols) { HIPCHK(h, hipMemcpyAsync(counts, B->d_counts, B->n_cols * 16, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream)); }
+    return MLST_OK;
+}
+
+// test hook (include/mlst_debug.h): every `force_miss_every`-th cell's guess is thrown away, so that k_bam_link walks it itself
+extern "C" int mlst_debug_bam_split(mlst_handle* h, uint32_t force_miss_every, uint64_t* cells_rewalked_out) {
+    if (!h) return MLST_E_INVALID;
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    h->bam_force_miss = force_miss_every;
+    if (cells_rewalked_out) *cells_rewalked_out = h->bam ? h->bam->rewalked : 0;
+    return MLST_OK;
+}
+
 // BGZF block CRCs (include/mlst.h): the switch may change only between streams -- a piece in flight was queued with or without the check
 // (any open stream counts, a text stream of mlst_submit_fastq_stream and a paired stream that failed and was not reset included)
 extern "C" int mlst_set_bgzf_verify(mlst_handle* h, int on) {
     if (!h) return MLST_E_INVALID;
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
     h->bgzf_verify = on != 0;
     return MLST_OK;
 }

@@ -66,6 +66,11 @@ class BgzfCrcMismatch(MlstError):
         self.file = file
 
 
+class HostPathNeeded(MlstError):
+    """The library's "host path needed: <reason> at record <n>" (mlst_submit_bam_bgzf): the BAM holds a record the device does not
+    treat; the caller runs samin.AlignmentSample on the file, which raises or answers as the reference would."""
+
+
 class CorruptInput(Exception):
     """a BGZF block of the file `path` does not have the CRC-32 of its trailer: the device's report or the host's, with the file's name"""
 
@@ -178,6 +183,11 @@ def load_library(path: str | None = None):
         "mlst_submit_fastq_pair": (C.c_int, [H, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "mlst_get_route_trace": (C.c_int, [H, u64p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "mlst_debug_route_realloc": (C.c_int, [H, C.c_uint64]),
+        "mlst_bam_open": (C.c_int, [H, C.c_int, i32p, i32p, u8p, C.c_uint32, C.c_uint32, u32p, C.c_uint32]),
+        "mlst_submit_bam_bgzf": (C.c_int, [H, u8p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mlst_bam_set_capacity": (C.c_int, [H, C.c_uint64]),
+        "mlst_bam_pileup_fetch": (C.c_int, [H, u32p]),
+        "mlst_debug_bam_split": (C.c_int, [H, C.c_uint32, C.POINTER(C.c_uint64)]),
         "mlst_synchronize": (C.c_int, [H]),
     }
     tolerant = bool(os.environ.get("MLST_LIB_ALLOW_MISSING"))      # A/B runs against an older build (profiles/ab.sh)
@@ -286,6 +296,8 @@ class Engine:
             text = msg.decode() if msg else "?"
             if rc == -1 and text.startswith("CRC mismatch in BGZF block"):      # MLST_E_INVALID with k_bgzf_crc's report (include/mlst.h)
                 raise BgzfCrcMismatch("%s failed (%d): %s" % (what, rc, text), 1 if " of file 1 " in text else 2 if " of file 2 " in text else None)
+            if rc == -1 and text.startswith("host path needed"):
+                raise HostPathNeeded("%s: %s" % (what, text))
             raise MlstError("%s failed (%d): %s" % (what, rc, text))
 
     # ---- reference ----
@@ -360,6 +372,87 @@ class Engine:
         three waves per CU (k_inflate_tok2 holds four: 65,536 blocks a turn), and the chunk behind it is copied and inflated
         meanwhile; the library cuts a first chunk's head and a last chunk's tail off as pieces of their own (mlst_submit_fastq_bgzf)."""
         return self._submit_bgzf_pieces(path, 0, os.path.getsize(path), chunk_bytes, paired, True)
+
+    # ---- BGZF BAM (ready-made alignments) ----
+    def bam_open(self, which: int, ref_allele, ref_locus, ref_flags, skip_bytes: int = 0, chosen=None) -> None:
+        """Open a BAM stream (mlst_bam_open): which = 1 accumulates, 2 piles the records of `chosen` up; the three tables come
+        from the BAM header (samin.bam_ref_table), skip_bytes from samin.read_bam_header."""
+        ra, rl, rf = np.ascontiguousarray(ref_allele, np.int32), np.ascontiguousarray(ref_locus, np.int32), np.ascontiguousarray(ref_flags, np.uint8)
+        ch = np.ascontiguousarray([] if chosen is None else chosen, np.uint32)
+        self._check(self.lib.mlst_bam_open(self._h, int(which), _ptr(ra), _ptr(rl), _ptr(rf), ra.size, int(skip_bytes), _ptr(ch) if ch.size else None, ch.size),
+                    "mlst_bam_open")
+
+    def submit_bam_bgzf(self, data, final: bool, partial: bool = False):
+        """One chunk of the open BAM stream: whole BGZF blocks (partial: the buffer may end inside one).  Returns (records
+        completed by the call, bytes taken)."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+        n, used = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mlst_submit_bam_bgzf(self._h, _ptr(buf) if buf.size else None, buf.size, int(final), C.byref(n), C.byref(used) if partial else None),
+                    "mlst_submit_bam_bgzf")
+        return int(n.value), int(used.value) if partial else buf.size
+
+    def _bam_stream_file(self, path: str, lo: int, chunk_bytes: int) -> int:
+        """Compressed bytes [lo, end) of a BAM into the open stream, piece by piece (the reader ring of _submit_bgzf_pieces)."""
+        from .fastq import prefetch, raw_chunks, release_buffers
+        margin, hi = 1 << 17, os.path.getsize(path)
+        total, carry, at = 0, None, lo
+        n, used = C.c_uint64(), C.c_uint64()
+        if hi <= lo:
+            self._check(self.lib.mlst_submit_bam_bgzf(self._h, None, 0, 1, C.byref(n), None), "mlst_submit_bam_bgzf")
+            return int(n.value)
+        ring: list = []
+        try:
+            for buf, got in prefetch(raw_chunks(path, chunk_bytes, lo, hi, margin, reuse=True, ring=ring)):
+                at += got
+                c = 0 if carry is None else carry.size
+                if c > margin:
+                    raise MlstError("a BGZF block of more than %d bytes?" % margin)
+                if c:
+                    buf[margin - c:margin] = carry
+                view = buf[margin - c:margin + got]
+                last = at >= hi
+                self._check(self.lib.mlst_submit_bam_bgzf(self._h, _ptr(view), view.size, int(last), C.byref(n), None if last else C.byref(used)),
+                            "mlst_submit_bam_bgzf")
+                total += int(n.value)
+                carry = None if last else view[int(used.value):].copy()
+        finally:
+            release_buffers(ring)
+        return total
+
+    def submit_bam_file(self, path: str, species_filter: str | None = None, chunk_bytes: int = 64 << 20) -> int:
+        """Pass 1 over a BGZF BAM (hit accumulation, metamlst.py:101-130) on the device; returns the number of records.  The
+        statistics are the engine's (stats(), typing_*).  HostPathNeeded: a record only the host reader treats.  With set_bgzf_verify
+        on, the blocks of the header are checked on the host (fastq.BgzfCrcError), those of the records on the device."""
+        from .samin import bam_ref_table, read_bam_header
+        names, lo, skip = read_bam_header(path, self.bgzf_verify)      # (the header's blocks are the host's to check)
+        self.bam_open(1, *bam_ref_table(self.index, names, species_filter), skip_bytes=skip)
+        return self._bam_stream_file(path, lo, chunk_bytes)
+
+    def pileup_bam_file(self, path: str, chosen, chunk_bytes: int = 64 << 20) -> dict[int, np.ndarray]:
+        """Pass 2 over a BGZF BAM: {allele idx: uint32[len, 4]} of the chosen contigs, counted on the device from the records in
+        place (true AS / XM by name, the engine's minscore / max_xm / minqual)."""
+        from .samin import bam_ref_table, read_bam_header
+        names, lo, skip = read_bam_header(path, self.bgzf_verify)      # (the header's blocks are the host's to check)
+        ch = np.ascontiguousarray(chosen, np.uint32)
+        self.bam_open(2, *bam_ref_table(self.index, names, None), skip_bytes=skip, chosen=ch)
+        self._bam_stream_file(path, lo, chunk_bytes)
+        lens = [int(self.index.off[a + 1] - self.index.off[a]) for a in ch]
+        counts = np.zeros((max(1, sum(lens)), 4), np.uint32)
+        self._check(self.lib.mlst_bam_pileup_fetch(self._h, _ptr(counts)), "mlst_bam_pileup_fetch")
+        out, at = {}, 0
+        for a, L in zip(ch, lens):
+            out[int(a)] = counts[at:at + L]
+            at += L
+        return out
+
+    def bam_set_capacity(self, max_entries: int) -> None:
+        self._check(self.lib.mlst_bam_set_capacity(self._h, int(max_entries)), "mlst_bam_set_capacity")
+
+    def debug_bam_split(self, force_miss_every: int = 0) -> int:
+        """Test hook (mlst_debug_bam_split): returns the cells the last BAM stream walked again."""
+        n = C.c_uint64()
+        self._check(self.lib.mlst_debug_bam_split(self._h, int(force_miss_every), C.byref(n)), "mlst_debug_bam_split")
+        return int(n.value)
 
     def submit_fastq_bgzf_pair(self, data1, data2, final: bool) -> int:
         """Pass 1 from the two bgzip'd files of a paired-end sample: whole BGZF blocks of file 1 and of file 2 (any number of

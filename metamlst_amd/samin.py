@@ -229,3 +229,119 @@ class AlignmentSample:
                 qual[int(seq_off[k]):int(seq_off[k]) + len(q)] = q - 33
         return engine.pileup_alignments(chosen, rec_allele, rec_pos, rec_as, rec_xm, cig_off, cig, seq_off, seq, qual,
                                         a.minscore, a.max_xM, minqual)
+
+
+# ------------------------------------------------------------------ BGZF BAM on the device
+def is_bgzf_bam(path: str) -> bool:
+    """True for a BAM written as BGZF (what samtools and bowtie2 | samtools view -b write): the device path's input."""
+    import zlib
+    with open(path, "rb") as f:
+        head = f.read(65536 + 32)
+    if len(head) < 28 or head[:4] != b"\x1f\x8b\x08\x04":
+        return False
+    xlen = struct.unpack_from("<H", head, 10)[0]
+    at, bsize = 12, None
+    while at + 4 <= 12 + xlen:
+        si1, si2, slen = head[at], head[at + 1], struct.unpack_from("<H", head, at + 2)[0]
+        if si1 == 66 and si2 == 67 and slen == 2:
+            bsize = struct.unpack_from("<H", head, at + 4)[0] + 1
+        at += 4 + slen
+    if bsize is None or bsize > len(head):
+        return False
+    try:
+        return zlib.decompressobj(-15).decompress(head[12 + xlen:bsize - 8], 4) == b"BAM\1"
+    except zlib.error:
+        return False
+
+
+def read_bam_header(path: str, verify_crc: bool = False):
+    """The header of a BGZF BAM, inflated on the host block by block: -> (reference names, offset, skip_bytes): the records begin
+    `skip_bytes` inflated bytes into the BGZF block at compressed `offset` (mlst_bam_open / mlst_submit_bam_bgzf take it from there).
+    Every block read here must inflate to the length its trailer states (ISIZE); verify_crc: and have the trailer's CRC-32
+    (fastq.BgzfCrcError with the block's offset) -- the blocks in front of `offset` never reach the device's check, and the
+    reference names they hold decide which allele a record counts for."""
+    from .fastq import _bgzf_read_block
+    buf = bytearray()
+    blocks = []                              # (compressed offset, inflated offset, inflated length)
+    with open(path, "rb") as f:
+        state = {"coff": 0}
+
+        def more():
+            n, text = _bgzf_read_block(f, state["coff"], verify_crc)
+            if n == 0:
+                return False
+            f.seek(state["coff"] + n - 4)
+            if struct.unpack("<I", f.read(4))[0] != len(text):
+                raise ValueError("the BGZF block at byte %d does not inflate to the length of its trailer" % state["coff"])
+            blocks.append((state["coff"], len(buf), len(text)))
+            buf.extend(text)
+            state["coff"] += n
+            return True
+
+        def need(pos, n):
+            while len(buf) < pos + n:
+                if not more():
+                    raise ValueError("truncated BAM")
+
+        need(0, 8)
+        if bytes(buf[:4]) != b"BAM\1":
+            raise ValueError("not a BAM file")
+        pos = 8 + struct.unpack_from("<i", buf, 4)[0]
+        need(pos, 4)
+        n_ref = struct.unpack_from("<i", buf, pos)[0]
+        pos += 4
+        names = []
+        for _ in range(n_ref):
+            need(pos, 4)
+            ln = struct.unpack_from("<i", buf, pos)[0]
+            need(pos + 4, ln + 4)
+            names.append(bytes(buf[pos + 4:pos + 4 + ln - 1]).decode("ascii"))
+            pos += 8 + ln
+        for coff, u0, ulen in blocks:
+            if u0 <= pos < u0 + ulen:
+                return names, coff, pos - u0
+        return names, state["coff"], 0       # the header ends with its block
+
+
+def bam_ref_table(index: AlleleIndex, names, species_filter: str | None = None):
+    """Per reference sequence of a BAM header: (allele index or -1, locus index or -1, flags) with the name rules of
+    AlignmentSample.add / .stats(): flags bit 0 = the species passes --filter (metamlst.py:114), bit 1 = the name does not split
+    in three at '_' (the reference raises there, metamlst.py:106)."""
+    label2a = {index.label(a): a for a in range(index.n_alleles)}
+    allowed = species_filter.split(",") if species_filter else None
+    n = len(names)
+    ra, rl, rf = np.full(n, -1, np.int32), np.full(n, -1, np.int32), np.zeros(n, np.uint8)
+    for k, name in enumerate(names):
+        parts = name.split("_")
+        if len(parts) != 3:
+            rf[k] = 2
+            continue
+        sp, g, _ = parts
+        if allowed is None or sp in allowed:
+            rf[k] = 1
+        ra[k] = label2a.get(name, -1)
+        try:
+            rl[k] = index.locus_index(sp, g)
+        except Exception:
+            pass
+    return ra, rl, rf
+
+
+class BamSample:
+    """AlignmentSample's two faces for a BGZF BAM typed on the device: .stats() and .pileup(engine, chosen).  The engine's
+    parameters (minscore, max_xm, min_read_len, minqual) are the sample's.  HostPathNeeded from either: use AlignmentSample."""
+
+    def __init__(self, index: AlleleIndex, args: TypingArgs | None, engine):
+        self.index, self.args, self.engine = index, args or TypingArgs(), engine
+        self.path, self.n_records = None, 0
+
+    def add_file(self, path: str, chunk_bytes: int = 64 << 20):
+        self.path = path
+        self.n_records = self.engine.submit_bam_file(path, self.args.filter or None, chunk_bytes)
+        return self
+
+    def stats(self) -> SampleStats:
+        return self.engine.stats()
+
+    def pileup(self, engine, chosen, chunk_bytes: int = 64 << 20) -> dict:
+        return engine.pileup_bam_file(self.path, chosen, chunk_bytes)
