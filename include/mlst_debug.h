@@ -52,6 +52,12 @@ int mlst_debug_bgzf_walk(const uint8_t* data, uint64_t n_bytes, uint64_t* n_bloc
 int mlst_get_route_trace(mlst_handle* h, uint64_t* out, uint64_t cap_words, uint64_t* n_words);
 int mlst_debug_route_realloc(mlst_handle* h, uint64_t pad_bytes);
 
+/* The consumer of the routed sieve (k_route_probe with examiner waves, MLST_PROBE_EXAM_WAVES; tests/test_gpu_probe_examiners.py).
+ * Waits for the stream.  *ring_full: blocks of parked entries that found the workgroup's LDS ring full and went to the global
+ * list instead, summed over the sample.  *n_cand: the sample's candidates; cand (optional, room for cap values): the candidate
+ * list of the LAST submission, in no particular order -- the whole sample's only where the sample was one submission. */
+int mlst_debug_route_probe(mlst_handle* h, uint64_t* ring_full, uint32_t* cand, uint64_t cap, uint64_t* n_cand);
+
 /* The record split of BAM input (csrc/bam_dev.h): force_miss_every = n > 0 throws the guessed record start of every n-th cell
  * of the streams that follow away, so that the chain walk has to enter those cells from their true entry (the path a wrong guess
  * takes); 0 = off.  *cells_rewalked_out: cells walked again during the last stream.  Only while no BAM stream is open. */

@@ -148,7 +148,8 @@ struct Counters {
     // with these two in front of cnt[], k_extend, whose code had not changed, ran 0.62 instead of 0.55 ms)
     u64 rt_next;         // routed sieve: tiles handed out beyond every producer's first one (zero between submissions)
     u64 rt_parked;       // routed sieve: entries that passed the filter and wait in R.parked for k_route_verify (zero between submissions)
-    u64 pad_[14];        // the block stays a multiple of 128 bytes longer than it was in round 2
+    u64 rt_ring_full;    // routed sieve: blocks of parked entries that found the consumer's LDS ring full and left for R.parked (cumulative; mlst_debug_route_probe)
+    u64 pad_[13];        // the block stays a multiple of 128 bytes longer than it was in round 2
     u64 ext_q2[EXT_Q][16];      // work queues of k_extend_pairs (as ext_q; 4 KB: the arrays behind keep their alignment)
 };
 // item_state bits
@@ -610,7 +611,8 @@ __device__ inline bool bin_exact(u32 w0, u32 w1, const uint4* __restrict__ sieve
 //   k_route_probe  one workgroup per owner holds the owner's 128 KiB filter slice in LDS (three bits in each of two 32-bit
 //                  words per key, rt_filter_addr: ~0.3 % of foreign seeds pass, 0.2 % of them collisions of the 33 hash bits), streams the owner's regions 16 bytes per lane, and sends the
 //                  entries that pass the exact way: the read's seeds are re-hashed, the one(s) equal to the entry's hash
-//                  probe the fingerprint sieve, a hit sets the read's candidate flag.
+//                  probe the fingerprint sieve, a hit sets the read's candidate flag.  The exact way is walked by examiner
+//                  waves of the same workgroup, fed through a ring in LDS (RtRing); what the ring cannot take, by k_route_verify.
 //   k_flag_compact candidate flags -> candidate list.
 // A tile that would overflow a region or the sort buffer (only degenerate data: low-complexity reads crowd one owner) is
 // not routed at all: its reads become candidates outright (k_seed looks every candidate up exactly), and the producer's
@@ -656,9 +658,11 @@ struct RouteDev {
     GP<const u32> filter;            // [owner][RT_FWORDS]
     GP<u32> flags;                   // candidate flag per read (zeroed per submission)
     GP<u64> trace;                   // diagnostics (mlst_get_route_trace), NULL when off: four words per workgroup
-    GP<u64> parked; u64 parked_cap;  // entries that passed the filter (rt_park), examined by k_route_verify
+    GP<u64> parked; u64 parked_cap;  // entries that passed the filter (rt_park) and did not fit k_route_probe's ring, examined by k_route_verify
     u32 cap, n_prod, tiles_max, nw;  // nw = waves per producer workgroup = groups of 64 reads per tile
-    u32 dbg;                         // profiling builds of the launch: bit 0 = entries that pass the filter are not examined (timing only, results wrong)
+    u32 dbg;                         // MLST_RT_DEBUG: 2 = examine in place, 8 = parked reads become candidates unexamined, 16 = the LDS ring is bypassed (examiner waves
+                                     // idle); results unchanged.  Builds with -DMLST_RT_EXPERIMENTS only: 1 = entries that pass the filter are not examined,
+                                     // 4 = every second one is dropped (timing only, candidates are lost)
 };
 // where and when a workgroup ran: XCC id | HW_ID << 32, wall clock at its start; the end is stored by rt_trace_end
 __device__ inline void rt_trace_begin(const RouteDev& R, u32 slot) {
@@ -961,11 +965,13 @@ __device__ inline void rt_examine_one(u64 e, const u32* __restrict__ packed, u64
     const u32 tile = R.emitted[(u64)p * (R.tiles_max + 1) + 1 + jt];
     const u64 rr = ((u64)tile * NWP + wv) * 64 + ln;
     if (rr >= n_reads) return;
-    // experiments of round 5 (MLST_RT_DEBUG, profiles/round5/sieve.md): 4 = every second entry is dropped unexamined (TIMING ONLY,
+    // experiments of round 5 (MLST_RT_DEBUG, profiles/round5/sieve.md): 4 (-DMLST_RT_EXPERIMENTS builds) = every second entry is dropped unexamined (TIMING ONLY,
     // candidates are lost: what the examination would cost if a check on the entry's 33 hash bits alone removed the filter's false
     // positives first); 8 = the read becomes a candidate without its row being fetched (results unchanged -- k_seed looks every
     // seed of a candidate up exactly -- but k_seed sees every parked read: what leaving the examination out would cost there)
+#ifdef MLST_RT_EXPERIMENTS
     if ((R.dbg & 4u) && (((u32)e ^ (u32)(e >> 7)) & 1u)) return;
+#endif
     if (R.dbg & 8u) { atomicOr(&R.flags.p[rr >> 5], 1u << (rr & 31)); return; }
     // a read on a locus arrives here nine times, from nine owners: once its flag is up the other eight need no row (640
     // bytes each).  A stale look (the flag words are written by atomics of other XCDs) only costs the fetch it would have saved.
@@ -986,25 +992,107 @@ __device__ inline void rt_examine_one(u64 e, const u32* __restrict__ packed, u64
     if (nm == 1) hit = bin_exact(k0, k1, sieve, smask, sshift);
     if (hit) atomicOr(&R.flags.p[rr >> 5], 1u << (rr & 31));
 }
-// up to 64 parked entries of one wave leave for k_route_verify (one atomic, one coalesced store); when the list is full
-// they are examined here
+// The ring of parked entries inside k_route_probe (its examiner waves): a bounded queue of blocks of up to 64 entries in
+// LDS, many producers (the streaming waves) and many consumers, with a sequence number per block (seq == ticket: free for
+// the producer that draws this ticket; == ticket + 1: filled; the consumer hands it on as ticket + RT_RING_BLOCKS).  The
+// waves of ONE workgroup meet here and nowhere else: they are resident together by construction, a producer never waits
+// (a full ring sends its block to R.parked instead), and every retry loop below is bounded.  A streaming wave publishes
+// about a dozen blocks per launch, so the tickets are all but uncontended.
+#define RT_EXAM_DEFAULT 4              // examiner waves of k_route_probe (MLST_PROBE_EXAM_WAVES; the sweep: profiles/round6/probe_examiners.md)
+#define RT_RING_BLOCKS 16              // 8 KiB of entries: with the filter slice and s_q 152 KiB of the CU's 160
+#define RT_RING_TRIES  32              // draws of a ticket that lost against another wave before the ring counts as full / empty
+#define RT_RING_IDLE   (1u << 22)      // looks at an empty ring (~1 us each) after which a waiting wave goes on to the closing barrier
+struct RtRing {
+    u64 ent[RT_RING_BLOCKS][64];
+    u32 seq[RT_RING_BLOCKS], cnt[RT_RING_BLOCKS];
+    u32 head, tail, done;              // tickets drawn by producers / by consumers; streaming waves that have published their last block
+};
+#define RT_LDS_LOAD(p, order)  __hip_atomic_load((p), order, __HIP_MEMORY_SCOPE_WORKGROUP)
+// cnt <= 64 entries (lane = entry) become one block of the ring; false = the ring is full (nothing was written)
+__device__ inline bool rt_ring_push(RtRing& g, u64 e, u32 cnt, int lane) {
+    u32 pos = 0, got = 0;
+    if (lane == 0) {
+        for (int t = 0; t < RT_RING_TRIES && !got; t++) {
+            pos = RT_LDS_LOAD(&g.head, __ATOMIC_RELAXED);
+            const int dif = (int)(RT_LDS_LOAD(&g.seq[pos % RT_RING_BLOCKS], __ATOMIC_ACQUIRE) - pos);
+            if (dif < 0) break;                                                  // the block of this ticket has not been taken out yet: full
+            if (dif == 0) got = __hip_atomic_compare_exchange_strong(&g.head, &pos, pos + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) ? 1u : 0u;
+        }
+    }
+    got = (u32)__builtin_amdgcn_readfirstlane((int)got); pos = (u32)__builtin_amdgcn_readfirstlane((int)pos);
+    if (!got) return false;
+    const u32 b = pos % RT_RING_BLOCKS;
+    if ((u32)lane < cnt) g.ent[b][lane] = e;
+    if (lane == 0) g.cnt[b] = cnt;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // the wave's LDS writes above are in place before the block is published
+    if (lane == 0) __hip_atomic_store(&g.seq[b], pos + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return true;
+}
+// the next filled block, lane = entry: returns its number of entries, 0 = none is ready
+__device__ inline u32 rt_ring_pop(RtRing& g, u64& e, int lane) {
+    u32 pos = 0, got = 0;
+    if (lane == 0) {
+        for (int t = 0; t < RT_RING_TRIES && !got; t++) {
+            pos = RT_LDS_LOAD(&g.tail, __ATOMIC_RELAXED);
+            const int dif = (int)(RT_LDS_LOAD(&g.seq[pos % RT_RING_BLOCKS], __ATOMIC_ACQUIRE) - (pos + 1u));
+            if (dif < 0) break;                                                  // not published (yet): empty
+            if (dif == 0) got = __hip_atomic_compare_exchange_strong(&g.tail, &pos, pos + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) ? 1u : 0u;
+        }
+    }
+    got = (u32)__builtin_amdgcn_readfirstlane((int)got); pos = (u32)__builtin_amdgcn_readfirstlane((int)pos);
+    if (!got) return 0u;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const u32 b = pos % RT_RING_BLOCKS;
+    u32 n = g.cnt[b]; n = (u32)__builtin_amdgcn_readfirstlane((int)(n < 64u ? n : 64u));
+    e = (u32)lane < n ? g.ent[b][lane] : 0ull;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // the entries are in registers before the block is handed back
+    if (lane == 0) __hip_atomic_store(&g.seq[b], pos + RT_RING_BLOCKS, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return n;
+}
+// A wave takes blocks out of the ring and examines them.  wait: an empty ring ends the wave's turn only once all n_stream
+// streaming waves have published their last block (`done` is read BEFORE the look at the ring); it sleeps between looks, and
+// after RT_RING_IDLE of them it leaves for the closing barrier, behind which every wave calls this once more without waiting
+// (everything has been published by then), so that no entry is lost whichever way a wave left.
+template <int WPR>
+__device__ inline void rt_ring_serve(RtRing& g, u32 n_stream, bool wait, int lane, const u32* __restrict__ packed, u64 n_reads, const RouteDev& R, u32 NWP,
+                                     const uint4* __restrict__ sieve, u32 smask, u32 sshift) {
+    for (u32 idle = 0;;) {
+        const u32 dn = wait ? (u32)__builtin_amdgcn_readfirstlane((int)RT_LDS_LOAD(&g.done, __ATOMIC_ACQUIRE)) : n_stream;
+        u64 e; const u32 n = rt_ring_pop(g, e, lane);
+        if (n) { if ((u32)lane < n) rt_examine_one<WPR, true>(e, packed, n_reads, R, NWP, sieve, smask, sshift); idle = 0; continue; }
+        if (dn >= n_stream || ++idle > RT_RING_IDLE) break;
+        __builtin_amdgcn_s_sleep(16);
+    }
+}
+// up to 64 parked entries of one wave leave the streaming loop: into the workgroup's ring where there is one (one LDS atomic),
+// else -- or when the ring is full: a degenerate batch -- to R.parked for k_route_verify (one atomic, one coalesced store);
+// when that list is full too they are examined here
 template <int WPR>
 __device__ inline void rt_flush(const u64* q, u32 cnt, int lane, const u32* __restrict__ packed, u64 n_reads, const RouteDev& R, u32 NWP,
-                                const uint4* __restrict__ sieve, u32 smask, u32 sshift, Counters* __restrict__ ctr) {
-    if (cnt == 0 || (R.dbg & 1u)) return;
-    u64 base = 0;
-    if (lane == 0) base = atomicAdd(&ctr->rt_parked, (u64)cnt);
-    base = uniform_u64(base);
+                                const uint4* __restrict__ sieve, u32 smask, u32 sshift, Counters* __restrict__ ctr, RtRing* ring = nullptr) {
+    if (cnt == 0) return;
+#ifdef MLST_RT_EXPERIMENTS
+    if (R.dbg & 1u) return;
+#endif
     u64 e = 0;
     if ((u32)lane < cnt) {      // the queue holds entry | (run | region << 20) << 32: packed here, 64 at a time, not where an entry passed the filter
         const u64 raw = q[lane]; const u32 hi = (u32)(raw >> 32), run = hi & 0xFFFFFu, p = hi >> 20;
         e = rt_park((u32)raw, run & (NWP - 1u), NWP == 16 ? run >> 4 : run >> 3, p);
     }
+    if (ring) {
+        if (!(R.dbg & 16u) && rt_ring_push(*ring, e, cnt, lane)) return;
+        if (lane == 0 && !(R.dbg & 16u)) atomicAdd(&ctr->rt_ring_full, 1ull);
+    }
+    u64 base = 0;
+    if (lane == 0) base = atomicAdd(&ctr->rt_parked, (u64)cnt);
+    base = uniform_u64(base);
     if (base + cnt <= R.parked_cap) { if ((u32)lane < cnt) R.parked[base + (u32)lane] = e; }
     else if ((u32)lane < cnt) rt_examine_one<WPR, false>(e, packed, n_reads, R, NWP, sieve, smask, sshift);
 }
-// the entries that passed the LDS filter, examined at full occupancy (inside k_route_probe, whose 147 KB of LDS allow 16
-// waves per CU, the three round trips of an examination stalled the streaming waves: 0.5 of 1.2 ms at 7.7 M entries)
+// the entries of the global parked list, examined at full occupancy: all that passed the LDS filter where k_route_probe has no
+// examiner waves (MLST_PROBE_EXAM_WAVES=0), else the blocks that found its ring full -- normally none, and the launch is a few
+// microseconds.  (Inside k_route_probe, whose LDS allows 16 waves per CU, the three round trips of an examination stalled the
+// STREAMING waves that did it themselves: 0.5 of 1.2 ms at 7.7 M entries; waves of its own do it there since round 6.)
 template <int WPR>
 __global__ __launch_bounds__(256) void k_route_verify(const u32* __restrict__ packed, u64 n_reads, const uint4* __restrict__ sieve, u32 smask, const RouteDev R,
                                                       Counters* __restrict__ ctr) {
@@ -1013,11 +1101,22 @@ __global__ __launch_bounds__(256) void k_route_verify(const u32* __restrict__ pa
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x)
         rt_examine_one<WPR, true>(R.parked[i], packed, n_reads, R, R.nw, sieve, smask, sshift);
 }
-template <int WPR, int PF>
+// EX = examiner waves: of the workgroup's 16 waves, S = 16 - EX stream the owner's regions through the filter and hand the
+// entries that pass, 64 at a time, to a ring in LDS (RtRing); the other EX take them from there, lane = entry, and examine them
+// (rt_examine_one: three dependent round trips, no LDS, few vector instructions -- on wave slots the streaming waves' three
+// budgets leave idle; a streaming wave that examined its own entries stalled for them: 0.5 of 1.2 ms in round 3).  A streaming
+// wave that has finished its regions examines as well.  EX = 0: every block goes to R.parked for k_route_verify, as before
+// round 6 (MLST_PROBE_EXAM_WAVES=0, the A/B switch); with EX > 0 only the blocks that find the ring full do.
+// Both barriers are reached by all 16 waves whatever their role.
+template <int WPR, int PF, int EX>
 __global__ __launch_bounds__(1024) void k_route_probe(const u32* __restrict__ packed, u64 n_reads,
                                                       const uint4* __restrict__ sieve, u32 smask, const RouteDev R, Counters* __restrict__ ctr) {
+    constexpr u32 S = 16 - EX;                    // streaming waves: wave w < S takes the regions w, w + S, ...
+    constexpr int NC = (RT_MAXP + 64 * (int)S - 1) / (64 * (int)S);
     __shared__ __attribute__((aligned(16))) u32 s_f[RT_FWORDS];
     __shared__ u64 s_q[16][128];                  // per-wave queue of entries that passed the filter: read | hash << 32
+    RtRing* ring = nullptr;
+    if constexpr (EX > 0) { __shared__ RtRing s_ring; ring = &s_ring; }
     // PF = 16-byte loads per lane in flight: 2 (2 KiB per wave, 32 KiB per CU) or 4
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u32 owner = blockIdx.x, P = R.n_prod;
@@ -1028,23 +1127,28 @@ __global__ __launch_bounds__(1024) void k_route_probe(const u32* __restrict__ pa
         #pragma unroll
         for (int j = 0; j < RT_FWORDS / 4 / 1024; j++) s4[tid + 1024 * j] = g4[tid + 1024 * j];
     }
+    if constexpr (EX > 0) {
+        if (tid < RT_RING_BLOCKS) { ring->seq[tid] = (u32)tid; ring->cnt[tid] = 0u; }
+        if (tid == 0) { ring->head = 0u; ring->tail = 0u; ring->done = 0u; }
+    }
     __syncthreads();
     const u32 NWP = R.nw;                          // runs per tile in a region (one per producer wave)
     u64* const q = s_q[wave]; u32 qn = 0, n_pass = 0;      // wave-uniform: parked entries; entries that passed the filter so far
     const u64 lt = lane ? (~0ull >> (64 - lane)) : 0ull;
     const v4u none4 = {RT_DUMMY, RT_DUMMY, RT_DUMMY, RT_DUMMY};      // lanes beyond a region's end: neither a seed nor a run start
-    // the entry counts of this wave's regions (lane i: region wave + 16 i), fetched once: read region by region they cost a
+    if ((u32)wave < S) {                           // ---- a streaming wave
+    // the entry counts of this wave's regions (lane i: region wave + S i), fetched once: read region by region they cost a
     // dependent round trip in front of every region's first load
-    u32 my_n[RT_MAXP / 1024];
+    u32 my_n[NC];
     #pragma unroll
-    for (int c = 0; c < RT_MAXP / 1024; c++) {
-        const u32 pp = (u32)wave + 16u * ((u32)lane + 64u * c);
+    for (int c = 0; c < NC; c++) {
+        const u32 pp = (u32)wave + S * ((u32)lane + 64u * c);
         my_n[c] = pp < P ? R.counts[(u64)owner * P + pp] : 0u;
     }
-    for (u32 p = (u32)wave, pi = 0; p < P; p += 16, pi++) {      // this wave's regions
+    for (u32 p = (u32)wave, pi = 0; p < P; p += S, pi++) {      // this wave's regions
         u32 n = 0;
         #pragma unroll
-        for (int c = 0; c < RT_MAXP / 1024; c++) if ((pi >> 6) == (u32)c) n = (u32)__shfl((int)my_n[c], (int)(pi & 63));
+        for (int c = 0; c < NC; c++) if ((pi >> 6) == (u32)c) n = (u32)__shfl((int)my_n[c], (int)(pi & 63));
         n = (u32)__builtin_amdgcn_readfirstlane((int)n);
         const auto ent4 = reinterpret_cast<const v4u GLOBAL_AS*>(R.arena.g() + ((u64)owner * P + p) * R.cap);
         int seq = -1;                               // flags seen so far - 1 = sequence number of the current (tile, wave) run
@@ -1099,7 +1203,7 @@ __global__ __launch_bounds__(1024) void k_route_probe(const u32* __restrict__ pa
                         qn += (u32)__popcll(pm);
                         if (qn >= 64) {
                             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                            rt_flush<WPR>(q + (qn - 64), 64, lane, packed, n_reads, R, NWP, sieve, smask, sshift, ctr);
+                            rt_flush<WPR>(q + (qn - 64), 64, lane, packed, n_reads, R, NWP, sieve, smask, sshift, ctr, ring);
                             qn -= 64; n_pass += 64;
                         }
                     }
@@ -1109,9 +1213,22 @@ __global__ __launch_bounds__(1024) void k_route_probe(const u32* __restrict__ pa
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    rt_flush<WPR>(q, qn, lane, packed, n_reads, R, NWP, sieve, smask, sshift, ctr);
+    rt_flush<WPR>(q, qn, lane, packed, n_reads, R, NWP, sieve, smask, sshift, ctr, ring);
     n_pass += qn;
     if (lane == 0 && n_pass) atomicAdd(&ctr->cnt[MLST_CNT_SIEVE_PASS], (u64)n_pass);
+    if constexpr (EX > 0) {                        // this wave's last block is in the ring (or in R.parked)
+        if (lane == 0) __hip_atomic_fetch_add(&ring->done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    }
+    if constexpr (EX > 0) {
+        // examiners from the start, streaming waves from here: the ring is served until every streaming wave is done, then,
+        // behind the closing barrier, looked at once more (rt_ring_serve).  One barrier, passed once by each of the 16 waves.
+        #pragma unroll 1
+        for (int turn = 0; turn < 2; turn++) {
+            rt_ring_serve<WPR>(*ring, S, turn == 0, lane, packed, n_reads, R, NWP, sieve, smask, sshift);
+            if (turn == 0) __syncthreads();
+        }
+    } else
     __syncthreads();
     if (tid == 0) { atomicMax(&ctr->sv_t1, (u64)wall_clock64()); rt_trace_end(R, P + owner); }
 }
@@ -3519,7 +3636,7 @@ struct mlst_handle {
     // CU-routed sieve (K1c): filter slices (reference) and the per-submission arena
     int sieve_kind = 0; u32 sieve_chain = 0; u64 n_keys = 0;
     u32* d_rfilter = nullptr; u32* d_rt_arena = nullptr; u64 cap_rt_arena = 0; u32* d_rt_counts = nullptr; u32* d_rt_emitted = nullptr; u64 cap_rt_emitted = 0;
-    u32 rt_prod = 0, rt_cap = 0, rt_tiles_max = 0, rt_nw = 16, rt_pf = 2; u64 rt_slice = 0;
+    u32 rt_prod = 0, rt_cap = 0, rt_tiles_max = 0, rt_nw = 16, rt_pf = 2, rt_exam = RT_EXAM_DEFAULT; u64 rt_slice = 0;
     u64* d_rt_parked = nullptr; u64 cap_rt_parked = 0;      // entries that passed the LDS filter (k_route_probe -> k_route_verify)
     u64* d_rt_trace = nullptr; bool rt_trace_on = false; const void* rt_last_packed = nullptr;      // mlst_get_route_trace
     std::vector<void*> dbg_pads;                 // mlst_debug_route_realloc: allocations kept to move the arena elsewhere
@@ -4340,6 +4457,8 @@ static int ensure_route_buffers(mlst_handle* h, u64 n_reads, u32 wpr, u64 n_read
     u32 nw = 16;                                        // waves per producer workgroup (tile = nw groups of 64 reads)
     { const char* e = getenv("MLST_ROUTE_WAVES"); if (e && atoi(e) == 8) nw = 8; }
     { const char* e = getenv("MLST_PROBE_PF"); h->rt_pf = (e && atoi(e) == 4) ? 4u : 2u; }
+    // examiner waves of k_route_probe: 1, 2 or 4 of its 16 (profiles/round6/probe_examiners.md); 0 = none, k_route_verify examines (A/B)
+    { const char* e = getenv("MLST_PROBE_EXAM_WAVES"); const int v = e ? atoi(e) : RT_EXAM_DEFAULT; h->rt_exam = (v == 0 || v == 1 || v == 2 || v == 4) ? (u32)v : (u32)RT_EXAM_DEFAULT; }
     const u64 tile = (u64)nw * 64, n_tiles = (n_reads + tile - 1) / tile;
     u32 prod = (wpr <= 10 ? 512u : 256u) * (16u / nw) / (u32)h->cu_split;  // as many workgroups as the LDS lets share the CUs
     { const char* e = getenv("MLST_ROUTE_BLOCKS"); if (e && atoi(e) > 0) prod = (u32)atoi(e); }
@@ -4415,7 +4534,7 @@ static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* 
     const int gs = phase ? 0 : graph_enter(h, h->g_submit, {(u64)(uintptr_t)d_packed, (u64)(uintptr_t)d_qrows, (u64)(uintptr_t)d_lens, (u64)n_reads, (u64)wpr,
                                                (u64)qstride, (u64)h->reads_seen, (u64)(uintptr_t)h->d_cand,
                                                (u64)(uintptr_t)h->d_bin_flags, (u64)(uintptr_t)h->d_rt_arena, (u64)(uintptr_t)h->d_rt_counts,
-                                               (u64)(uintptr_t)h->d_rt_emitted, (u64)h->rt_cap, (u64)h->rt_prod, (u64)h->rt_nw, (u64)paired, (u64)(uintptr_t)h->d_rt_trace, (u64)(uintptr_t)h->d_rt_parked, (u64)h->cap_rt_parked, (u64)h->rt_pf, rt_slice});
+                                               (u64)(uintptr_t)h->d_rt_emitted, (u64)h->rt_cap, (u64)h->rt_prod, (u64)h->rt_nw, (u64)paired, (u64)(uintptr_t)h->d_rt_trace, (u64)(uintptr_t)h->d_rt_parked, (u64)h->cap_rt_parked, (u64)h->rt_pf, rt_slice, (u64)h->rt_exam});
     if (gs == 1) { h->reads_seen += n_reads; return MLST_OK; }
     if (phase != 2) { Prof pf(h, 0);
       if (h->sieve_kind == MLST_SIEVE_LDS) {      // LDS first level: one 1024-thread workgroup per CU
@@ -4442,13 +4561,15 @@ static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* 
 #undef SIEVE_CASE
         }
         { Prof pb(h, 10);
-#define SIEVE_CASE(W) case W: if (h->rt_pf == 4) hipLaunchKernelGGL((k_route_probe<W, 4>), dim3(RT_OWNERS), dim3(1024), 0, h->stream, sl_packed, (u64)sl_n, E.sieve, E.sieve_mask, R, E.ctr); \
-                              else hipLaunchKernelGGL((k_route_probe<W, 2>), dim3(RT_OWNERS), dim3(1024), 0, h->stream, sl_packed, (u64)sl_n, E.sieve, E.sieve_mask, R, E.ctr); break;
+#define PROBE_LAUNCH(W, PF, EX) hipLaunchKernelGGL((k_route_probe<W, PF, EX>), dim3(RT_OWNERS), dim3(1024), 0, h->stream, sl_packed, (u64)sl_n, E.sieve, E.sieve_mask, R, E.ctr)
+#define SIEVE_CASE(W) case W: if (h->rt_exam == 1) PROBE_LAUNCH(W, 2, 1); else if (h->rt_exam == 2) PROBE_LAUNCH(W, 2, 2); else if (h->rt_exam == 4) PROBE_LAUNCH(W, 2, 4); \
+                              else if (h->rt_pf == 4) PROBE_LAUNCH(W, 4, 0); else PROBE_LAUNCH(W, 2, 0); break;
         switch (wpr) { SIEVE_CASE(2) SIEVE_CASE(4) SIEVE_CASE(6) SIEVE_CASE(8) SIEVE_CASE(10) SIEVE_CASE(12) SIEVE_CASE(14)
                        SIEVE_CASE(16) SIEVE_CASE(18) SIEVE_CASE(20) default: return fail(h, MLST_E_INVALID, "words_per_read %u unsupported", wpr); }
 #undef SIEVE_CASE
+#undef PROBE_LAUNCH
         }
-        { Prof pc(h, 11);
+        { Prof pc(h, 11);      // what k_route_probe left in R.parked: everything (MLST_PROBE_EXAM_WAVES=0) or the blocks that found its ring full (normally none)
 #define SIEVE_CASE(W) case W: hipLaunchKernelGGL(k_route_verify<W>, dim3(2048), dim3(256), 0, h->stream, sl_packed, (u64)sl_n, E.sieve, E.sieve_mask, R, E.ctr); break;
         switch (wpr) { SIEVE_CASE(2) SIEVE_CASE(4) SIEVE_CASE(6) SIEVE_CASE(8) SIEVE_CASE(10) SIEVE_CASE(12) SIEVE_CASE(14)
                        SIEVE_CASE(16) SIEVE_CASE(18) SIEVE_CASE(20) default: return fail(h, MLST_E_INVALID, "words_per_read %u unsupported", wpr); }
@@ -6459,6 +6580,20 @@ extern "C" int mlst_get_route_trace(mlst_handle* h, uint64_t* out, uint64_t cap_
     out[0] = h->rt_prod; out[1] = (u64)(uintptr_t)h->d_rt_arena; out[2] = (u64)(uintptr_t)h->rt_last_packed; out[3] = (u64)h->wall_khz;
     out[4] = h->rt_cap; out[5] = (u64)(uintptr_t)h->d_rfilter; out[6] = (u64)(uintptr_t)h->d_bin_flags; out[7] = h->cap_rt_arena;
     HIPCHK(h, hipMemcpy(out + 8, h->d_rt_trace, n_wg * 32, hipMemcpyDeviceToHost));
+    return MLST_OK;
+}
+extern "C" int mlst_debug_route_probe(mlst_handle* h, uint64_t* ring_full, uint32_t* cand, uint64_t cap, uint64_t* n_cand) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    hipSetDevice(h->device);
+    Counters* c = nullptr;
+    int rc = fetch_stats(h, &c); if (rc) return rc;
+    if (ring_full) *ring_full = c->rt_ring_full;
+    const u64 n = c->cnt[MLST_CNT_CANDIDATES];
+    if (n_cand) *n_cand = n;
+    if (cand && n) {
+        if (cap < n || h->cap_cand < n || !h->d_cand) return fail(h, MLST_E_INVALID, "candidate list: %llu entries, room for %llu", (unsigned long long)n, (unsigned long long)cap);
+        HIPCHK(h, hipMemcpy(cand, h->d_cand, n * 4, hipMemcpyDeviceToHost));
+    }
     return MLST_OK;
 }
 extern "C" int mlst_debug_route_realloc(mlst_handle* h, uint64_t pad_bytes) {

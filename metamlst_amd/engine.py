@@ -183,6 +183,7 @@ def load_library(path: str | None = None):
         "mlst_submit_fastq_pair": (C.c_int, [H, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "mlst_get_route_trace": (C.c_int, [H, u64p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "mlst_debug_route_realloc": (C.c_int, [H, C.c_uint64]),
+        "mlst_debug_route_probe": (C.c_int, [H, C.POINTER(C.c_uint64), u32p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "mlst_bam_open": (C.c_int, [H, C.c_int, i32p, i32p, u8p, C.c_uint32, C.c_uint32, u32p, C.c_uint32]),
         "mlst_submit_bam_bgzf": (C.c_int, [H, u8p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mlst_bam_set_capacity": (C.c_int, [H, C.c_uint64]),
@@ -855,6 +856,17 @@ class Engine:
     def debug_route_realloc(self, pad_bytes: int = 0):
         """pad_bytes = -1: keep the old arena allocated (the new one is other memory for certain)."""
         self._check(self.lib.mlst_debug_route_realloc(self._h, int(pad_bytes) & 0xFFFFFFFFFFFFFFFF), "mlst_debug_route_realloc")
+
+    def debug_route_probe(self, with_candidates: bool = True) -> tuple[int, np.ndarray | None]:
+        """Test hook (mlst_debug_route_probe): (blocks of parked entries that found the consumer's LDS ring full during the sample,
+        the sorted candidate list of the last submission or None)."""
+        full, n = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mlst_debug_route_probe(self._h, C.byref(full), None, 0, C.byref(n)), "mlst_debug_route_probe")
+        if not with_candidates:
+            return int(full.value), None
+        cand = np.zeros(max(int(n.value), 1), np.uint32)
+        self._check(self.lib.mlst_debug_route_probe(self._h, C.byref(full), _ptr(cand), cand.size, C.byref(n)), "mlst_debug_route_probe")
+        return int(full.value), np.sort(cand[:int(n.value)])
 
     def synchronize(self):
         self._check(self.lib.mlst_synchronize(self._h), "mlst_synchronize")
