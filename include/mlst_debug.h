@@ -24,6 +24,14 @@ int mlst_selftest_inflate(const uint8_t* in, uint64_t n_in, uint8_t* out, uint64
  * hook obeys too (a mismatch fails it with the block's number), of the inflate kernels and the CRC kernel behind them. */
 int mlst_selftest_inflate_device(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, uint8_t* out, uint64_t cap, uint64_t* produced, double* kernel_ms);
 
+/* Which kernel inflated the blocks of the LAST mlst_selftest_inflate_device call (tests/test_inflate_streams.py; no data path reads
+ * or writes what this returns).  *n_blocks: the BGZF blocks with data of that call; *left_to_wave: how many of them phase 1 of the
+ * two-kernel inflate (k_inflate_tok / k_inflate_tok2) left to k_inflate -- the TOK_OVERFLOW entries of its token-count array;
+ * 0 with MLST_INFLATE_MODE=1, where there is no phase 1.  MLST_E_INVALID before the first such call, after one that ended before
+ * its kernels were launched (bad framing, no block with data, an allocation that failed), and after one of more than 16,384
+ * blocks (more than one pass may have run: the array then holds the last pass only). */
+int mlst_debug_inflate_paths(mlst_handle* h, uint64_t* n_blocks, uint64_t* left_to_wave);
+
 /* Test hook of the CRC stage (csrc/bgzf_crc.h): whole BGZF blocks in; they are inflated as by the call above and the CRC-32 that
  * k_bgzf_crc computes of every block with data comes out, in file order, whatever the trailers say (nothing is compared).
  * cap: room in crc_out (values); *n_blocks: values written; kernel_ms (optional): the CRC kernel alone (HIP events). */

@@ -3656,6 +3656,7 @@ struct mlst_handle {
     // pileup scratch
     int* d_locus_chosen = nullptr; u64* d_locus_colbase = nullptr; u64* d_pl_list = nullptr; u8* d_tb = nullptr;
     u32* d_itok = nullptr; u32* d_intok = nullptr; u64 cap_itok_blocks = 0; int inflate_mode = 0;      // two-kernel inflate: token buffer (INFL_TOK_CAP words per block of a pass), tokens per block
+    u64 dbg_infl_blocks = 0, dbg_infl_left = 0; bool dbg_infl_known = false;      // mlst_debug_inflate_paths: the last mlst_selftest_inflate_device call
     // BGZF input in three stages on three streams (mlst_submit_fastq_bgzf, round 5): the copy of piece k (copy_stream), the inflate
     // of piece k (infl_stream) and the parse + pass 1 of piece k - 1 (the engine's stream) run side by side.  Two slots of
     // compressed bytes / block descriptors / error words used in turn; `bz_pend` is the piece whose text is being inflated
@@ -5594,6 +5595,7 @@ extern "C" int mlst_submit_fastq_bgzf_pair(mlst_handle* h, const uint8_t* data1,
 extern "C" int mlst_selftest_inflate_device(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, uint8_t* out, uint64_t cap, uint64_t* produced, double* kernel_ms) {
     if (!h) return MLST_E_INVALID;
     if (produced) *produced = 0;
+    h->dbg_infl_known = false;      // (mlst_debug_inflate_paths reports on THIS call, or on none if it ends before its launch)
     if (!data || !out) return fail(h, MLST_E_INVALID, "NULL argument");
     hipSetDevice(h->device);
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
@@ -5624,6 +5626,7 @@ extern "C" int mlst_selftest_inflate_device(mlst_handle* h, const uint8_t* data,
         hipEvent_t e0 = ev_get(h), e1 = ev_get(h);
         hipEventRecord(e0, h->stream);
         rc = launch_inflate(h, d_in, (u64)n_bytes + 16, (const BgzfBlk*)d_blk, (u32)blks.size(), d_out, d_err, d_st);
+        const bool launched = rc == MLST_OK;
         hipEventRecord(e1, h->stream);
         hipError_t se = hipStreamSynchronize(h->stream);
         float ms = 0; if (se == hipSuccess) hipEventElapsedTime(&ms, e0, e1);
@@ -5632,6 +5635,16 @@ extern "C" int mlst_selftest_inflate_device(mlst_handle* h, const uint8_t* data,
         if (se != hipSuccess || hipMemcpy(err, d_err, 16, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out, d_out, text_bytes, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(h, MLST_E_HIP, "k_inflate failed: %s", hipGetErrorString(hipGetLastError()));
         else if (err[0]) rc = bz_fail(h, err, err[0] - 1, "");
+        // (mlst_debug_inflate_paths: what phase 1 left to k_inflate, read from its token counts after the fact)
+        h->dbg_infl_blocks = blks.size(); h->dbg_infl_left = 0;
+        if (launched && se == hipSuccess && (h->inflate_mode == 1 || d_st)) h->dbg_infl_known = true;
+        else if (launched && se == hipSuccess && blks.size() <= h->cap_itok_blocks && blks.size() <= INFL_PASS) {      // (one pass of either phase 1; k_inflate_tok2 would take more in one, not needed here)
+            std::vector<u32> nt(blks.size());
+            if (hipMemcpy(nt.data(), h->d_intok, blks.size() * sizeof(u32), hipMemcpyDeviceToHost) == hipSuccess) {
+                for (u32 v : nt) h->dbg_infl_left += v == (u32)inflate_lane::TOK_OVERFLOW;
+                h->dbg_infl_known = true;
+            }
+        }
 #if defined(MLST_PTR_TRACE)
         { u32 tr[8] = {0}; if (hipMemcpy(tr, d_err, 32, hipMemcpyDeviceToHost) == hipSuccess)
             fprintf(stderr, "k_inflate_ptr phases over %zu blocks (units of 64 cycles): fill %u, pointer jumping %u (%u rounds), gather %u\n", blks.size(), tr[2], tr[3], tr[5], tr[4]); }
@@ -5645,6 +5658,15 @@ extern "C" int mlst_selftest_inflate_device(mlst_handle* h, const uint8_t* data,
     }
     hipFree(d_in); hipFree(d_out); hipFree(d_blk); hipFree(d_err); hipFree(d_st);
     return rc;
+}
+
+// which kernel inflated the blocks of the last mlst_selftest_inflate_device call: a test hook (include/mlst_debug.h)
+extern "C" int mlst_debug_inflate_paths(mlst_handle* h, uint64_t* n_blocks, uint64_t* left_to_wave) {
+    if (!h) return MLST_E_INVALID;
+    if (!n_blocks || !left_to_wave) return fail(h, MLST_E_INVALID, "NULL argument");
+    if (!h->dbg_infl_known) return fail(h, MLST_E_INVALID, "no mlst_selftest_inflate_device call of a single pass to report on");
+    *n_blocks = h->dbg_infl_blocks; *left_to_wave = h->dbg_infl_left;
+    return MLST_OK;
 }
 
 // the CRC-32 of every block with data as k_bgzf_crc computes it behind the decoders (whatever the trailers say): test hook

@@ -130,6 +130,7 @@ def load_library(path: str | None = None):
         "mlst_debug_bgzf_walk": (C.c_int, [u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
         "mlst_selftest_inflate_device": (C.c_int, [H, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
         "mlst_selftest_bgzf_crc": (C.c_int, [H, u8p, C.c_uint64, u32p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+        "mlst_debug_inflate_paths": (C.c_int, [H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mlst_set_bgzf_verify": (C.c_int, [H, C.c_int]),
         "mlst_get_bgzf_verify": (C.c_int, [H, C.POINTER(C.c_int)]),
         "mlst_submit_reads_device": (C.c_int, [H, u8p, u8p, u64p, C.c_uint64, C.c_uint32, C.c_int]),
@@ -521,11 +522,29 @@ class Engine:
     def inflate_bgzf(self, data) -> bytes:
         """Test hook: whole BGZF blocks -> their text, inflated by the device kernel."""
         buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
-        out = np.empty(max(1, (buf.size // 18 + 1) * 65536), np.uint8)
+        room, off = 0, 0                             # the blocks' ISIZE fields added up; anything odd: the format's bound (the library checks)
+        while off + 18 <= buf.size:
+            size = int(buf[off + 16]) + (int(buf[off + 17]) << 8) + 1
+            plain = buf[off:off + 16].tobytes() == b"\x1f\x8b\x08\x04" + buf[off + 4:off + 10].tobytes() + b"\x06\x00BC\x02\x00"      # (XLEN = 6: the BC subfield alone)
+            if not plain or size < 26 or off + size > buf.size:
+                room = (buf.size // 18 + 1) * 65536
+                break
+            room += min(int.from_bytes(buf[off + size - 4:off + size].tobytes(), "little"), 65536)
+            off += size
+        if off != buf.size:
+            room = (buf.size // 18 + 1) * 65536
+        out = np.empty(max(1, room), np.uint8)
         n, ms = C.c_uint64(), C.c_double()
         self._check(self.lib.mlst_selftest_inflate_device(self._h, _ptr(buf), buf.size, _ptr(out), out.size, C.byref(n), C.byref(ms)), "mlst_selftest_inflate_device")
         self.last_inflate_ms = float(ms.value)
         return out[:int(n.value)].tobytes()
+
+    def inflate_paths(self):
+        """Test hook (mlst_debug_inflate_paths): (BGZF blocks with data of the last inflate_bgzf call, how many of them phase 1 of
+        the two-kernel inflate left to k_inflate)."""
+        n, left = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mlst_debug_inflate_paths(self._h, C.byref(n), C.byref(left)), "mlst_debug_inflate_paths")
+        return int(n.value), int(left.value)
 
     def bgzf_block_crcs(self, data) -> np.ndarray:
         """Test hook: whole BGZF blocks -> the CRC-32 the device computes of every block with data (uint32, file order), whatever
