@@ -317,6 +317,42 @@ int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, 
 int mlst_bam_set_capacity(mlst_handle* h, uint64_t max_entries);
 int mlst_bam_pileup_fetch(mlst_handle* h, uint32_t* counts);
 
+/* ---- the READS of a BGZF BAM (unaligned BAMs, the unmapped remainder of a host depletion, a BAM aligned to something else) -----
+ * The records are taken as reads the way `samtools fastq` takes them with its defaults, chosen, strand-corrected and packed on the
+ * GPU (csrc/bam_reads.h) and typed like the reads of a FASTQ file; their alignments are ignored.  Replaces the `samtools fastq`
+ * run in front of the user-run bowtie2 [NOT IN TREE].  Records count in file order:
+ *   - FLAG 0x100 (secondary) or 0x800 (supplementary): not a read; skipped and counted.
+ *   - l_seq == 0: skipped and counted.  (A deviation: samtools writes an empty record; the FASTQ parser has no statement on
+ *     empty reads.)  A record that is both counts as secondary / supplementary.
+ *   - FLAG 0x10: the record is stored on the reference strand; the read is its reverse complement, its Phred values reversed.
+ *   - base nibbles 1 2 4 8 are A C G T; every other nibble (N, IUPAC, =) is a non-ACGT base: packed as A, bit 7 in its qrows
+ *     byte, bit 15 of lens -- what an N of FASTQ text gets.  The filler nibble of an odd l_seq is no base.  The complement swaps
+ *     1 <-> 8 and 2 <-> 4; anything else stays non-ACGT.
+ *   - Phred: the raw byte clamped to 0..127 (what the text path makes of chr(q + 33)).  A first quality byte of 0xFF means no
+ *     qualities: every base gets Phred 1 (the default of samtools fastq -v).
+ *   - l_seq > 320 (MLST_MAX_READ_LEN): MLST_E_LIMIT "a BAM read is longer than 320 bases"; the stream ends.
+ *   - the read index is the number of reads kept before it: locus_first_read and mlst_set_read_index_base as after FASTQ.
+ *   - ref_id, pos, CIGAR and the optional fields are stepped over.
+ * mlst_bam_reads_open: n_ref = the header's reference count (0 for an unaligned BAM; it bounds the ref_id of a plausible record
+ *   head, nothing else), skip_bytes as for mlst_bam_open.  Refuses while another stream is open; while it is open the other
+ *   entries refuse as for mlst_bam_open.  The data follows through mlst_submit_bam_bgzf, unchanged in form (whole blocks,
+ *   n_consumed_out, final_chunk, n_records_out = records completed by the call, CRC verification, MLST_BGZF_PIPE=0): a call copies
+ *   and inflates its piece; the piece is split, its reads chosen, packed and submitted to pass 1 when it is finished -- by the next
+ *   call on the handle or by any entry that looks at the sample's state (one host synchronisation per piece: the pack buffers are
+ *   sized by its read count and longest read).
+ *   paired != 0: the reads kept must come as neighbours -- kept reads 2k and 2k + 1 carry byte-identical QNAMEs and FLAG 0x1 both
+ *   -- and are submitted as pairs (one QNAME per pair for sequenceBank, metamlst.py:127, Q3, as mlst_submit_fastq_pair); skipped
+ *   records may stand between and behind them.  A kept read whose neighbour has another name, one without 0x1, or an odd number of
+ *   kept reads at the end of the file: MLST_E_INVALID "record <n> has no mate next to it (a paired BAM must be collated by name)"
+ *   (n counts all records of the file from 0).  Every submission holds whole pairs: a piece that ends on an odd number of kept
+ *   reads hands its last kept record (and what follows it) on to the next piece; if that does not fit the 1 MiB head room:
+ *   MLST_E_LIMIT, as for an oversized record.
+ * mlst_bam_reads_info: of the reads stream just finished or still open (a piece in flight is finished first): [0] reads
+ *   submitted, [1] records skipped as secondary / supplementary, [2] records skipped as empty, [3] cells the record split walked
+ *   again (mlst_debug_bam_split). */
+int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip_bytes, int paired);
+int mlst_bam_reads_info(mlst_handle* h, uint64_t out[4]);
+
 /* ---- whole typing tail on the device, without a host round trip between the passes ----------------------
  * mlst_typing_enqueue queues, behind the pass-1 work already submitted on the engine's stream:
  *   the allele choice of metamlst.py:133-151 + :244 (per locus the allele with the highest

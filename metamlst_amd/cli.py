@@ -1,6 +1,7 @@
 """Command-line entry points with the reference's flags.
 
     python -m metamlst_amd.cli type  SAMPLE.fastq[.gz] [-2 MATES.fastq] -d DB [-o out] [--penalty ...]   (metamlst.py:34-49)
+    python -m metamlst_amd.cli type  READS.bam -d DB [-o out]            (the reads of a BAM, as `samtools fastq` takes them)
     python -m metamlst_amd.cli merge FOLDER -d DB [-z 5] [--filter ...] [--meta ...] [--idField ...]       (metamlst-merge.py:35-49)
     python -m metamlst_amd.cli index -d DB [-s seqs.fasta,...] [-t typings.txt,...] [-q dump.fa] [--list]   (metamlst-index.py:24-33)
 
@@ -26,7 +27,9 @@ from .typing import TypingArgs, log_table, sample_name, type_sample
 def _type_parser(sub):
     p = sub.add_parser("type", help="reconstruct the MLST loci of one sample from its reads (counterpart of metamlst.py)")
     p.add_argument("READS", nargs="+",
-                   help="FASTQ file (plain, .gz or bgzip; `a.fq,b.fq` = two files of one sample, as bowtie2 -U takes them); with "
+                   help="FASTQ file (plain, .gz or bgzip; `a.fq,b.fq` = two files of one sample, as bowtie2 -U takes them), or a BAM "
+                        "whose records are taken as reads the way `samtools fastq` takes them (unaligned BAMs, `samtools view -f 4`; "
+                        "a name-collated paired BAM is typed as pairs); with "
                         "--alignments: a SAM (plain or .gz) or BAM file.  Several files, or a folder of FASTQ files: every one is a "
                         "sample of its own, typed one after the other (with --gpus N: whole samples dealt to the GPUs, rank 0 "
                         "gathers the .nfo lines) -- the many-samples-into-one-folder use that metamlst-merge.py reads")
@@ -146,8 +149,12 @@ def run_type(a, argv=None) -> int:
         return 1
     a.READS, extra_files = samples[0][0], samples[0][1:]
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    has_bam = not a.alignments and not a.contigs and any(_is_reads_bam(f) for smp in samples for f in smp)
+    if has_bam and a.mates:
+        print("-2 names the second FASTQ file of a pair: the mates of a BAM are records of the BAM itself (collate it by name)")
+        return 1
     if a.gpus > 1 and world == 1:
-        if a.alignments or a.contigs:
+        if a.alignments or a.contigs or has_bam:
             print("--gpus applies to FASTQ input")
             return 1
         from .multigpu import launch_ranks
@@ -256,7 +263,7 @@ def run_type(a, argv=None) -> int:
         return 0
     # FASTQ text goes to the GPU as is and is parsed there (mlst_submit_fastq); a reader thread stays two chunks ahead
     try:
-        submit_sample_files(eng, paths, paired, chunk_bytes)
+        submit_sample_files(eng, paths, paired, chunk_bytes, report=None if a.quiet else print)
     except CorruptInput as e:      # nothing of the sample is typed: no .nfo
         print(e, file=sys.stderr)
         database.closeConnection()
@@ -295,8 +302,27 @@ def open_sample_reader(paths, paired: bool, chunk_bytes: int):
     return _FileReader(paths[0], chunk_bytes)
 
 
-def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader=None) -> None:
-    """All reads of one sample's FASTQ file(s) into one engine (first_reader: open_sample_reader(paths, ...), if opened ahead)."""
+def _is_reads_bam(path: str) -> bool:
+    from .samin import is_bgzf_bam
+    return os.path.isfile(path) and is_bgzf_bam(path)
+
+
+def submit_bam_reads(eng, path: str, report=None) -> int:
+    """The reads of a BGZF BAM into one engine (Engine.submit_bam_reads_file): as pairs iff the first record kept carries FLAG 0x1
+    (decided on the first record, as mates_share_names does for mate files).  report: called with one line on what was taken."""
+    from .samin import bam_first_read_flags
+    flags = bam_first_read_flags(path)
+    paired = bool(flags is not None and flags & 1)
+    n = crc_checked([path], lambda: eng.submit_bam_reads_file(path, paired=paired))
+    if report is not None:
+        _, n_sec, n_empty, _ = eng.bam_reads_info()
+        report("%s: %d reads taken%s, %d secondary / supplementary and %d empty records skipped" % (path, n, " as pairs" if paired else "", n_sec, n_empty))
+    return n
+
+
+def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader=None, report=None) -> None:
+    """All reads of one sample's file(s) into one engine: FASTQ (first_reader: open_sample_reader(paths, ...), if opened ahead), or
+    BAMs whose records are taken as reads (report: see submit_bam_reads)."""
     if paired and is_bgzf(paths[0]) and is_bgzf(paths[1]):      # bgzip'd mates: inflated and paired on the GPU
         crc_checked(paths, lambda: eng.submit_fastq_bgzf_pair_files(paths[0], paths[1]))
         return
@@ -308,6 +334,9 @@ def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader
         release_buffers(ring)
         return
     for k, path in enumerate(paths):
+        if _is_reads_bam(path):      # a BAM that holds reads: inflated, chosen, strand-corrected and packed on the GPU
+            submit_bam_reads(eng, path, report)
+            continue
         if is_bgzf(path):      # bgzip'd FASTQ: the compressed blocks go to the GPU and are inflated there
             crc_checked([path], lambda: eng.submit_fastq_bgzf_file(path, paired=False))
             continue

@@ -3603,6 +3603,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 }
 
 #include "bam_dev.h"
+#include "bam_reads.h"
 
 // ================================================================== host side
 struct EvPair { hipEvent_t a, b; int which; };
@@ -3711,6 +3712,7 @@ struct mlst_handle {
     double wall_khz = 100000.0;                  // wall_clock64 rate (hipDeviceAttributeWallClockRate)
     struct BamStream* bam = nullptr;             // BAM input (mlst_bam_open / mlst_submit_bam_bgzf), allocated by the first stream
     u32 bam_force_miss = 0; u64 bam_max_entries = 0;      // mlst_debug_bam_split, mlst_bam_set_capacity
+    struct { u64 n_reads = 0; u32 wpr = 0, qstride = 0; } last_pack;      // mlst_debug_last_packed: what d_packed / d_qrows / d_lens hold (text and BAM reads)
 };
 
 static std::string g_create_err;
@@ -3897,6 +3899,7 @@ static int reset_sample_state(mlst_handle* h) {
     HIPCHK(h, hipMemsetAsync(h->d_stats + h->off_first, 0xFF, h->stats_bytes - h->off_first, h->stream));
     if (h->d_acc64 && h->n_alleles) HIPCHK(h, hipMemsetAsync(h->d_acc64, 0, (u64)h->n_alleles * 8, h->stream));      // (zero after every complete submission already: k_accumulate; this is for one that was cut short)
     h->reads_seen = 0; h->fq_carry_len = 0; h->max_wpr = 0;
+    h->last_pack.n_reads = 0; h->last_pack.wpr = h->last_pack.qstride = 0;
     h->pc_len[0] = h->pc_len[1] = 0; h->pair_open = false;      // (mlst_submit_fastq_bgzf_pair: both files' carries)
     bam_drop(h, false);
     return MLST_OK;
@@ -4616,6 +4619,7 @@ static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* 
 }
 
 static int ensure_pack_buffers(mlst_handle* h, u64 n_reads, u32 wpr, u32 qstride) {
+    h->last_pack.n_reads = 0; h->last_pack.wpr = h->last_pack.qstride = 0;      // (every writer of the pack buffers passes here; the text and BAM packers say what they wrote afterwards)
     if (h->cap_packed_words < packed_words(n_reads, wpr) + 4 || h->cap_qrow_bytes < n_reads * qstride || h->cap_lens < n_reads + 2) {
         hipStreamSynchronize(h->stream);
         hipFree(h->d_packed); hipFree(h->d_qrows); hipFree(h->d_lens); h->d_packed = nullptr; h->d_qrows = nullptr; h->d_lens = nullptr;
@@ -4784,6 +4788,7 @@ static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, i
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
     if (n_reads_out) *n_reads_out = n_reads;
+    h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
     return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired);
 }
 
@@ -4870,6 +4875,7 @@ extern "C" int mlst_submit_packed_host(mlst_handle* h, const uint32_t* packed, c
     if (qstride < 4 || qstride > RQ || (qstride & 3)) return fail(h, MLST_E_INVALID, "qual_stride must be a multiple of 4 in 4..%d", RQ);
     if (n_reads == 0) return MLST_OK;
     // bases + lengths cross the link; the quality buffer on the device only ever holds candidates' rows
+    h->last_pack.n_reads = 0; h->last_pack.wpr = h->last_pack.qstride = 0;      // (d_packed holds the caller's rows from here on, d_qrows none)
     if (h->cap_packed_words < packed_words(n_reads, wpr) + 4 || h->cap_lens < n_reads + 2) {
         hipStreamSynchronize(h->stream);
         hipFree(h->d_packed); hipFree(h->d_lens); h->d_packed = nullptr; h->d_lens = nullptr;
@@ -5721,8 +5727,10 @@ extern "C" int mlst_selftest_bgzf_crc(mlst_handle* h, const uint8_t* data, uint6
 struct BamSlot {
     u8* d_comp = nullptr; u64 cap_comp = 0; BgzfBlk* d_blk = nullptr; BgzfBlk* h_blk = nullptr; u64 cap_blk = 0;
     u8* d_text = nullptr; u64 cap_text = 0; u32* d_cells = nullptr; u32* d_list = nullptr; u64 cap_cells = 0;
-    u32* d_err = nullptr; u8* h_res = nullptr;      // h_res (pinned): 4 error words of the inflate, then the BamMeta after the piece
+    u32* d_err = nullptr; u8* h_res = nullptr;      // h_res (pinned): 4 error words of the inflate, then the BamMeta after the piece (a reads stream: and its BamReadsMeta)
     hipEvent_t ev_copied = nullptr, ev_done = nullptr;
+    // a reads stream: the piece's text has been inflated / its reads have been packed (the slot is free again); what its finish needs to know
+    hipEvent_t ev_inflated = nullptr, ev_free = nullptr; u32* d_rd = nullptr; u64 cap_rd = 0; u32 text_end = 0, n_cells = 0; bool final_piece = false, first_piece = false;
     u64 bound = 0;      // pass 1: most list entries the piece in this slot can add (a record per 37 bytes), counted in BamStream::bound_pend while it is in flight
 };
 struct BamStream {
@@ -5732,6 +5740,7 @@ struct BamStream {
     BamEntry* d_entries = nullptr; u64 cap_entries = 0, entries_done = 0, bound_pend = 0; u32 last_carry = 0;
     int* d_allele_slot = nullptr; u64 cap_slot = 0; u32* d_counts = nullptr; u64 cap_counts = 0, n_cols = 0; bool counts_ready = false;
     u64 rewalked = 0;
+    bool reads = false; int paired = 0; BamReadsMeta* d_rmeta = nullptr; u64 reads_done = 0, n_secondary = 0, n_empty = 0;      // mlst_bam_reads_open
     u64* d_sort_k[2] = {nullptr, nullptr}; u32* d_sort_v[2] = {nullptr, nullptr}; void* d_sort_tmp = nullptr; u64 cap_sort = 0, cap_sort_tmp = 0;      // bam_bank's buffers, kept between streams
 };
 static_assert(MLST_BAM_MAX_RECORD == BAM_REC_MAX, "mlst_policy.h and csrc/bam_dev.h state the largest BAM record differently");
@@ -5740,15 +5749,16 @@ static bool bam_is_open(const mlst_handle* h) { return h->bam && h->bam->open; }
 static void bam_drop(mlst_handle* h, bool release) {
     BamStream* B = h->bam;
     if (!B) return;
-    if (B->pend || B->open) { if (h->copy_stream) hipStreamSynchronize(h->copy_stream); if (h->stream) hipStreamSynchronize(h->stream); }
+    if (B->pend || B->open) { if (h->copy_stream) hipStreamSynchronize(h->copy_stream); if (h->infl_stream) hipStreamSynchronize(h->infl_stream); if (h->stream) hipStreamSynchronize(h->stream); }
     B->open = false; B->pend = false; B->counts_ready = false;
     if (!release) return;
     for (auto& S : B->s) {
         hipFree(S.d_comp); hipFree(S.d_blk); if (S.h_blk) hipHostFree(S.h_blk); hipFree(S.d_text); hipFree(S.d_cells); hipFree(S.d_list); hipFree(S.d_err);
         if (S.h_res) hipHostFree(S.h_res); if (S.ev_copied) hipEventDestroy(S.ev_copied); if (S.ev_done) hipEventDestroy(S.ev_done);
+        hipFree(S.d_rd); if (S.ev_inflated) hipEventDestroy(S.ev_inflated); if (S.ev_free) hipEventDestroy(S.ev_free);
     }
     hipFree(B->d_ref_allele); hipFree(B->d_ref_locus); hipFree(B->d_ref_flags); hipFree(B->d_carry); hipFree(B->d_meta); hipFree(B->d_entries);
-    hipFree(B->d_allele_slot); hipFree(B->d_counts);
+    hipFree(B->d_allele_slot); hipFree(B->d_counts); hipFree(B->d_rmeta);
     for (int k = 0; k < 2; k++) { hipFree(B->d_sort_k[k]); hipFree(B->d_sort_v[k]); } hipFree(B->d_sort_tmp);
     delete B; h->bam = nullptr;
 }
@@ -5764,9 +5774,11 @@ static const char* bam_reason(u32 r) {
     }
 }
 // the piece in flight: wait for it, report what it met.  whole: the file ends with it.
+static int bamr_finish(mlst_handle* h, uint64_t* n_records_out);
 static int bam_finish(mlst_handle* h, uint64_t* n_records_out) {
     BamStream* B = h->bam;
     if (!B || !B->pend) return MLST_OK;
+    if (B->reads) return bamr_finish(h, n_records_out);
     B->pend = false;
     BamSlot& S = B->s[B->cur];
     HIPCHK(h, hipEventSynchronize(S.ev_done));
@@ -5838,7 +5850,7 @@ extern "C" int mlst_bam_open(mlst_handle* h, int pass, const int32_t* ref_allele
         B->n_cols = cols;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (the tables came from the caller's pageable memory)
-    B->open = true; B->pend = false; B->first = true; B->pass = pass; B->n_ref = n_ref; B->skip = skip_bytes;
+    B->open = true; B->pend = false; B->first = true; B->pass = pass; B->n_ref = n_ref; B->skip = skip_bytes; B->reads = false;
     B->entries_done = B->bound_pend = 0; B->s[0].bound = B->s[1].bound = 0; B->last_carry = 0;
     return MLST_OK;
 }
@@ -5900,19 +5912,26 @@ extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_
     if (text_bytes >= (1ull << 31) - (1ull << 21)) { bam_drop(h, false); return fail(h, MLST_E_LIMIT, "BGZF chunk inflates to more than 2 GiB"); }
     if (n_consumed_out) *n_consumed_out = n_bytes;
     uint64_t done = 0;
-    if (blks.empty()) {
+    bool no_piece = blks.empty();
+    if (no_piece) {
         { int rc = bam_finish(h, &done); if (rc) return rc; }
         if (n_records_out) *n_records_out = done;
         if (!final_chunk) return MLST_OK;
-        if (B->last_carry || B->first) { const bool never = B->first; bam_drop(h, false); return fail(h, MLST_E_INVALID, never ? "truncated BAM: no records block" : "truncated BAM: the file ends inside a record"); }
-    } else {
+        // (a paired reads stream may hold a whole kept record in its carry: a piece without blocks says what is wrong with it)
+        if (B->reads && B->paired && B->last_carry && !B->first) no_piece = false;
+        else if (B->last_carry || B->first) { const bool never = B->first; bam_drop(h, false); return fail(h, MLST_E_INVALID, never ? "truncated BAM: no records block" : "truncated BAM: the file ends inside a record"); }
+    }
+    if (!no_piece) {
         // (slot `cur` holds the piece in flight; this piece takes the other one, whose last user was finished by the call before)
         const int sl = B->pend ? (B->cur ^ 1) : B->cur;
         BamSlot& S = B->s[sl];
         if (!S.ev_done) {
             HIPCHK(h, hipEventCreateWithFlags(&S.ev_copied, hipEventDisableTiming)); HIPCHK(h, hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming));
-            HIPCHK(h, dmalloc(&S.d_err, (u64)16)); HIPCHK(h, hipHostMalloc((void**)&S.h_res, 16 + sizeof(BamMeta), hipHostMallocDefault));
+            HIPCHK(h, dmalloc(&S.d_err, (u64)16)); HIPCHK(h, hipHostMalloc((void**)&S.h_res, 16 + sizeof(BamMeta) + sizeof(BamReadsMeta), hipHostMallocDefault));
+            HIPCHK(h, hipEventCreateWithFlags(&S.ev_inflated, hipEventDisableTiming)); HIPCHK(h, hipEventCreateWithFlags(&S.ev_free, hipEventDisableTiming));
         }
+        // (a reads stream: the slot's last piece was finished by the host, but its kernels may still read the slot's buffers)
+        if (B->reads) HIPCHK(h, hipEventSynchronize(S.ev_free));
         if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
         const u32 n_cells = (u32)((text_bytes + BAM_CELL - 1) / BAM_CELL);
         if (S.cap_comp < n_bytes) { hipFree(S.d_comp); S.d_comp = nullptr; S.cap_comp = 0; HIPCHK(h, dmalloc(&S.d_comp, n_bytes + n_bytes / 8 + 32)); S.cap_comp = n_bytes + n_bytes / 8; }
@@ -5925,9 +5944,13 @@ extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_
         if (S.cap_cells < n_cells) {
             hipFree(S.d_cells); hipFree(S.d_list); S.d_cells = S.d_list = nullptr; S.cap_cells = 0;
             const u64 cap = (u64)n_cells + n_cells / 8 + 8;
-            HIPCHK(h, dmalloc(&S.d_cells, cap * 4)); HIPCHK(h, dmalloc(&S.d_list, cap * BAM_CELL_CAP)); S.cap_cells = cap;
+            HIPCHK(h, dmalloc(&S.d_cells, cap * 6)); HIPCHK(h, dmalloc(&S.d_list, cap * BAM_CELL_CAP)); S.cap_cells = cap;      // first, exit, count, base; a reads stream: kept, kbase
         }
-        if (B->pass == 1) {      // the list grows with the file: what the finished pieces filled, plus at most a record per 37 bytes of the pieces in flight
+        if (B->reads && S.cap_rd < S.cap_cells) {      // record start, info and record index of every kept record: a record per cell entry at most
+            hipFree(S.d_rd); S.d_rd = nullptr; S.cap_rd = 0;
+            HIPCHK(h, dmalloc(&S.d_rd, S.cap_cells * BAM_CELL_CAP * 3)); S.cap_rd = S.cap_cells;
+        }
+        if (B->pass == 1 && !B->reads) {      // the list grows with the file: what the finished pieces filled, plus at most a record per 37 bytes of the pieces in flight
             const u64 bound = (text_bytes - BAM_HEAD + B->last_carry + BAM_HEAD) / 37 + 1, cap_max = h->bam_max_entries ? h->bam_max_entries : BAM_DEFAULT_ENTRIES;
             const u64 need = std::min(cap_max, B->entries_done + B->bound_pend + bound);
             if (B->cap_entries < need) {
@@ -5939,10 +5962,29 @@ extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_
             }
             B->bound_pend += bound; S.bound = bound;
         }
-        memcpy(S.h_blk, blks.data(), blks.size() * sizeof(BgzfBlk));
-        HIPCHK(h, hipMemcpyAsync(S.d_comp, data, n_bytes, hipMemcpyHostToDevice, h->copy_stream));
+        if (!blks.empty()) memcpy(S.h_blk, blks.data(), blks.size() * sizeof(BgzfBlk));      // (no blocks: the closing piece of a paired reads stream)
+        if (n_bytes) HIPCHK(h, hipMemcpyAsync(S.d_comp, data, n_bytes, hipMemcpyHostToDevice, h->copy_stream));
         HIPCHK(h, hipEventRecord(S.ev_copied, h->copy_stream));
         struct CopyGuard { mlst_handle* h; ~CopyGuard() { hipStreamSynchronize(h->copy_stream); } } copy_guard{h};      // `data` is the caller's again on return
+        if (B->reads) {      // the call queues the copy and the inflate of its piece; the rest is bamr_finish's
+            { int rc = bz_stream(h); if (rc) return rc; }
+            hipStream_t si = h->infl_stream;
+            if (!blks.empty()) HIPCHK(h, hipMemcpyAsync(S.d_blk, S.h_blk, blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice, si));
+            HIPCHK(h, hipMemsetAsync(S.d_err, 0, 64, si));
+            HIPCHK(h, hipStreamWaitEvent(si, S.ev_copied, 0));
+            { int rc = launch_inflate(h, S.d_comp, S.cap_comp + 16, S.d_blk, (u32)blks.size(), S.d_text, S.d_err, nullptr, si); if (rc) { bam_drop(h, false); return rc; } }
+            HIPCHK(h, hipMemcpyAsync(S.h_res, S.d_err, 16, hipMemcpyDeviceToHost, si));
+            HIPCHK(h, hipEventRecord(S.ev_inflated, si));
+            if (hipGetLastError() != hipSuccess) { bam_drop(h, false); return fail(h, MLST_E_HIP, "a BAM kernel could not be launched"); }
+            S.text_end = (u32)text_bytes; S.n_cells = n_cells; S.final_piece = final_chunk != 0; S.first_piece = B->first;
+            if (B->pend) { const int rc = bam_finish(h, &done); if (rc) return rc; }      // the piece before, while the GPU inflates this one
+            B->cur = sl; B->pend = true; B->first = false;
+            if (final_chunk || !piped) { const int rc = bam_finish(h, &done); if (rc) return rc; }
+            if (n_records_out) *n_records_out = done;
+            if (!final_chunk) return MLST_OK;
+            B->open = false;
+            return MLST_OK;
+        }
         hipStream_t st = h->stream;
         HIPCHK(h, hipMemcpyAsync(S.d_blk, S.h_blk, blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice, st));
         HIPCHK(h, hipMemsetAsync(S.d_err, 0, 64, st));
@@ -5976,9 +6018,128 @@ extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_
     }
     // the stream ends here
     int rc = MLST_OK;
-    if (B->pass == 1) rc = bam_bank(h); else B->counts_ready = true;
+    if (B->reads) {}
+    else if (B->pass == 1) rc = bam_bank(h); else B->counts_ready = true;
     B->open = false;
     return rc;
+}
+
+// ---- the reads of a BAM (mlst_bam_reads_open; kernels: csrc/bam_reads.h).  A piece is copied and inflated by its call (copy stream,
+// inflate stream) and finished here, on the engine's stream, by the next call on the handle (or bam_flush): record split as for
+// alignments, then the records that are reads are chosen and numbered, mates checked, and -- after the one host synchronisation
+// that sizes the pack buffers (read count, longest read), as fastq_pipeline has for its line count -- packed and submitted to pass 1.
+static int bamr_finish(mlst_handle* h, uint64_t* n_records_out) {
+    BamStream* B = h->bam;
+    B->pend = false;
+    BamSlot& S = B->s[B->cur];
+    hipStream_t st = h->stream;
+    const u32 n_cells = S.n_cells, text_end = S.text_end;
+    u32* d_first = S.d_cells; u32* d_exit = d_first + S.cap_cells; u32* d_count = d_exit + S.cap_cells; u32* d_base = d_count + S.cap_cells;
+    u32* d_kept = d_base + S.cap_cells; u32* d_kbase = d_kept + S.cap_cells;
+    u32* rd_rec = S.d_rd; u32* rd_info = rd_rec + S.cap_rd * BAM_CELL_CAP; u32* rd_ridx = rd_info + S.cap_rd * BAM_CELL_CAP;
+    HIPCHK(h, hipStreamWaitEvent(st, S.ev_inflated, 0));
+    hipLaunchKernelGGL(k_bam_carry_in, dim3(64), dim3(256), 0, st, S.d_text, (const u8*)B->d_carry, B->d_meta, S.first_piece ? B->skip : 0u);
+    hipLaunchKernelGGL(k_bam_cells, dim3(std::min(n_cells, 16384u)), dim3(256), 0, st, (const u8*)S.d_text, text_end, n_cells, (int)B->n_ref, (const BamMeta*)B->d_meta,
+                       d_first, d_exit, d_count, S.d_list, h->bam_force_miss);
+    hipLaunchKernelGGL(k_bam_link, dim3(1), dim3(64), 0, st, (const u8*)S.d_text, text_end, n_cells, (int)B->n_ref, B->d_meta, (const u32*)S.d_err,
+                       (const u32*)d_first, (const u32*)d_exit, d_count, d_base, S.d_list, S.final_piece ? 1 : 0);
+    hipLaunchKernelGGL(k_bamr_count, dim3(std::min(n_cells, 8192u)), dim3(256), 0, st, (const u8*)S.d_text, n_cells, (const u32*)d_count, (const u32*)S.d_list, d_kept);
+    hipLaunchKernelGGL(k_bamr_scan, dim3(1), dim3(1024), 0, st, (const u8*)S.d_text, text_end, n_cells, B->d_meta, B->d_rmeta, (const u32*)d_count, (const u32*)d_base,
+                       (const u32*)S.d_list, (const u32*)d_kept, d_kbase, B->paired, S.final_piece ? 1 : 0);
+    hipLaunchKernelGGL(k_bamr_select, dim3(std::min(n_cells, 8192u)), dim3(256), 0, st, (const u8*)S.d_text, n_cells, (const BamMeta*)B->d_meta, B->d_rmeta, (const u32*)d_count,
+                       (const u32*)d_base, (const u32*)S.d_list, (const u32*)d_kbase, rd_rec, rd_info, rd_ridx, B->paired);
+    if (B->paired) hipLaunchKernelGGL(k_bamr_mates, dim3(1024), dim3(256), 0, st, (const u8*)S.d_text, (const BamMeta*)B->d_meta, B->d_rmeta, (const u32*)rd_rec, (const u32*)rd_ridx);
+    HIPCHK(h, hipMemcpyAsync(S.h_res + 16, B->d_meta, sizeof(BamMeta), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(S.h_res + 16 + sizeof(BamMeta), B->d_rmeta, sizeof(BamReadsMeta), hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_bam_carry_out, dim3(64), dim3(256), 0, st, (const u8*)S.d_text, B->d_carry, B->d_meta);
+    if (hipGetLastError() != hipSuccess) { bam_drop(h, false); return fail(h, MLST_E_HIP, "a BAM kernel could not be launched"); }
+    HIPCHK(h, hipStreamSynchronize(st));      // the one host synchronisation of a piece
+    const u32* e = (const u32*)S.h_res; BamMeta m; BamReadsMeta r; memcpy(&m, S.h_res + 16, sizeof m); memcpy(&r, S.h_res + 16 + sizeof m, sizeof r);
+    if (e[0]) { bam_drop(h, false); return bz_fail(h, e, e[0] - 1, " of the chunk"); }
+    if (m.err) {
+        bam_drop(h, false);
+        switch (m.err) {
+            case BAM_ERR_LIMIT: return fail(h, MLST_E_LIMIT, "a BAM record of more than %u bytes", (unsigned)BAM_REC_MAX);
+            case BAM_ERR_TRUNC: return fail(h, MLST_E_INVALID, "truncated BAM: the file ends inside a record (after record %llu)", (unsigned long long)(m.rec_total));
+            default: return fail(h, MLST_E_INVALID, "malformed BAM record behind record %llu", (unsigned long long)m.rec_total);
+        }
+    }
+    if (r.err_key != ~0ull) {
+        bam_drop(h, false);
+        if ((r.err_key & 15u) == BAMR_ERR_LONG) return fail(h, MLST_E_LIMIT, "a BAM read is longer than %d bases", MLST_MAX_READ_LEN);
+        return fail(h, MLST_E_INVALID, "record %llu has no mate next to it (a paired BAM must be collated by name)", (unsigned long long)(r.err_key >> 4));
+    }
+    B->last_carry = m.carry_len; B->rewalked = m.rewalked; B->n_secondary = r.n_secondary; B->n_empty = r.n_empty;
+    if (n_records_out) *n_records_out += m.n_rec;
+    const u64 n_reads = r.n_reads;
+    if (n_reads) {
+        u32 wpr = (r.max_len + 15) / 16; if (wpr < 2) wpr = 2; wpr = (wpr + 1) & ~1u;
+        u32 qstride = (r.max_len + 7) & ~7u; if (qstride < 8) qstride = 8;
+        { int rc = ensure_pack_buffers(h, n_reads, wpr, qstride); if (rc) { bam_drop(h, false); return rc; } }
+        hipLaunchKernelGGL(k_bamr_pack, dim3(grid_for((n_reads + 63) / 64, 1, 8192)), dim3(256), 0, st, (const u8*)S.d_text, (const u32*)rd_rec, (const u32*)rd_info, n_reads,
+                           h->d_packed, h->d_qrows, h->d_lens, wpr, qstride);
+        HIPCHK(h, hipGetLastError());
+        h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
+    }
+    HIPCHK(h, hipEventRecord(S.ev_free, st));      // the slot's buffers may be overwritten from here on
+    if (n_reads) {
+        const int rc = mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, (h->last_pack.wpr), h->last_pack.qstride, B->paired);
+        if (rc) { bam_drop(h, false); return rc; }
+        B->reads_done += n_reads;
+    }
+    return MLST_OK;
+}
+
+extern "C" int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip_bytes, int paired) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (n_ref >= 0x7FFFFFFFu || skip_bytes >= 65536u) return fail(h, MLST_E_INVALID, "bad argument");
+    paired = paired ? 1 : 0;
+    if (paired && (h->reads_seen & 1ull)) return fail(h, MLST_E_INVALID, "paired submissions hold whole pairs (reads 2k, 2k+1) and start at an even read index");
+    hipSetDevice(h->device);
+    if (!h->bam) h->bam = new BamStream();
+    BamStream* B = h->bam;
+    if (!B->d_carry) HIPCHK(h, dmalloc(&B->d_carry, (u64)BAM_HEAD));
+    if (!B->d_meta) HIPCHK(h, dmalloc(&B->d_meta, (u64)1));
+    if (!B->d_rmeta) HIPCHK(h, dmalloc(&B->d_rmeta, (u64)1));
+    BamMeta m; memset(&m, 0, sizeof m); m.flag_key = ~0ull;
+    BamReadsMeta r; memset(&r, 0, sizeof r); r.err_key = ~0ull;
+    HIPCHK(h, hipMemcpyAsync(B->d_meta, &m, sizeof m, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(B->d_rmeta, &r, sizeof r, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (m and r are this frame's)
+    B->counts_ready = false;
+    B->open = true; B->pend = false; B->first = true; B->pass = 1; B->n_ref = n_ref; B->skip = skip_bytes; B->reads = true; B->paired = paired;
+    B->entries_done = B->bound_pend = 0; B->s[0].bound = B->s[1].bound = 0; B->last_carry = 0;
+    B->reads_done = B->n_secondary = B->n_empty = 0; B->rewalked = 0;
+    return MLST_OK;
+}
+
+extern "C" int mlst_bam_reads_info(mlst_handle* h, uint64_t out[4]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    BamStream* B = h->bam;
+    if (!B || !B->reads) return fail(h, MLST_E_INVALID, "no BAM reads stream (mlst_bam_reads_open)");
+    out[0] = B->reads_done; out[1] = B->n_secondary; out[2] = B->n_empty; out[3] = B->rewalked;
+    return MLST_OK;
+}
+
+// test hook (include/mlst_debug.h): the pack buffers of the last submission made from FASTQ text or from the reads of a BAM
+extern "C" int mlst_debug_last_packed(mlst_handle* h, uint32_t* packed, uint64_t cap_words, uint8_t* qrows, uint64_t cap_q, uint16_t* lens, uint64_t cap_reads, uint64_t out[3]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    const u64 n = h->last_pack.n_reads; const u32 wpr = h->last_pack.wpr, qs = h->last_pack.qstride;
+    out[0] = n; out[1] = wpr; out[2] = qs;
+    if (!n) return MLST_OK;
+    if ((packed && cap_words < packed_words(n, wpr)) || (qrows && cap_q < n * qs) || (lens && cap_reads < n)) return fail(h, MLST_E_CAPACITY, "buffers too small for the last pack (%llu reads)", (unsigned long long)n);
+    hipSetDevice(h->device);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (packed) HIPCHK(h, hipMemcpyAsync(packed, h->d_packed, packed_words(n, wpr) * 4, hipMemcpyDeviceToHost, h->stream));
+    if (qrows) HIPCHK(h, hipMemcpyAsync(qrows, h->d_qrows, n * qs, hipMemcpyDeviceToHost, h->stream));
+    if (lens) HIPCHK(h, hipMemcpyAsync(lens, h->d_lens, n * 2, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLST_OK;
 }
 
 extern "C" int mlst_bam_pileup_fetch(mlst_handle* h, uint32_t* counts) {

@@ -190,6 +190,9 @@ def load_library(path: str | None = None):
         "mlst_bam_set_capacity": (C.c_int, [H, C.c_uint64]),
         "mlst_bam_pileup_fetch": (C.c_int, [H, u32p]),
         "mlst_debug_bam_split": (C.c_int, [H, C.c_uint32, C.POINTER(C.c_uint64)]),
+        "mlst_bam_reads_open": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_int]),
+        "mlst_bam_reads_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "mlst_debug_last_packed": (C.c_int, [H, u32p, C.c_uint64, u8p, C.c_uint64, u16p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "mlst_synchronize": (C.c_int, [H]),
     }
     tolerant = bool(os.environ.get("MLST_LIB_ALLOW_MISSING"))      # A/B runs against an older build (profiles/ab.sh)
@@ -446,6 +449,41 @@ class Engine:
             out[int(a)] = counts[at:at + L]
             at += L
         return out
+
+    # ---- BGZF BAM (its records taken as reads) ----
+    def bam_reads_open(self, n_ref: int, skip_bytes: int = 0, paired: bool = False) -> None:
+        """Open a reads stream (mlst_bam_reads_open); the data follows through submit_bam_bgzf."""
+        self._check(self.lib.mlst_bam_reads_open(self._h, int(n_ref), int(skip_bytes), int(paired)), "mlst_bam_reads_open")
+
+    def submit_bam_reads_file(self, path: str, paired: bool = False, chunk_bytes: int = 64 << 20) -> int:
+        """Pass 1 over the READS of a BGZF BAM (the rules of `samtools fastq`, include/mlst.h): inflated, chosen, strand-corrected
+        and packed on the device; returns the reads submitted (bam_reads_info() has the records skipped).  paired: the reads kept
+        come as neighbours with one QNAME and are submitted as pairs.  With set_bgzf_verify on, the blocks of the header are
+        checked on the host (fastq.BgzfCrcError), those of the records on the device."""
+        from .samin import read_bam_header
+        names, lo, skip = read_bam_header(path, self.bgzf_verify)      # (the header's blocks are the host's to check)
+        self.bam_reads_open(len(names), skip, paired)
+        self._bam_stream_file(path, lo, chunk_bytes)
+        return self.bam_reads_info()[0]
+
+    def bam_reads_info(self) -> tuple[int, int, int, int]:
+        """(reads submitted, records skipped as secondary / supplementary, skipped as empty, cells of the record split walked
+        again) of the reads stream just finished or still open (mlst_bam_reads_info)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.mlst_bam_reads_info(self._h, out), "mlst_bam_reads_info")
+        return tuple(int(x) for x in out)
+
+    def debug_last_packed(self):
+        """Test hook (mlst_debug_last_packed): (packed, qrows, lens, words_per_read, qual_stride) of the last submission made from
+        FASTQ text or from the reads of a BAM, copied from the device."""
+        out = (C.c_uint64 * 3)()
+        self._check(self.lib.mlst_debug_last_packed(self._h, None, 0, None, 0, None, 0, out), "mlst_debug_last_packed")
+        n, wpr, qs = (int(x) for x in out)
+        packed = np.zeros(((n + 63) // 64) * 64 * wpr, np.uint32); qrows = np.zeros((n, qs), np.uint8); lens = np.zeros(n, np.uint16)
+        if n:
+            self._check(self.lib.mlst_debug_last_packed(self._h, _ptr(packed), packed.size, _ptr(qrows), qrows.size, _ptr(lens), lens.size, out),
+                        "mlst_debug_last_packed")
+        return packed, qrows, lens, wpr, qs
 
     def bam_set_capacity(self, max_entries: int) -> None:
         self._check(self.lib.mlst_bam_set_capacity(self._h, int(max_entries)), "mlst_bam_set_capacity")

@@ -252,7 +252,8 @@ def type_many_samples(engines, idx, database, targs, samples: list[list[str]], r
 
     def feed(e, job):
         try:
-            submit_sample_files(e, job[1], False, chunk_bytes)
+            # (a BAM's "reads taken" line: unless --quiet, as for a single sample; feeder threads print whole lines)
+            submit_sample_files(e, job[1], False, chunk_bytes, report=None if printer is None else (lambda line: print(line, flush=True)))
         except CorruptInput as ex:
             print(ex, file=sys.stderr, flush=True)
             corrupt.add(job[0])

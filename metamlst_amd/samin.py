@@ -82,7 +82,8 @@ def _aux_text(buf: bytes, at: int, end: int) -> list:
     return out
 
 
-def _iter_bam(fh):
+def _iter_bam(fh, raw: bool = False):
+    """The records of an inflated BAM stream as Alignment; raw: as (QNAME bytes, FLAG, l_seq, packed SEQ, QUAL bytes) instead."""
     def need(n):
         b = fh.read(n)
         if len(b) != n:
@@ -104,6 +105,10 @@ def _iter_bam(fh):
         rec = need(struct.unpack("<i", head)[0])
         ref_id, pos, l_name, _mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiBBHHHi", rec, 0)
         at = 32
+        if raw:
+            at += l_name + 4 * n_cig
+            yield rec[32:32 + l_name - 1], flag, l_seq, rec[at:at + (l_seq + 1) // 2], rec[at + (l_seq + 1) // 2:at + (l_seq + 1) // 2 + l_seq]
+            continue
         qname = rec[at:at + l_name - 1].decode("ascii"); at += l_name
         ops = struct.unpack_from("<%dI" % n_cig, rec, at); at += 4 * n_cig
         cigar = "".join("%d%s" % (o >> 4, CIGAR_OPS[o & 15]) for o in ops) or "*"
@@ -229,6 +234,73 @@ class AlignmentSample:
                 qual[int(seq_off[k]):int(seq_off[k]) + len(q)] = q - 33
         return engine.pileup_alignments(chosen, rec_allele, rec_pos, rec_as, rec_xm, cig_off, cig, seq_off, seq, qual,
                                         a.minscore, a.max_xM, minqual)
+
+
+# ------------------------------------------------------------------ the reads of a BAM (include/mlst.h: mlst_bam_reads_open)
+_NIB_LETTER = b"NACMGRSVTWYHKDBN"                                            # ('=' has no letter of its own in a read: N)
+_NIB_COMP = bytes(int("{:04b}".format(n)[::-1], 2) for n in range(16))      # complement on nibbles: 1 <-> 8, 2 <-> 4 (the bits reversed)
+NO_MATE = "record %d has no mate next to it (a paired BAM must be collated by name)"
+
+
+def _bam_read_records(path: str):
+    """(record index, QNAME, FLAG, bases, Phred+33) of the records `samtools fastq` takes with its defaults, bytes each; the last
+    item is (None, secondary / supplementary skipped, empty skipped)."""
+    n_sec = n_empty = 0
+    with gzip.open(path, "rb") as z:
+        for k, (qname, flag, l_seq, packed, q) in enumerate(_iter_bam(z, raw=True)):
+            if flag & 0x900:
+                n_sec += 1
+                continue
+            if l_seq == 0:
+                n_empty += 1
+                continue
+            nib = np.frombuffer(packed, np.uint8)
+            nib = np.stack((nib >> 4, nib & 15), axis=1).reshape(-1)[:l_seq]      # (the filler nibble of an odd l_seq is dropped here)
+            ph = np.full(l_seq, 1, np.uint8) if q[0] == 0xFF else np.minimum(np.frombuffer(q, np.uint8), 127)
+            if flag & 0x10:
+                nib, ph = np.frombuffer(_NIB_COMP, np.uint8)[nib[::-1]], ph[::-1]
+            yield k, qname, flag, np.frombuffer(_NIB_LETTER, np.uint8)[nib].tobytes(), (ph + 33).astype(np.uint8).tobytes()
+    yield None, n_sec, n_empty
+
+
+def bam_reads_fastq(path: str, paired: bool = False, chunk_bytes: int = 64 << 20, counts: dict | None = None):
+    """The reads of a BAM as FASTQ text, by the rules of mlst_bam_reads_open applied on the host: chunks (bytes) of whole records
+    (paired: of whole pairs).  Name lines are @QNAME, or @QNAME/1 and /2 when not paired and FLAG has 0x40 / 0x80.  paired: kept
+    reads 2k and 2k + 1 must share a QNAME and carry FLAG 0x1 both (ValueError with the library's words otherwise); the text is
+    what mlst_submit_fastq(paired = 1) takes.  counts (optional) receives reads / secondary / empty.  This is the yardstick of
+    the device path and the way in for a BAM that is not BGZF."""
+    out, n_reads, held = bytearray(), 0, None
+    for rec in _bam_read_records(path):
+        if rec[0] is None:
+            if counts is not None:
+                counts.update(reads=n_reads, secondary=rec[1], empty=rec[2])
+            break
+        k, qname, flag, bases, qual = rec
+        name = qname
+        if not paired:
+            name += b"/1" if flag & 0x40 else b"/2" if flag & 0x80 else b""
+        else:      # (the smallest record index that fails, as the device reports it)
+            if held is not None and held[1] != qname:
+                raise ValueError(NO_MATE % held[0])
+            if not flag & 1:
+                raise ValueError(NO_MATE % k)
+            held = (k, qname) if held is None else None
+        out += b"@" + name + b"\n" + bases + b"\n+\n" + qual + b"\n"
+        n_reads += 1
+        if len(out) >= chunk_bytes and held is None:
+            yield bytes(out)
+            out = bytearray()
+    if held is not None:
+        raise ValueError(NO_MATE % held[0])
+    if out:
+        yield bytes(out)
+
+
+def bam_first_read_flags(path: str):
+    """FLAG of the first record of a BAM that is a read (None: the file holds none): bit 0x1 decides whether `cli type` submits
+    the file's reads as pairs -- decided on the first record, as fastq.mates_share_names does for mate files."""
+    for rec in _bam_read_records(path):
+        return None if rec[0] is None else rec[2]
 
 
 # ------------------------------------------------------------------ BGZF BAM on the device
