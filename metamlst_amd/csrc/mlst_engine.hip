@@ -690,7 +690,12 @@ __device__ inline u32 wave_incl_scan_dpp(u32 v) {
 // workgroup ever reads.  What the waves share is LDS: lgkmcnt(0) before s_barrier makes a wave's LDS writes visible to
 // the waves that pass the barrier.
 __device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int WPR, int NW>
+// WO = the write-out of round 7 (profiles/round7/route_diet.md): every owner's segment starts in s_sorted at an index congruent
+// to the owner's carry count modulo four, so that entry i of the stream (carry ++ segment) lies at a 16-byte aligned LDS
+// address for every lane's four -- one 16-byte read per lane and pass instead of four 4-byte reads with a compare and a
+// select each.  WO = false (MLST_ROUTE_WRITEOUT=0) is the write-out and key arithmetic of rounds 2-6, kept for A/B runs;
+// both produce the same arena, word for word.
+template <int WPR, int NW, bool WO>
 __attribute__((amdgpu_waves_per_eu(WPR <= 10 ? 8 : 4, WPR <= 10 ? 8 : 4)))      // reads up to 160 bases: 64 VGPRs, so that the LDS decides how many workgroups share a CU
 __global__ __launch_bounds__(NW * 64) void k_route(const u32* __restrict__ packed, const u16* __restrict__ lens, u64 n_reads,
                                                    const RouteDev R, Counters* __restrict__ ctr) {
@@ -700,12 +705,19 @@ __global__ __launch_bounds__(NW * 64) void k_route(const u32* __restrict__ packe
     constexpr u32 SCAP = TILE * NT + (NW == 16 ? 1024u : 768u);       // + dummy entries of empty runs (typically ~5 %)
     constexpr u32 CW = 16;                        // entries per 64-byte chunk: what leaves for a region is whole, aligned chunks
     constexpr int OPW = RT_OWNERS / NW;           // owners whose segments a wave writes out
+    // WO: up to three words of padding in front of every owner's segment (and in front of the first).  The room for them is
+    // what s_part held: s_part is dead once the scan has read it, the segments are dead until the scan is over, so s_part
+    // lies on the head of s_sorted and the LDS per workgroup is no more than before (two 16-wave workgroups share a CU).
+    constexpr u32 PADROOM = WO ? 3u * RT_OWNERS + 8u : 0u;
+    constexpr u32 SPARE = SCAP + PADROOM;         // a spare word for slots without a seed (a lane's four may read up to three words past the last segment)
+    constexpr u32 PART_AT = WO ? 0u : SPARE + 4u; // where s_part lies in s_sorted[]: behind it, as its own array was, or on its head
+    static_assert(PADROOM == 0 || (SCAP + PADROOM < 65536u && QN * RT_OWNERS <= SCAP), "s_off packs start and length into 16 bits each");
     __shared__ u32 s_cnt[NW][RT_OWNERS];          // per (wave, owner): count, later the start of the run in s_sorted
-    __shared__ __attribute__((aligned(16))) u32 s_sorted[SCAP + 4];      // + a spare word for slots without a seed
-    __shared__ u32 s_part[QN][RT_OWNERS];         // entries of an owner's runs per slice of the waves
-    __shared__ u32 s_off[RT_OWNERS + 1];          // start of each owner's segment in s_sorted (multiples of four)
+    __shared__ __attribute__((aligned(16))) u32 s_sorted[SPARE + 4 + (WO ? 0u : QN * RT_OWNERS)];
+    u32 (*s_part)[RT_OWNERS] = reinterpret_cast<u32 (*)[RT_OWNERS]>(&s_sorted[PART_AT]);      // entries of an owner's runs per slice of the waves
+    __shared__ u32 s_off[RT_OWNERS + 1];          // start of each owner's segment in s_sorted; WO: start | length << 16
     __shared__ u32 s_cur[RT_OWNERS];              // where region (owner, this workgroup) continues, as the number of the 64-byte chunk in the ARENA (one shift away from the address: the region's base was three 64-bit multiply-adds per owner and tile)
-    __shared__ u32 s_carry[RT_OWNERS][CW];        // the entries of an owner that did not fill a chunk yet (fewer than CW), oldest first
+    __shared__ __attribute__((aligned(16))) u32 s_carry[RT_OWNERS][CW];        // the entries of an owner that did not fill a chunk yet (fewer than CW), oldest first
     __shared__ u32 s_cn[RT_OWNERS];               // how many
     __shared__ u32 s_wsum[4]; __shared__ u32 s_over;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // the wave number in a scalar register
@@ -787,7 +799,8 @@ __global__ __launch_bounds__(NW * 64) void k_route(const u32* __restrict__ packe
             const u32 rb_nxt = revc(w[t + 1]);
             const u32 slo = w[t], shi = w[t + 1] & 0xFFu;
             const u32 rlo = __builtin_amdgcn_alignbit(rb_cur, rb_nxt, 24), rhi = rb_cur >> 24;
-            const bool rc_less = rhi < shi || (rhi == shi && rlo < slo);
+            // WO: the 40-bit strand comparison as one 64-bit compare (two vector instructions per seed fewer than two 32-bit compares and an equality)
+            const bool rc_less = WO ? (((u64)rhi << 32) | rlo) < (((u64)shi << 32) | slo) : (rhi < shi || (rhi == shi && rlo < slo));
             u32 ow; rt_hash(rc_less ? rlo : slo, rc_less ? rhi : shi, ow, hv[t]);
             rk[t] = ow;
             rb_cur = rb_nxt;
@@ -821,24 +834,37 @@ __global__ __launch_bounds__(NW * 64) void k_route(const u32* __restrict__ packe
         u32 pq[QN], tot = 0;
         #pragma unroll
         for (int v = 0; v < QN; v++) { pq[v] = s_part[v][so_]; tot += pq[v]; }
-        const u32 inc = wave_incl_scan_dpp(tot);           // every wave scans the 64 owners of its chunk (so_ >> 6)
+        // WO: the segment of owner o starts at an index congruent to its carry count cn[o] modulo four.  Given that, the gap
+        // behind it is a function of the two owners alone, (cn[o+1] - cn[o] - tot[o]) & 3, so the starts are still one prefix
+        // sum: of tot + gap, with the gaps summed in the upper half of the same word (the overflow test below is the one of
+        // WO = false, on the entries without the gaps: the same tiles are routed; the gaps, 3 * 256 + 3 words at most, have
+        // PADROOM of their own).
+        u32 val = tot, cn_o = 0;
+        if (WO) {
+            cn_o = s_cn[so_];
+            const u32 gap = so_ + 1 < RT_OWNERS ? (s_cn[so_ + 1] - cn_o - tot) & 3u : 0u;
+            val = (tot + gap) | (gap << 16);
+        }
+        const u32 inc = wave_incl_scan_dpp(val);           // every wave scans the 64 owners of its chunk (so_ >> 6)
         if (sq_ == 0 && ln == 63) s_wsum[so_ >> 6] = inc;
         lds_barrier();
         {
-            u32 off = inc - tot;
+            u32 off = inc - val;
             for (u32 v = 0; v < (so_ >> 6); v++) off += s_wsum[v];
+            u32 off_e = off;                              // the entries in front of this owner's
+            if (WO) { off_e = (off & 0xFFFFu) - (off >> 16); off = (off & 0xFFFFu) + (s_cn[0] & 3u); }
             if (sq_ == 0) {
-                s_off[so_] = off;
-                if (so_ == RT_OWNERS - 1) s_off[RT_OWNERS] = off + tot;
+                if (WO) s_off[so_] = off | (tot << 16);
+                else { s_off[so_] = off; if (so_ == RT_OWNERS - 1) s_off[RT_OWNERS] = off + tot; }
                 const u32 written = (s_cur[so_] - (so_ * P + p) * cap_ch) * CW;
-                if (written + s_cn[so_] + tot + CW > R.cap || off + tot > SCAP) s_over = 1;      // (+ CW: the last chunk is padded at the end)
+                if (written + (WO ? cn_o : s_cn[so_]) + tot + CW > R.cap || off_e + tot > SCAP) s_over = 1;      // (+ CW: the last chunk is padded at the end)
             }
             #pragma unroll
             for (int v = 0; v < QN; v++) off += (u32)v < sq_ ? pq[v] : 0u;
             #pragma unroll
             for (int v = 0; v < 4; v++) {
                 s_cnt[sq_ * 4 + v][so_] = off;
-                if (c4[v] == 0) { if (off < SCAP) s_sorted[off] = RT_FLAG | RT_DUMMY; off += 1; }      // dummy: the run exists, it holds no seed
+                if (c4[v] == 0) { if (off < SPARE) s_sorted[off] = RT_FLAG | RT_DUMMY; off += 1; }      // dummy: the run exists, it holds no seed
                 else off += c4[v];
             }
         }
@@ -868,7 +894,9 @@ __global__ __launch_bounds__(NW * 64) void k_route(const u32* __restrict__ packe
             #pragma unroll
             for (int t = 0; t < NT; t++) {
                 const bool valid = rk[t] != 0xFFFFFFFFu;
-                s_sorted[valid ? st[t] + (rk[t] & 0xFFFFu) : SCAP] = ((rk[t] & 0xFFFFu) == 0 ? RT_FLAG : 0u) | ((u32)ln << 25) | hv[t];
+                // WO: the run-start flag without a compare and a select -- rank - 1 has bit 31 set for rank 0 alone (ranks are below 2^16)
+                const u32 flag = WO ? ((rk[t] & 0xFFFFu) - 1u) & RT_FLAG : ((rk[t] & 0xFFFFu) == 0 ? RT_FLAG : 0u);
+                s_sorted[valid ? st[t] + (rk[t] & 0xFFFFu) : SPARE] = flag | ((u32)ln << 25) | hv[t];
             }
         }
         lds_barrier();
@@ -879,7 +907,42 @@ __global__ __launch_bounds__(NW * 64) void k_route(const u32* __restrict__ packe
         // lines were completed in L2 by the next tile's segment -- or left it half written; 2.41 GB reached HBM for 2.05 GB
         // of entries.)  Wave v serves owners OPW v .. OPW v + OPW - 1, four at a time: 16 lanes per owner, four consecutive
         // entries of the stream per lane and pass.
-        {
+        // WO: entry i of the stream, i >= cn, is s_sorted[start - cn + i] and start - cn is a multiple of four, so the four
+        // entries of a lane are one 16-byte read, from s_carry below the carry's last whole four and from s_sorted from there
+        // on.  Only the lane at that boundary mixes the two (cn & 3 words of the carry's last four, read once per owner, over
+        // what lies in front of the segment: the gap or the tail of the owner before).  What a lane reads past the end of the
+        // stream is never looked at: a chunk that leaves is whole, and s_carry is read below s_cn only.
+        if constexpr (WO) {
+            constexpr int NI = 2;                 // owners-of-four handled together (OPW / 4 = 4 or 8 in all)
+            const u32 sub = (u32)ln & 15u, grp = (u32)ln >> 4;
+            #pragma unroll
+            for (int i0 = 0; i0 < OPW / 4; i0 += NI) {
+                u32 oo[NI], sl[NI], sc[NI], cn[NI];
+                #pragma unroll
+                for (int i = 0; i < NI; i++) {
+                    oo[i] = (u32)wave * OPW + (u32)(i0 + i) * 4 + grp;
+                    asm volatile("" : "+v"(oo[i]));      // keeps the region addresses out of the loop-invariant (spilled) set
+                    sl[i] = s_off[oo[i]]; sc[i] = s_cur[oo[i]]; cn[i] = s_cn[oo[i]];
+                }
+                tie_all<NI>(sl); tie_all<NI>(sc); tie_all<NI>(cn);
+                #pragma unroll
+                for (int i = 0; i < NI; i++) {
+                    const u32 T = cn[i] + (sl[i] >> 16), out = T & ~(CW - 1u), cq = cn[i] & ~3u, k = cn[i] & 3u;
+                    const u32 vb = (sl[i] & 0xFFFFu) - cn[i];      // (below zero for a carry longer than the start: only indices from cq on are read)
+                    u32* carry = &s_carry[oo[i]][0];
+                    const v4u c = *reinterpret_cast<const v4u*>(carry + cq);
+                    auto dst = reinterpret_cast<v4u GLOBAL_AS*>(R.arena.g()) + (u64)sc[i] * (CW / 4);
+                    for (u32 base = sub * 4; base < T; base += 64) {      // one pass for streams up to 64 entries, seldom two
+                        const u32* src = base < cq ? carry + base : &s_sorted[vb + base];
+                        v4u q4 = *reinterpret_cast<const v4u*>(src);
+                        if (base == cq) { q4.x = k > 0 ? c.x : q4.x; q4.y = k > 1 ? c.y : q4.y; q4.z = k > 2 ? c.z : q4.z; }
+                        if (base < out) dst[base >> 2] = q4;      // (base and out are multiples of 4 and 16: whole or not at all)
+                        else *reinterpret_cast<v4u*>(carry + (base - out)) = q4;
+                    }
+                    if (sub == 0) { s_cur[oo[i]] = sc[i] + out / CW; s_cn[oo[i]] = T - out; }
+                }
+            }
+        } else {
             constexpr int NI = 2;                 // owners-of-four handled together (OPW / 4 = 4 or 8 in all)
             const u32 sub = (u32)ln & 15u, grp = (u32)ln >> 4;
             #pragma unroll
@@ -923,7 +986,8 @@ __global__ __launch_bounds__(NW * 64) void k_route(const u32* __restrict__ packe
     }
     if (tid < RT_OWNERS) {      // the last, partly filled chunk of every region: padded with entries that are neither a seed nor a run start
         const u32 ch = s_cur[tid], cn = s_cn[tid];
-        u32 done = (ch - ((u32)tid * P + p) * cap_ch) * CW;
+        u32 to = (u32)tid; if (WO) asm volatile("" : "+v"(to));      // (the region's base computed here: held across the tile loop it was the one register too many)
+        u32 done = (ch - (to * P + p) * cap_ch) * CW;
         if (cn) {
             auto dst = reinterpret_cast<v4u GLOBAL_AS*>(R.arena.g()) + (u64)ch * (CW / 4);
             #pragma unroll
@@ -3637,7 +3701,7 @@ struct mlst_handle {
     // CU-routed sieve (K1c): filter slices (reference) and the per-submission arena
     int sieve_kind = 0; u32 sieve_chain = 0; u64 n_keys = 0;
     u32* d_rfilter = nullptr; u32* d_rt_arena = nullptr; u64 cap_rt_arena = 0; u32* d_rt_counts = nullptr; u32* d_rt_emitted = nullptr; u64 cap_rt_emitted = 0;
-    u32 rt_prod = 0, rt_cap = 0, rt_tiles_max = 0, rt_nw = 16, rt_pf = 2, rt_exam = RT_EXAM_DEFAULT; u64 rt_slice = 0;
+    u32 rt_prod = 0, rt_cap = 0, rt_tiles_max = 0, rt_nw = 16, rt_pf = 2, rt_exam = RT_EXAM_DEFAULT, rt_wo = 1; u64 rt_slice = 0;
     u64* d_rt_parked = nullptr; u64 cap_rt_parked = 0;      // entries that passed the LDS filter (k_route_probe -> k_route_verify)
     u64* d_rt_trace = nullptr; bool rt_trace_on = false; const void* rt_last_packed = nullptr;      // mlst_get_route_trace
     std::vector<void*> dbg_pads;                 // mlst_debug_route_realloc: allocations kept to move the arena elsewhere
@@ -4460,6 +4524,8 @@ extern "C" int mlst_pack_reads_device(mlst_handle* h, const uint8_t* d_bases, co
 static int ensure_route_buffers(mlst_handle* h, u64 n_reads, u32 wpr, u64 n_reads_flags = 0) {
     u32 nw = 16;                                        // waves per producer workgroup (tile = nw groups of 64 reads)
     { const char* e = getenv("MLST_ROUTE_WAVES"); if (e && atoi(e) == 8) nw = 8; }
+    // the producer's write-out: aligned 16-byte LDS reads (round 7, profiles/round7/route_diet.md); 0 = the one of rounds 2-6 (A/B), same arena
+    { const char* e = getenv("MLST_ROUTE_WRITEOUT"); h->rt_wo = (e && e[0] == '0' && e[1] == 0) ? 0u : 1u; }
     { const char* e = getenv("MLST_PROBE_PF"); h->rt_pf = (e && atoi(e) == 4) ? 4u : 2u; }
     // examiner waves of k_route_probe: 1, 2 or 4 of its 16 (profiles/round6/probe_examiners.md); 0 = none, k_route_verify examines (A/B)
     { const char* e = getenv("MLST_PROBE_EXAM_WAVES"); const int v = e ? atoi(e) : RT_EXAM_DEFAULT; h->rt_exam = (v == 0 || v == 1 || v == 2 || v == 4) ? (u32)v : (u32)RT_EXAM_DEFAULT; }
@@ -4538,7 +4604,7 @@ static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* 
     const int gs = phase ? 0 : graph_enter(h, h->g_submit, {(u64)(uintptr_t)d_packed, (u64)(uintptr_t)d_qrows, (u64)(uintptr_t)d_lens, (u64)n_reads, (u64)wpr,
                                                (u64)qstride, (u64)h->reads_seen, (u64)(uintptr_t)h->d_cand,
                                                (u64)(uintptr_t)h->d_bin_flags, (u64)(uintptr_t)h->d_rt_arena, (u64)(uintptr_t)h->d_rt_counts,
-                                               (u64)(uintptr_t)h->d_rt_emitted, (u64)h->rt_cap, (u64)h->rt_prod, (u64)h->rt_nw, (u64)paired, (u64)(uintptr_t)h->d_rt_trace, (u64)(uintptr_t)h->d_rt_parked, (u64)h->cap_rt_parked, (u64)h->rt_pf, rt_slice, (u64)h->rt_exam});
+                                               (u64)(uintptr_t)h->d_rt_emitted, (u64)h->rt_cap, (u64)h->rt_prod, (u64)h->rt_nw, (u64)paired, (u64)(uintptr_t)h->d_rt_trace, (u64)(uintptr_t)h->d_rt_parked, (u64)h->cap_rt_parked, (u64)h->rt_pf, rt_slice, (u64)h->rt_exam, (u64)h->rt_wo});
     if (gs == 1) { h->reads_seen += n_reads; return MLST_OK; }
     if (phase != 2) { Prof pf(h, 0);
       if (h->sieve_kind == MLST_SIEVE_LDS) {      // LDS first level: one 1024-thread workgroup per CU
@@ -4558,11 +4624,13 @@ static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* 
         R.cap = h->rt_cap; R.n_prod = h->rt_prod; R.tiles_max = h->rt_tiles_max; R.nw = h->rt_nw;
         { const char* e = getenv("MLST_RT_DEBUG"); R.dbg = e ? (u32)atoi(e) : 0u; if (R.dbg & 2u) R.parked_cap = 0; }      // 2 = examine in place (no k_route_verify work)
         { Prof pa(h, 9);
-#define SIEVE_CASE(W) case W: if (h->rt_nw == 8) hipLaunchKernelGGL((k_route<W, 8>), dim3(h->rt_prod), dim3(512), 0, h->stream, sl_packed, sl_lens, (u64)sl_n, R, E.ctr); \
-                              else hipLaunchKernelGGL((k_route<W, 16>), dim3(h->rt_prod), dim3(1024), 0, h->stream, sl_packed, sl_lens, (u64)sl_n, R, E.ctr); break;
+#define ROUTE_LAUNCH(W, N, WO) hipLaunchKernelGGL((k_route<W, N, WO>), dim3(h->rt_prod), dim3(N * 64), 0, h->stream, sl_packed, sl_lens, (u64)sl_n, R, E.ctr)
+#define SIEVE_CASE(W) case W: if (h->rt_nw == 8) { if (h->rt_wo) ROUTE_LAUNCH(W, 8, true); else ROUTE_LAUNCH(W, 8, false); } \
+                              else { if (h->rt_wo) ROUTE_LAUNCH(W, 16, true); else ROUTE_LAUNCH(W, 16, false); } break;
         switch (wpr) { SIEVE_CASE(2) SIEVE_CASE(4) SIEVE_CASE(6) SIEVE_CASE(8) SIEVE_CASE(10) SIEVE_CASE(12) SIEVE_CASE(14)
                        SIEVE_CASE(16) SIEVE_CASE(18) SIEVE_CASE(20) default: return fail(h, MLST_E_INVALID, "words_per_read %u unsupported", wpr); }
 #undef SIEVE_CASE
+#undef ROUTE_LAUNCH
         }
         { Prof pb(h, 10);
 #define PROBE_LAUNCH(W, PF, EX) hipLaunchKernelGGL((k_route_probe<W, PF, EX>), dim3(RT_OWNERS), dim3(1024), 0, h->stream, sl_packed, (u64)sl_n, E.sieve, E.sieve_mask, R, E.ctr)
