@@ -69,7 +69,10 @@ enum {
 void mlst_default_params(mlst_params* p);
 
 /* Create / destroy an engine bound to HIP device `device`.  Fails with MLST_E_NOGPU when
- * no device is present (there is no CPU path in this library). */
+ * no device is present (there is no CPU path in this library), and with MLST_E_LIMIT for scoring
+ * parameters under which a read of MLST_MAX_READ_LEN bases could exceed a packed field (10-bit score,
+ * 8-bit xm, 7-bit xo): match_bonus * 320 >= 1024, match_bonus > 4 * min(n_penalty, mm_min), or
+ * 5 * match_bonus > 2 * (gap_open + gap_ext). */
 int  mlst_create(int device, const mlst_params* p, mlst_handle** out);
 void mlst_destroy(mlst_handle* h);
 const char* mlst_last_error(const mlst_handle* h);   /* h may be NULL: last create error */

@@ -3869,6 +3869,17 @@ extern "C" int mlst_create(int device, const mlst_params* p, mlst_handle** out) 
     if (prm.band_w < 1 || prm.band_w > MAX_W) return fail(nullptr, MLST_E_INVALID, "band_w must be in 1..%d", MAX_W);
     if (prm.max_xm > 254 || prm.minscore > 1000) return fail(nullptr, MLST_E_INVALID, "max_xm/minscore out of range");
     if (prm.match_bonus < 1 || prm.match_bonus > 127) return fail(nullptr, MLST_E_INVALID, "match_bonus must be in 1..127");
+    {   // The packed results keep the score in 10 bits, xm in 8 and xo in 7: a scoring scheme under which a read of
+        // MLST_MAX_READ_LEN bases can exceed one of them is refused here, so that no submission ever wraps a field.
+        const int pmin = std::min(prm.n_penalty, prm.mm_min), gap1 = prm.gap_open + prm.gap_ext;
+        if (pmin < 0 || prm.mm_max < prm.mm_min || prm.gap_open < 0 || prm.gap_ext < 0) return fail(nullptr, MLST_E_INVALID, "penalties must not be negative, mm_max not below mm_min");
+        if (prm.match_bonus * MLST_MAX_READ_LEN >= 1024)       // a perfect read of 320 bases
+            return fail(nullptr, MLST_E_LIMIT, "match_bonus %d: the score of a %d-base read does not fit 10 bits", prm.match_bonus, MLST_MAX_READ_LEN);
+        if (prm.match_bonus > 4 * pmin)                         // xm = 256 with a positive score: 64 matches outweigh 256 cheapest mismatches
+            return fail(nullptr, MLST_E_LIMIT, "match_bonus %d against a cheapest mismatch of %d: xm of a %d-base read does not fit 8 bits", prm.match_bonus, pmin, MLST_MAX_READ_LEN);
+        if (5 * prm.match_bonus > 2 * gap1)                     // xo = 128 with a positive score: 320 matches outweigh 128 gaps of one base
+            return fail(nullptr, MLST_E_LIMIT, "match_bonus %d against a one-base gap of %d: xo of a %d-base read does not fit 7 bits", prm.match_bonus, gap1, MLST_MAX_READ_LEN);
+    }
     if (!prm.max_retained_reads) prm.max_retained_reads = 4ull << 20;
     if (!prm.max_items) prm.max_items = 8ull << 20;
     if (prm.max_items >= (1ull << 32)) return fail(nullptr, MLST_E_INVALID, "max_items must be below 2^32");
