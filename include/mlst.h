@@ -356,6 +356,32 @@ int mlst_bam_pileup_fetch(mlst_handle* h, uint32_t* counts);
 int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip_bytes, int paired);
 int mlst_bam_reads_info(mlst_handle* h, uint64_t out[4]);
 
+/* ---- CONTIGS (an assembled genome, the modality of the reference's mlst.py) tiled into reads on the GPU -----------------------------
+ * `text` is uncompressed FASTA in host memory that holds whole contigs (a call's text is cut in front of a '>' that starts a line, as
+ * mlst_submit_fastq wants whole records).  The bytes cross the link once; the contigs are cut into overlapping windows, packed on the
+ * device (csrc/fasta_dev.h) and typed like unpaired reads of a FASTQ file.  Replaces the FASTQ text metamlst_amd.fastq.tile_fasta
+ * writes on the host, whose rules these are:
+ *   - a line whose first byte is '>' opens a contig; everything else on that line is ignored.  A '>' anywhere else is a base.
+ *   - lines in front of the first header of a call are ignored.
+ *   - a contig's sequence is the bytes of its lines with the line ends (LF or CRLF) removed; empty lines add nothing; the last line
+ *     need not end with LF.
+ *   - a contig of n bases: n < min_len: no read.  n <= read_len: one read of n bases.  Otherwise windows of read_len bases at starts
+ *     0, stride, 2 * stride, ... <= n - read_len, plus one flush with the contig's end when (n - read_len) % stride != 0.
+ *   - read order is contig order, then start order; read indices continue the handle's count across calls (locus_first_read and
+ *     mlst_set_read_index_base as after FASTQ).
+ *   - letters in either case are themselves; every other byte (N, IUPAC, '>', bytes >= 0x80, NUL) is a non-ACGT base: packed as A,
+ *     bit 7 in its qrows byte, bit 15 of lens -- what an N of FASTQ text gets.
+ *   - every base has Phred 40; qrows bytes past a read's end are 0.  words_per_read / qual_stride are those of the FASTQ path for
+ *     the longest read of the call.
+ * Refused: read_len, stride or min_len of 0 (MLST_E_INVALID); read_len > 320 (MLST_MAX_READ_LEN: MLST_E_LIMIT); a call while a FASTQ
+ * or BAM stream is open on the handle.  A sequence line of a contig that holds 0x09, 0x0B, 0x0C, 0x20 or a CR that is not directly
+ * in front of an LF -- where Python's strip() and a device rule could part ways -- submits nothing of the call and fails with
+ * MLST_E_INVALID "host path needed: <reason> at byte <n>" (n counts the call's text from 0): the caller tiles the file on the host.
+ * A call that yields no read returns 0 and submits nothing.  n_contigs_out / n_reads_out (optional): header lines / reads of the
+ * call.  One host synchronisation per call (the counts size the pack buffers).  Compressed FASTA is inflated by the caller. */
+int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n_bytes, uint32_t read_len, uint32_t stride, uint32_t min_len,
+                      uint64_t* n_contigs_out, uint64_t* n_reads_out);
+
 /* ---- whole typing tail on the device, without a host round trip between the passes ----------------------
  * mlst_typing_enqueue queues, behind the pass-1 work already submitted on the engine's stream:
  *   the allele choice of metamlst.py:133-151 + :244 (per locus the allele with the highest

@@ -71,11 +71,11 @@ int mlst_debug_route_probe(mlst_handle* h, uint64_t* ring_full, uint32_t* cand, 
  * takes); 0 = off.  *cells_rewalked_out: cells walked again during the last stream.  Only while no BAM stream is open. */
 int mlst_debug_bam_split(mlst_handle* h, uint32_t force_miss_every, uint64_t* cells_rewalked_out);
 
-/* The pack buffers of the LAST submission made from FASTQ text (k_pack_text) or from the reads of a BAM (k_bamr_pack,
- * csrc/bam_reads.h), copied out: `packed` in the resident layout (ceil(n / 64) * 64 * wpr words), `qrows` (n x qstride), `lens`;
+/* The pack buffers of the LAST submission made from FASTQ text (k_pack_text), from the reads of a BAM (k_bamr_pack,
+ * csrc/bam_reads.h) or from contigs tiled on the device (mlst_submit_fasta: k_pack_text over csrc/fasta_dev.h's flat sequence), copied out: `packed` in the resident layout (ceil(n / 64) * 64 * wpr words), `qrows` (n x qstride), `lens`;
  * any of the three may be NULL.  out = { n_reads, words_per_read, qual_stride } (all 0 before the first such submission).  A
  * piece in flight is finished first; MLST_E_CAPACITY when a buffer is too small (out is filled in either way).
- * tests/test_gpu_bam_reads.py compares the rows with mlst_pack_fastq_host's. */
+ * tests/test_gpu_bam_reads.py and tests/test_gpu_fasta.py compare the rows with mlst_pack_fastq_host's. */
 int mlst_debug_last_packed(mlst_handle* h, uint32_t* packed, uint64_t cap_words, uint8_t* qrows, uint64_t cap_q, uint16_t* lens, uint64_t cap_reads,
                            uint64_t out[3] /* n_reads, wpr, qstride */);
 

@@ -125,26 +125,41 @@ def run_index(a) -> int:
 
 
 FASTQ_SUFFIXES = (".fastq", ".fq", ".fastq.gz", ".fq.gz", ".fastq.bgz", ".fq.bgz")
+FASTA_SUFFIXES = (".fa", ".fna", ".fasta", ".fas", ".fa.gz", ".fna.gz", ".fasta.gz", ".fas.gz")
 
 
-def expand_samples(reads: list[str]) -> list[list[str]]:
-    """READS arguments -> one list of files per sample (a folder contributes its FASTQ files in name order)."""
+def expand_samples(reads: list[str], contigs: bool = False) -> list[list[str]]:
+    """READS arguments -> one list of files per sample (a folder contributes its FASTQ files in name order; contigs: its FASTA
+    files -- assemblies, one sample each -- instead)."""
     out = []
     for r in reads:
         if os.path.isdir(r):
-            out += [[os.path.join(r, f)] for f in sorted(os.listdir(r)) if f.endswith(FASTQ_SUFFIXES)]
+            out += [[os.path.join(r, f)] for f in sorted(os.listdir(r)) if f.endswith(FASTA_SUFFIXES if contigs else FASTQ_SUFFIXES)]
         else:
             out.append(r.split(",") if "," in r and not os.path.exists(r) else [r])
     return out
 
 
 def run_type(a, argv=None) -> int:
-    samples = expand_samples(a.READS)
+    tile = None
+    if a.contigs:
+        if a.mates or a.alignments:
+            print("--contigs takes assemblies (FASTA): it goes with neither -2 nor --alignments")
+            return 1
+        try:
+            read_len, stride = (int(x) for x in a.tile.split(","))
+            if read_len < 1 or stride < 1:
+                raise ValueError
+        except ValueError:
+            print("--tile LEN,STEP takes two positive numbers, not %r" % a.tile)
+            return 1
+        tile = (read_len, stride, a.min_read_len)
+    samples = expand_samples(a.READS, contigs=bool(a.contigs))
     if not samples:
-        print("no FASTQ file found in " + ", ".join(a.READS))
+        print("no %s file found in " % ("FASTA" if a.contigs else "FASTQ") + ", ".join(a.READS))
         return 1
     many = len(samples) > 1
-    if many and (a.alignments or a.contigs or a.mates):
+    if many and (a.alignments or a.mates):
         print("several samples at once: FASTQ input only (use `r1.fq,r2.fq` for a sample made of two files)")
         return 1
     a.READS, extra_files = samples[0][0], samples[0][1:]
@@ -154,7 +169,7 @@ def run_type(a, argv=None) -> int:
         print("-2 names the second FASTQ file of a pair: the mates of a BAM are records of the BAM itself (collate it by name)")
         return 1
     if a.gpus > 1 and world == 1:
-        if a.alignments or a.contigs or has_bam:
+        if a.alignments or (a.contigs and not many) or has_bam:      # (a folder of assemblies is dealt to the ranks, one assembly is not cut up)
             print("--gpus applies to FASTQ input")
             return 1
         from .multigpu import launch_ranks
@@ -206,7 +221,7 @@ def run_type(a, argv=None) -> int:
     if many:
         from .multigpu import type_many_samples
         rc = type_many_samples(engines, idx, database, targs, samples, rank, world, a.o, a.log, chunk_bytes,
-                               printer=None if a.quiet else (lambda results: _print_results(a, results)))
+                               printer=None if a.quiet else (lambda results: _print_results(a, results)), tile=tile)
         database.closeConnection()
         return rc
     if a.alignments:
@@ -234,10 +249,8 @@ def run_type(a, argv=None) -> int:
                 return 1
         smp = AlignmentSample(idx, targs).add_file(a.READS)
         return _finish_type(a, idx, database, targs, smp.stats(), lambda chosen: smp.pileup(eng, chosen))
-    if a.contigs:
-        read_len, stride = (int(x) for x in a.tile.split(","))
-        for chunk in tile_fasta(a.READS, read_len, stride, a.min_read_len):
-            eng.submit_fastq(chunk, paired=False)
+    if a.contigs:      # the file's bytes go to the GPU and are cut into windows there (mlst_submit_fasta)
+        submit_contigs(eng, a.READS, tile)
         return _finish_type_device(a, eng, idx, database, targs)
     # Mates are unpaired reads for the aligner (bowtie2 -U r1,r2).  What a shared read name changes is sequenceBank
     # (metamlst.py:127: one entry per QNAME and locus): pairs whose files name both mates alike are submitted as pairs.
@@ -320,9 +333,31 @@ def submit_bam_reads(eng, path: str, report=None) -> int:
     return n
 
 
-def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader=None, report=None) -> None:
+def submit_contigs(eng, path: str, tile) -> int:
+    """The contigs of one FASTA file into one engine as overlapping windows, tile = (read_len, stride, min_len): cut and packed on
+    the GPU (Engine.submit_fasta_file).  A file with a sequence line only Python's strip() treats (HostPathNeeded) is said so on
+    stderr and tiled on the host instead (tile_fasta, the statement of the rules).  Returns the reads submitted."""
+    from .engine import HostPathNeeded
+    read_len, stride, min_len = tile
+    try:
+        return eng.submit_fasta_file(path, read_len, stride, min_len)[1]
+    except HostPathNeeded as e:      # which path typed the sample is the user's to know
+        print("%s: %s -- reading the file on the host instead" % (path, str(e).split(": ", 1)[-1]), file=sys.stderr, flush=True)
+        eng.reset_sample()
+    n = 0
+    for chunk in tile_fasta(path, read_len, stride, min_len):
+        n += eng.submit_fastq(chunk, paired=False)
+    return n
+
+
+def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader=None, report=None, tile=None) -> None:
     """All reads of one sample's file(s) into one engine: FASTQ (first_reader: open_sample_reader(paths, ...), if opened ahead), or
-    BAMs whose records are taken as reads (report: see submit_bam_reads)."""
+    BAMs whose records are taken as reads (report: see submit_bam_reads).  tile = (read_len, stride, min_len): the files are
+    assemblies (FASTA), cut into windows on the GPU (submit_contigs)."""
+    if tile is not None:
+        for path in paths:
+            submit_contigs(eng, path, tile)
+        return
     if paired and is_bgzf(paths[0]) and is_bgzf(paths[1]):      # bgzip'd mates: inflated and paired on the GPU
         crc_checked(paths, lambda: eng.submit_fastq_bgzf_pair_files(paths[0], paths[1]))
         return

@@ -3668,6 +3668,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 
 #include "bam_dev.h"
 #include "bam_reads.h"
+#include "fasta_dev.h"
 
 // ================================================================== host side
 struct EvPair { hipEvent_t a, b; int which; };
@@ -3776,7 +3777,11 @@ struct mlst_handle {
     double wall_khz = 100000.0;                  // wall_clock64 rate (hipDeviceAttributeWallClockRate)
     struct BamStream* bam = nullptr;             // BAM input (mlst_bam_open / mlst_submit_bam_bgzf), allocated by the first stream
     u32 bam_force_miss = 0; u64 bam_max_entries = 0;      // mlst_debug_bam_split, mlst_bam_set_capacity
-    struct { u64 n_reads = 0; u32 wpr = 0, qstride = 0; } last_pack;      // mlst_debug_last_packed: what d_packed / d_qrows / d_lens hold (text and BAM reads)
+    struct { u64 n_reads = 0; u32 wpr = 0, qstride = 0; } last_pack;      // mlst_debug_last_packed: what d_packed / d_qrows / d_lens hold (text, BAM reads, tiled contigs)
+    // contigs tiled on the device (mlst_submit_fasta; csrc/fasta_dev.h): the descriptor and the results on the device, their pinned
+    // mirrors (h_fa: FaDev, then FaMeta), the flat sequence, the per-cell and the per-contig tables
+    struct { FaDev* d_desc = nullptr; FaMeta* d_meta = nullptr; u8* h_fa = nullptr; u8* d_flat = nullptr; u64 cap_flat = 0;
+             u32* d_kind = nullptr; u64* d_cseq = nullptr; u64* d_chdr = nullptr; u64 cap_cells = 0; u64* d_cstart = nullptr; u64* d_wcnt = nullptr; u64 cap_contigs = 0; } fa;
 };
 
 static std::string g_create_err;
@@ -3958,6 +3963,8 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     hipFree(h->d_cand); hipFree(h->d_in_bases); hipFree(h->d_in_quals); hipFree(h->d_in_off);
     hipFree(h->d_fq_slot[0]); hipFree(h->d_fq_slot[1]); hipFree(h->d_fq_nl[0]); hipFree(h->d_fq_nl[1]); hipFree(h->d_fq_blk); hipFree(h->d_fq_lines); hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); hipFree(h->d_fq_meta);
     hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta);
+    hipFree(h->fa.d_desc); hipFree(h->fa.d_meta); hipFree(h->fa.d_flat); hipFree(h->fa.d_kind); hipFree(h->fa.d_cseq); hipFree(h->fa.d_chdr); hipFree(h->fa.d_cstart); hipFree(h->fa.d_wcnt);
+    if (h->fa.h_fa) hipHostFree(h->fa.h_fa);
     hipFree(h->d_bgzf); hipFree(h->d_bgzf_blk); hipFree(h->d_fq_carry); h->d_bgzf = nullptr; h->d_bgzf_blk = nullptr; h->d_fq_carry = nullptr; h->cap_bgzf = h->cap_bgzf_blk = h->cap_fq_carry = h->fq_carry_len = 0;
     hipFree(h->d_packed); hipFree(h->d_qrows); hipFree(h->d_lens); hipFree(h->d_counts); hipFree(h->d_dist); hipFree(h->d_query);
     for (auto* g : {&h->g_submit, &h->g_typing}) if (g->exec) hipGraphExecDestroy(g->exec);
@@ -6204,7 +6211,117 @@ extern "C" int mlst_bam_reads_info(mlst_handle* h, uint64_t out[4]) {
     return MLST_OK;
 }
 
-// test hook (include/mlst_debug.h): the pack buffers of the last submission made from FASTQ text or from the reads of a BAM
+// ---- contigs tiled into reads on the device (kernels: csrc/fasta_dev.h; the rules: include/mlst.h).  The text crosses the link once
+// into a text slot of the FASTQ entries; header / sequence state, the flat sequence, the contig table and the reads of every contig
+// are made on the engine's stream.  One host synchronisation: contig and read counts and the longest read size the pack buffers,
+// as on the BAM-reads path.  The contig tables are sized by a guess (one contig per 64 bytes of text, and what earlier calls
+// needed); a call with more contigs than that repeats the steps behind the cell scan with tables that fit (a second
+// synchronisation, for texts of very short contigs only).  The reads are packed by k_pack_text and submitted unpaired.
+extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n_bytes, uint32_t read_len, uint32_t stride, uint32_t min_len,
+                                 uint64_t* n_contigs_out, uint64_t* n_reads_out) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (n_contigs_out) *n_contigs_out = 0;
+    if (n_reads_out) *n_reads_out = 0;
+    if (read_len == 0 || stride == 0 || min_len == 0) return fail(h, MLST_E_INVALID, "read_len, stride and min_len must be positive");
+    if (read_len > (u32)MLST_MAX_READ_LEN) return fail(h, MLST_E_LIMIT, "read_len %u exceeds %d bases", read_len, MLST_MAX_READ_LEN);
+    if (n_bytes == 0) return MLST_OK;
+    if (!text) return fail(h, MLST_E_INVALID, "NULL argument");
+    if (n_bytes >= (1ull << 40)) return fail(h, MLST_E_LIMIT, "FASTA chunk too large");
+    // lines in front of the first header are ignored: the device's text begins with that header's '>'
+    u64 skip = 0;
+    if (text[0] != '>') {
+        const u8* p = text; const u8* const e = text + n_bytes;
+        for (;;) {
+            const u8* q = (const u8*)memchr(p, '\n', (size_t)(e - p));
+            if (!q || q + 1 >= e) return MLST_OK;      // no header: no contig
+            if (q[1] == '>') { skip = (u64)(q + 1 - text); break; }
+            p = q + 1;
+        }
+    }
+    const u64 n = n_bytes - skip;
+    const u64 n_cells = (n + FA_CELL - 1) / FA_CELL;
+    hipSetDevice(h->device);
+    auto& F = h->fa;
+    if (!F.d_desc) HIPCHK(h, dmalloc(&F.d_desc, (u64)1));
+    if (!F.d_meta) HIPCHK(h, dmalloc(&F.d_meta, (u64)1));
+    if (!F.h_fa) { void* p = nullptr; HIPCHK(h, hipHostMalloc(&p, sizeof(FaDev) + sizeof(FaMeta), hipHostMallocDefault)); F.h_fa = (u8*)p; }
+    { int rc = next_text_slot(h, n); if (rc) return rc; }
+    const int tslot = h->fq_slot;
+    { int rc = h2d_overlapped(h, h->d_fq_text, text + skip, n, h->ev_packed[tslot]); if (rc) return rc; }
+    // (buffers of the call before are free: every call ends after its last kernel that reads them was queued on this stream, and
+    // hipFree waits for the device)
+    if (F.cap_flat < n) {
+        hipFree(F.d_flat); F.d_flat = nullptr; F.cap_flat = 0;
+        HIPCHK(h, dmalloc(&F.d_flat, (u64)FA_QUAL + n + 16)); F.cap_flat = n;
+        HIPCHK(h, hipMemsetAsync(F.d_flat, 'I', FA_QUAL, h->stream));
+    }
+    if (F.cap_cells < n_cells) {
+        hipFree(F.d_kind); hipFree(F.d_cseq); hipFree(F.d_chdr); F.d_kind = nullptr; F.d_cseq = F.d_chdr = nullptr; F.cap_cells = 0;
+        HIPCHK(h, dmalloc(&F.d_kind, n_cells)); HIPCHK(h, dmalloc(&F.d_cseq, n_cells)); HIPCHK(h, dmalloc(&F.d_chdr, n_cells)); F.cap_cells = n_cells;
+    }
+    u64 want_contigs = n / 64 + 1024;
+    FaMeta m; memset(&m, 0, sizeof m);
+    for (int turn = 0; ; turn++) {
+        if (F.cap_contigs < want_contigs) {
+            hipFree(F.d_cstart); hipFree(F.d_wcnt); F.d_cstart = F.d_wcnt = nullptr; F.cap_contigs = 0;
+            HIPCHK(h, dmalloc(&F.d_cstart, want_contigs)); HIPCHK(h, dmalloc(&F.d_wcnt, want_contigs)); F.cap_contigs = want_contigs;
+        }
+        FaDev* D = (FaDev*)F.h_fa;      // (the copy of the turn before has been waited for)
+        D->text = h->d_fq_text; D->flat = F.d_flat; D->kind = F.d_kind; D->cseq = F.d_cseq; D->chdr = F.d_chdr; D->cstart = F.d_cstart; D->wcnt = F.d_wcnt;
+        D->meta = F.d_meta; D->cap_contigs = F.cap_contigs;
+        HIPCHK(h, hipMemcpyAsync(F.d_desc, D, sizeof(FaDev), hipMemcpyHostToDevice, h->stream));
+        {
+            Prof pf(h, 6);
+            if (turn == 0) {
+                HIPCHK(h, hipMemsetAsync(F.d_meta, 0, sizeof(FaMeta), h->stream));
+                HIPCHK(h, hipMemsetAsync(F.d_meta, 0xFF, 8, h->stream));      // err_key
+                hipLaunchKernelGGL(k_fa_kind, dim3((u32)n_cells), dim3(256), 0, h->stream, (const FaDev*)F.d_desc, n);
+                hipLaunchKernelGGL(k_fa_state, dim3(1), dim3(1024), 0, h->stream, (const FaDev*)F.d_desc, (u32)n_cells);
+                hipLaunchKernelGGL(k_fa_count, dim3((u32)n_cells), dim3(256), 0, h->stream, (const FaDev*)F.d_desc, n);
+                hipLaunchKernelGGL(k_fa_scan, dim3(1), dim3(1024), 0, h->stream, (const FaDev*)F.d_desc, 0, n_cells);
+            } else HIPCHK(h, hipMemsetAsync(&F.d_meta->max_len, 0, 4, h->stream));
+            hipLaunchKernelGGL(k_fa_compact, dim3((u32)n_cells), dim3(256), 0, h->stream, (const FaDev*)F.d_desc, n);
+            hipLaunchKernelGGL(k_fa_windows, dim3(grid_for(F.cap_contigs, 256, 1024)), dim3(256), 0, h->stream, (const FaDev*)F.d_desc, read_len, stride, min_len);
+            hipLaunchKernelGGL(k_fa_scan, dim3(1), dim3(1024), 0, h->stream, (const FaDev*)F.d_desc, 1, (u64)0);
+        }
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(F.h_fa + sizeof(FaDev), F.d_meta, sizeof(FaMeta), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));      // the one host synchronisation of a call
+        memcpy(&m, F.h_fa + sizeof(FaDev), sizeof m);
+        if (m.err_key != ~0ull || m.n_contigs <= F.cap_contigs) break;
+        if (turn) return fail(h, MLST_E_HIP, "FASTA contig table inconsistent");
+        want_contigs = m.n_contigs;
+    }
+    HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
+    if (m.err_key != ~0ull)
+        return fail(h, MLST_E_INVALID, "host path needed: %s at byte %llu", (m.err_key & 7u) == FA_BAD_CR ? "a CR without its LF in a sequence line" : "white space inside a sequence line",
+                    (unsigned long long)((m.err_key >> 3) + skip));
+    if (m.n_seq > n || m.max_len > read_len) return fail(h, MLST_E_HIP, "FASTA tables inconsistent");
+    if (n_contigs_out) *n_contigs_out = m.n_contigs;
+    const u64 n_reads = m.n_reads;
+    if (n_reads == 0) return MLST_OK;
+    if (n_reads >= (1ull << 32)) return fail(h, MLST_E_LIMIT, "more than 2^32 reads from one FASTA chunk");
+    if (h->cap_fq_reads < n_reads) { hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); h->d_fq_soff = h->d_fq_qoff = nullptr; h->cap_fq_reads = 0;
+                                     HIPCHK(h, dmalloc(&h->d_fq_soff, n_reads)); HIPCHK(h, dmalloc(&h->d_fq_qoff, n_reads)); h->cap_fq_reads = n_reads; }
+    u32 wpr = (m.max_len + 15) / 16; if (wpr < 2) wpr = 2; wpr = (wpr + 1) & ~1u;
+    u32 qstride = (m.max_len + 7) & ~7u; if (qstride < 8) qstride = 8;
+    { int rc = ensure_pack_buffers(h, n_reads, wpr, qstride); if (rc) return rc; }
+    {
+        Prof pf(h, 6);
+        hipLaunchKernelGGL(k_fa_reads, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const FaDev*)F.d_desc, n_reads, read_len, stride, h->d_fq_soff, h->d_fq_qoff, h->d_lens);
+        hipLaunchKernelGGL(k_pack_text, dim3(grid_for((n_reads + 63) / 64, 1, 8192)), dim3(256), 0, h->stream, (const u8*)F.d_flat, (const u64*)h->d_fq_soff, (const u64*)h->d_fq_qoff,
+                           h->d_lens, n_reads, h->d_packed, h->d_qrows, wpr, qstride);
+    }
+    HIPCHK(h, hipGetLastError());
+    if (n_reads_out) *n_reads_out = n_reads;
+    h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
+    return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, 0);
+}
+
+// test hook (include/mlst_debug.h): the pack buffers of the last submission made from FASTQ text, from the reads of a BAM or from tiled contigs
 extern "C" int mlst_debug_last_packed(mlst_handle* h, uint32_t* packed, uint64_t cap_words, uint8_t* qrows, uint64_t cap_q, uint16_t* lens, uint64_t cap_reads, uint64_t out[3]) {
     if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }

@@ -68,7 +68,8 @@ class BgzfCrcMismatch(MlstError):
 
 class HostPathNeeded(MlstError):
     """The library's "host path needed: <reason> at record <n>" (mlst_submit_bam_bgzf): the BAM holds a record the device does not
-    treat; the caller runs samin.AlignmentSample on the file, which raises or answers as the reference would."""
+    treat; the caller runs samin.AlignmentSample on the file, which raises or answers as the reference would.  Also "... at byte
+    <n>" (mlst_submit_fasta): a sequence line only Python's strip() treats; the caller tiles the file with fastq.tile_fasta."""
 
 
 class CorruptInput(Exception):
@@ -122,6 +123,7 @@ def load_library(path: str | None = None):
         "mlst_set_reference_cache": (C.c_int, [C.c_char_p]),
         "mlst_submit_reads": (C.c_int, [H, u8p, u8p, u64p, C.c_uint64, C.c_int]),
         "mlst_submit_fastq": (C.c_int, [H, u8p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+        "mlst_submit_fasta": (C.c_int, [H, u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mlst_submit_fastq_bgzf": (C.c_int, [H, u8p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mlst_submit_fastq_bgzf_pair": (C.c_int, [H, u8p, C.c_uint64, u8p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                                   C.POINTER(C.c_uint64)]),
@@ -331,6 +333,35 @@ class Engine:
         self._check(self.lib.mlst_submit_fastq(self._h, _ptr(buf) if buf.size else None, buf.size, int(paired), C.byref(n)), "mlst_submit_fastq")
         return int(n.value)
 
+    def submit_fasta(self, text, read_len: int = 150, stride: int = 25, min_len: int = 50) -> tuple[int, int]:
+        """Pass 1 from FASTA text that holds whole contigs (bytes / bytearray / uint8 array): cut into the reads of
+        fastq.tile_fasta and packed on the GPU (mlst_submit_fasta; the rules: include/mlst.h).  Returns (contigs, reads).
+        HostPathNeeded: a sequence line with white space inside or a CR without its LF; nothing of the call was submitted."""
+        for v in (read_len, stride, min_len):
+            if not 0 <= int(v) < (1 << 32):
+                raise ValueError("read_len, stride and min_len are unsigned 32-bit numbers")
+        buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, np.uint8)
+        nc, nr = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mlst_submit_fasta(self._h, _ptr(buf) if buf.size else None, buf.size, int(read_len), int(stride), int(min_len),
+                                               C.byref(nc), C.byref(nr)), "mlst_submit_fasta")
+        return int(nc.value), int(nr.value)
+
+    def submit_fasta_file(self, path: str, read_len: int = 150, stride: int = 25, min_len: int = 50, chunk_bytes: int = 64 << 20) -> tuple[int, int]:
+        """submit_fasta over a FASTA file in whole-contig chunks (fastq.fasta_chunks: plain files through pooled read buffers; .gz
+        and bgzip'd files are inflated on the host -- a compressed genome is a few dozen BGZF blocks).  Returns (contigs, reads).
+        After HostPathNeeded the chunks before the refused one have been submitted: reset_sample() before the host path."""
+        from .fastq import fasta_chunks, prefetch, release_buffers
+        ring: list = []
+        nc = nr = 0
+        try:
+            for chunk in prefetch(fasta_chunks(path, chunk_bytes, reuse=True, ring=ring)):
+                c, r = self.submit_fasta(chunk, read_len, stride, min_len)      # (returns when the chunk has left the host buffer)
+                nc += c
+                nr += r
+        finally:
+            release_buffers(ring)
+        return nc, nr
+
     def submit_fastq_bgzf(self, data, final: bool, paired: bool = False) -> int:
         """Pass 1 from BGZF-compressed FASTQ: a run of whole BGZF blocks (fastq.bgzf_chunks), inflated and parsed on the GPU.
         final marks the last chunk of the file.  Returns the number of records completed by this chunk."""
@@ -475,7 +506,7 @@ class Engine:
 
     def debug_last_packed(self):
         """Test hook (mlst_debug_last_packed): (packed, qrows, lens, words_per_read, qual_stride) of the last submission made from
-        FASTQ text or from the reads of a BAM, copied from the device."""
+        FASTQ text, from the reads of a BAM or from tiled contigs, copied from the device."""
         out = (C.c_uint64 * 3)()
         self._check(self.lib.mlst_debug_last_packed(self._h, None, 0, None, 0, None, 0, out), "mlst_debug_last_packed")
         n, wpr, qs = (int(x) for x in out)

@@ -557,6 +557,78 @@ class prefetch:
         return x
 
 
+def fasta_chunks(path: str, chunk_bytes: int = 64 << 20, reuse: bool = False, ring: list | None = None):
+    """Yield byte chunks of a FASTA file that each hold whole contigs, for Engine.submit_fasta: a chunk is cut in front of the
+    last '>' that starts a line inside it (the last b"\n>"), and a contig longer than chunk_bytes makes its chunk as long as it
+    needs; the chunks one after the other are the file.  Plain files: positional reads into uint8 arrays (reuse / ring as in
+    text_chunks: pooled, page-locked when set_buffer_allocator says so).  .gz files (bgzip'd ones included) are inflated here on
+    the host and yield bytes: a compressed genome is a few dozen BGZF blocks, not worth a device inflate."""
+    if chunk_bytes < 1:
+        raise ValueError("chunk_bytes must be positive")
+    if path.endswith(".gz"):
+        with _open(path) as f:
+            held = b""
+            while True:
+                piece = f.read(chunk_bytes)
+                if not piece:
+                    break
+                held += piece
+                cut = held.rfind(b"\n>") if len(held) >= chunk_bytes else -1
+                if cut >= 0:
+                    yield held[:cut + 1]
+                    held = held[cut + 1:]
+            if held:
+                yield held
+        return
+    size = os.path.getsize(path)
+    if size == 0:
+        return
+    if ring is None:
+        ring = []
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        pos = 0
+        while pos < size:
+            e = min(pos + chunk_bytes, size)
+            cut = e
+            if e < size:      # the last b"\n>" inside [pos, e): looked for from the back, window by window
+                cut, hi, w = -1, e, 1 << 16
+                while hi > pos + 1:
+                    lo = max(pos, hi - w)
+                    k = os.pread(fd, hi - lo, lo).rfind(b"\n>")
+                    if k >= 0 and lo + k + 1 > pos:
+                        cut = lo + k + 1
+                        break
+                    if lo == pos:
+                        break
+                    hi, w = lo + 1, w * 4      # (one byte of overlap: a b"\n>" across the windows' edge)
+                lo = e - 1
+                while cut < 0:                 # one contig fills the chunk: up to the next header, wherever that is
+                    piece = os.pread(fd, 1 << 20, lo)
+                    k = piece.find(b"\n>")
+                    if k >= 0:
+                        cut = lo + k + 1
+                    elif lo + len(piece) >= size:
+                        cut = size
+                    else:
+                        lo += len(piece) - 1
+            n = cut - pos
+            if reuse and len(ring) >= 4:
+                buf = ring.pop(0)
+                if buf.size < n:
+                    _give_buffer(buf)
+                    buf = _take_buffer(n)
+            else:
+                buf = _take_buffer(n) if reuse else np.empty(n, np.uint8)
+            _pread_into(fd, buf, pos, cut)
+            if reuse:
+                ring.append(buf)
+            yield buf[:n]
+            pos = cut
+    finally:
+        os.close(fd)
+
+
 def tile_fasta(path: str, read_len: int = 150, stride: int = 25, min_len: int = 50, chunk_reads: int = 500_000):
     """Contigs / an assembled genome as input (the modality of the reference's mlst.py, which BLASTs contigs against
     the alleles; BLAST is not in the tree -- here the contigs go through the same alignment path as reads): every
