@@ -79,6 +79,14 @@ int mlst_debug_bam_split(mlst_handle* h, uint32_t force_miss_every, uint64_t* ce
 int mlst_debug_last_packed(mlst_handle* h, uint32_t* packed, uint64_t cap_words, uint8_t* qrows, uint64_t cap_q, uint16_t* lens, uint64_t cap_reads,
                            uint64_t out[3] /* n_reads, wpr, qstride */);
 
+/* Which paths the LAST mlst_submit_fasta call that reached the device took (csrc/fasta_dev.h; tests/test_gpu_fasta_edges.py):
+ * out = { cells of 4,096 bytes of its text (k_fa_state scans 1,024 of them per turn), contigs it counted (k_fa_scan scans 1,024
+ * per turn), entries of the contig tables when the call ended, passes over those tables (2: the tables were too small for the
+ * contigs counted, were grown, and the steps behind the cell scan ran again) }.  Host fields the entry keeps anyway: nothing
+ * is launched, copied or waited for.  MLST_E_INVALID before the first such call (an empty text or one without a header line
+ * does not reach the device). */
+int mlst_debug_fasta_info(mlst_handle* h, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3781,7 +3781,8 @@ struct mlst_handle {
     // contigs tiled on the device (mlst_submit_fasta; csrc/fasta_dev.h): the descriptor and the results on the device, their pinned
     // mirrors (h_fa: FaDev, then FaMeta), the flat sequence, the per-cell and the per-contig tables
     struct { FaDev* d_desc = nullptr; FaMeta* d_meta = nullptr; u8* h_fa = nullptr; u8* d_flat = nullptr; u64 cap_flat = 0;
-             u32* d_kind = nullptr; u64* d_cseq = nullptr; u64* d_chdr = nullptr; u64 cap_cells = 0; u64* d_cstart = nullptr; u64* d_wcnt = nullptr; u64 cap_contigs = 0; } fa;
+             u32* d_kind = nullptr; u64* d_cseq = nullptr; u64* d_chdr = nullptr; u64 cap_cells = 0; u64* d_cstart = nullptr; u64* d_wcnt = nullptr; u64 cap_contigs = 0;
+             u64 last_cells = 0, last_contigs = 0; u32 last_passes = 0; } fa;      // (last_*: mlst_debug_fasta_info; last_passes = 0: no call has reached the device)
 };
 
 static std::string g_create_err;
@@ -6291,6 +6292,7 @@ extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n
         HIPCHK(h, hipMemcpyAsync(F.h_fa + sizeof(FaDev), F.d_meta, sizeof(FaMeta), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));      // the one host synchronisation of a call
         memcpy(&m, F.h_fa + sizeof(FaDev), sizeof m);
+        F.last_cells = n_cells; F.last_contigs = m.n_contigs; F.last_passes = (u32)turn + 1;
         if (m.err_key != ~0ull || m.n_contigs <= F.cap_contigs) break;
         if (turn) return fail(h, MLST_E_HIP, "FASTA contig table inconsistent");
         want_contigs = m.n_contigs;
@@ -6319,6 +6321,15 @@ extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n
     if (n_reads_out) *n_reads_out = n_reads;
     h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
     return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, 0);
+}
+
+// test hook (include/mlst_debug.h): which paths the last mlst_submit_fasta call took (fields the entry keeps anyway; nothing is launched or copied)
+extern "C" int mlst_debug_fasta_info(mlst_handle* h, uint64_t out[4]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    const auto& F = h->fa;
+    if (!F.last_passes) return fail(h, MLST_E_INVALID, "no mlst_submit_fasta call has reached the device");
+    out[0] = F.last_cells; out[1] = F.last_contigs; out[2] = F.cap_contigs; out[3] = F.last_passes;
+    return MLST_OK;
 }
 
 // test hook (include/mlst_debug.h): the pack buffers of the last submission made from FASTQ text, from the reads of a BAM or from tiled contigs

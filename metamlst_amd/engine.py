@@ -195,6 +195,7 @@ def load_library(path: str | None = None):
         "mlst_bam_reads_open": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_int]),
         "mlst_bam_reads_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_debug_last_packed": (C.c_int, [H, u32p, C.c_uint64, u8p, C.c_uint64, u16p, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "mlst_debug_fasta_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_synchronize": (C.c_int, [H]),
     }
     tolerant = bool(os.environ.get("MLST_LIB_ALLOW_MISSING"))      # A/B runs against an older build (profiles/ab.sh)
@@ -515,6 +516,13 @@ class Engine:
             self._check(self.lib.mlst_debug_last_packed(self._h, _ptr(packed), packed.size, _ptr(qrows), qrows.size, _ptr(lens), lens.size, out),
                         "mlst_debug_last_packed")
         return packed, qrows, lens, wpr, qs
+
+    def fasta_info(self) -> tuple[int, int, int, int]:
+        """Test hook (mlst_debug_fasta_info): (cells, contigs, entries of the contig tables, passes over them: 1 or 2) of the last
+        submit_fasta call that reached the device."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.mlst_debug_fasta_info(self._h, out), "mlst_debug_fasta_info")
+        return tuple(int(x) for x in out)
 
     def bam_set_capacity(self, max_entries: int) -> None:
         self._check(self.lib.mlst_bam_set_capacity(self._h, int(max_entries)), "mlst_bam_set_capacity")

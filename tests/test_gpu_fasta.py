@@ -11,6 +11,7 @@ import pytest
 
 import fasta_zoo as fz
 import fixtures as fx
+from fasta_edges import assert_rows_equal
 from metamlst_amd import synth
 from metamlst_amd.fastq import fasta_chunks, tile_fasta
 
@@ -39,25 +40,6 @@ def typed(eng):
     eng.typing_enqueue()
     _, chosen, letters = eng.typing_fetch()
     return st, chosen, letters
-
-
-def assert_rows_equal(eng, path, tile, n_want=None):
-    from metamlst_amd.engine import pack_fastq_host
-    text = b"".join(tile_fasta(path, *tile))
-    n_rec = text.count(b"\n") // 4
-    eng.reset_sample()
-    n_contigs, n_reads = eng.submit_fasta(open(path, "rb").read(), *tile)
-    assert n_reads == n_rec and (n_want is None or n_reads == n_want)
-    assert n_contigs == (b"\n" + open(path, "rb").read()).count(b"\n>")
-    packed, qrows, lens, wpr, qs = eng.debug_last_packed()
-    longest = max(len(l) for l in text.split(b"\n")[1::4])
-    h_packed, h_qrows, h_lens, n, h_wpr, h_qs = pack_fastq_host(text, read_len_max=longest)
-    assert (n, h_wpr, h_qs) == (n_reads, wpr, qs) and lens.size == n
-    assert np.array_equal(lens, h_lens[:n]), np.nonzero(lens != h_lens[:n])[0][:10]
-    assert np.array_equal(qrows, h_qrows[:n]), np.unique(np.nonzero(qrows != h_qrows[:n])[0])[:10]
-    assert packed.size == ((n + 63) // 64) * 64 * wpr
-    assert np.array_equal(packed, h_packed[:packed.size]), np.nonzero(packed != h_packed[:packed.size])[0][:10]
-    assert int(eng.stats().counters[2]) == n_reads
 
 
 # ------------------------------------------------------------------ 1. rows
