@@ -19,6 +19,7 @@
 // flagged and left to inflate_wave.h's kernel.  Errors: the codes of inflate_dev.h; every loop is bounded as there.
 #pragma once
 #include "inflate_dev.h"
+#include "bgzf_host.h"      // inflate_lane::Blk, the block record (defined there so that the host-side lister compiles without device code)
 
 namespace inflate_lane {
 
@@ -27,7 +28,9 @@ typedef unsigned int u32;
 typedef unsigned short u16;
 typedef unsigned char u8;
 
-struct Blk { u64 in_off, out_off; u32 in_len, out_len; };      // one BGZF block: its deflate stream in the compressed buffer, its text in the output
+// Blk { u64 in_off, out_off; u32 in_len, out_len; } -- one BGZF block: its deflate stream in the compressed buffer, its text in the output (bgzf_host.h)
+static_assert(sizeof(Blk) == 24 && offsetof(Blk, in_off) == 0 && offsetof(Blk, out_off) == 8 && offsetof(Blk, in_len) == 16 && offsetof(Blk, out_len) == 20,
+              "the kernels read the block record as two 64-bit offsets and two 32-bit lengths");
 enum : u32 { TAG_LIT = 0u, TAG_RAW = 1u, TAG_MATCH = 2u, TAG_OPERAND = 3u, TOK_OVERFLOW = 0xFFFFFFFFu };
 enum : u32 { LIT_BASE = 0xFF00u };      // phase 2: a 16-bit pointer >= LIT_BASE is a literal, its byte in the low 8 bits
 // token (tag in bits 30-31): literal = the byte; match = (length - 3) << 16 | (distance - 1); stored run = its length (16 bits),

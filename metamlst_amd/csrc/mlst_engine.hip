@@ -30,6 +30,7 @@
 
 #include "mlst.h"
 #include "mlst_debug.h"
+#include "bgzf_host.h"      // BgzfBlk, bgzf_list: BGZF framing on the host
 #include "inflate_dev.h"
 #include "inflate_wave.h"
 #include "inflate_lane.h"
@@ -1345,7 +1346,7 @@ __global__ __launch_bounds__(1024) void k_flag_compact(u32* __restrict__ flags, 
 }
 
 // ------------------------------------------------------------------ BGZF -> text (one wave per <= 64 KiB deflate block)
-typedef inflate_lane::Blk BgzfBlk;      // { u64 in_off, out_off; u32 in_len, out_len; }
+// BgzfBlk (csrc/bgzf_host.h) = inflate_lane::Blk { u64 in_off, out_off; u32 in_len, out_len; }
 #if !defined(MLST_INFLATE_GROUP)
 #define MLST_INFLATE_GROUP 64
 #endif
@@ -3727,7 +3728,8 @@ struct mlst_handle {
     // of piece k (infl_stream) and the parse + pass 1 of piece k - 1 (the engine's stream) run side by side.  Two slots of
     // compressed bytes / block descriptors / error words used in turn; `bz_pend` is the piece whose text is being inflated
     // (or has been) and has not been parsed yet.
-    struct BzSlot { void* d_blk = nullptr; void* h_blk = nullptr; u64 cap_blk = 0; hipEvent_t ev_copied = nullptr, ev_inflated = nullptr; u32* d_err = nullptr; u32* h_err = nullptr; };
+    struct BlkList { BgzfBlk* d = nullptr; BgzfBlk* h = nullptr; u64 cap = 0; };      // a piece's block list on the device, and the page-locked buffer it travels through (blk_upload)
+    struct BzSlot { BlkList blk; hipEvent_t ev_copied = nullptr, ev_inflated = nullptr; u32* d_err = nullptr; u32* h_err = nullptr; };
     BzSlot bz[2]; int bz_slot = 0, bz_mode = -1; hipStream_t infl_stream = nullptr;
     // mlst_set_bgzf_verify (MLST_BGZF_CRC sets it for a new handle): k_bgzf_crc behind the decoders of every launch_inflate.
     // crc_hook (mlst_selftest_bgzf_crc, for the duration of its launch): the values instead of the comparison, and the kernel's two events
@@ -5006,11 +5008,15 @@ static void launch_bgzf_crc(mlst_handle* h, const u8* d_comp, const BgzfBlk* d_b
     hipLaunchKernelGGL(k_bgzf_crc, dim3(std::min((n_blk + 3u) / 4u, 2048u)), dim3(256), 0, st, d_comp, d_blk, n_blk, d_out, d_err, h->crc_hook.d_out);
     if (h->crc_hook.e1) hipEventRecord(h->crc_hook.e1, st);
 }
+static int inflate_mode(mlst_handle* h) {      // MLST_INFLATE_MODE, read once per handle
+    if (!h->inflate_mode) { const char* e = getenv("MLST_INFLATE_MODE"); h->inflate_mode = e ? atoi(e) : 2; if (h->inflate_mode != 1 && h->inflate_mode != 2) h->inflate_mode = 2; }
+    return h->inflate_mode;
+}
+static bool inflate_counted(mlst_handle* h) { return inflate_mode(h) == 2 && !getenv("MLST_BGZF_NOCOUNT"); }      // the two-kernel inflate counts the newlines of the text it writes
 static int launch_inflate(mlst_handle* h, const u8* d_comp, u64 comp_bytes_padded, const BgzfBlk* d_blk, u32 n_blk, u8* d_out, u32* d_err, unsigned long long* d_st, hipStream_t st = nullptr, u32* d_nl = nullptr) {
     if (n_blk == 0) return MLST_OK;
     if (!st) st = h->stream;
-    if (!h->inflate_mode) { const char* e = getenv("MLST_INFLATE_MODE"); h->inflate_mode = e ? atoi(e) : 2; if (h->inflate_mode != 1 && h->inflate_mode != 2) h->inflate_mode = 2; }
-    if (h->inflate_mode == 1 || d_st) {
+    if (inflate_mode(h) == 1 || d_st) {
         if (d_nl) return fail(h, MLST_E_INVALID, "newline counts come with the two-kernel inflate only");
         hipLaunchKernelGGL(k_inflate, dim3((u32)std::min<u64>(((u64)n_blk + INFLATE_NG - 1) / INFLATE_NG, 1u << 20)), dim3(64), 0, st, d_comp, comp_bytes_padded, d_blk, n_blk, d_out, d_err, d_st, (const u32*)nullptr, 0u);
         launch_bgzf_crc(h, d_comp, d_blk, n_blk, d_out, d_err, st);
@@ -5116,96 +5122,13 @@ extern "C" int mlst_submit_fastq_pair(mlst_handle* h, const uint8_t* text1, uint
     return fastq_pipeline(h, total, 1, true, n_reads_out, n1 + pad);
 }
 
-struct BzHdr { u64 off; u32 total, coff, clen, isize; };      // one BGZF block of a chunk: where it starts, its size, where its deflate data lies, the bytes it inflates to
-// BGZF framing (SAM spec 4.1): gzip member with an extra subfield 'B','C' holding the block size - 1; deflate data; CRC32, ISIZE
-static bool bgzf_block(const u8* p, u64 left, u64& total, u64& cdata_off, u64& cdata_len, u32& isize) {
-    if (left < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return false;
-    const u32 xlen = (u32)p[10] | ((u32)p[11] << 8);
-    if (left < 12ull + xlen) return false;
-    u32 bsize = 0; bool found = false;
-    for (u32 o = 0; o + 4 <= xlen; ) {
-        const u8* sf = p + 12 + o; const u32 slen = (u32)sf[2] | ((u32)sf[3] << 8);
-        if (sf[0] == 'B' && sf[1] == 'C' && slen == 2 && o + 6 <= xlen) { bsize = (u32)sf[4] | ((u32)sf[5] << 8); found = true; }
-        o += 4 + slen;
-    }
-    if (!found) return false;
-    total = (u64)bsize + 1;
-    if (total > left || total < 12ull + xlen + 8) return false;
-    cdata_off = 12ull + xlen; cdata_len = total - cdata_off - 8;
-    isize = (u32)p[total - 4] | ((u32)p[total - 3] << 8) | ((u32)p[total - 2] << 16) | ((u32)p[total - 1] << 24);
-    return true;
-}
-
-// The walk over a chunk's block headers is a chain of cache (and TLB) misses, ~190 ns per block (the next header's place is in this
-// one): a chunk of 32 MB or more is walked by four threads, each from a block start it FINDS behind its quarter mark (the header's
-// fixed bytes, parsed, and the block behind it parsed too); a list is taken only where the chain of the list before it lands exactly
-// on its first block -- so a false start (header bytes inside deflate data) costs the time, never the result -- and the caller's
-// serial loop goes on from `walked`, where the accepted lists end (all errors are its).  lists_taken: how many of the four counted.
-static void bgzf_walk_parallel(const u8* data, u64 n_bytes, std::vector<BzHdr>& hdr, u64& walked, int* lists_taken) {
-    hdr.clear(); walked = 0; if (lists_taken) *lists_taken = 0;
-    static const bool one = [] { const char* e = getenv("MLST_BGZF_WALK"); return e && e[0] == '1'; }();      // MLST_BGZF_WALK=1: the serial walk (A/B)
-    if (n_bytes < (32ull << 20) || one) return;
-    enum { WT = 4 };
-    std::vector<BzHdr> part[WT]; u64 stop[WT] = {0}, cand[WT] = {0}; bool have[WT] = {false};
-    auto work = [&](int k) {
-        u64 from = 0;
-        if (k) {
-            const u64 s0 = n_bytes * (u64)k / WT, s1 = std::min<u64>(s0 + 131072, n_bytes - 18);
-            bool ok = false;
-            for (u64 q = s0; q < s1 && !ok; q++) {
-                if (data[q] != 0x1f || data[q + 1] != 0x8b || data[q + 2] != 8 || !(data[q + 3] & 4)) continue;
-                u64 t, co, cl; u32 is;
-                if (!bgzf_block(data + q, n_bytes - q, t, co, cl, is)) continue;
-                u64 t2, co2, cl2; u32 is2;
-                if (q + t != n_bytes && !bgzf_block(data + q + t, n_bytes - q - t, t2, co2, cl2, is2)) continue;
-                from = q; ok = true;
-            }
-            if (!ok) return;
-            cand[k] = from; have[k] = true;
-        }
-        const u64 limit = k + 1 < WT ? std::min<u64>(n_bytes * (u64)(k + 1) / WT + 262144, n_bytes) : n_bytes;
-        part[k].reserve((size_t)((limit - from) / 8192 + 64));
-        u64 off = from;
-        while (off < limit) {
-            u64 t, co, cl; u32 is;
-            if (!bgzf_block(data + off, n_bytes - off, t, co, cl, is)) break;
-            part[k].push_back(BzHdr{off, (u32)t, (u32)co, (u32)cl, is});
-            off += t;
-        }
-        stop[k] = off;
-    };
-    std::thread th[WT - 1];
-    for (int k = 1; k < WT; k++) th[k - 1] = std::thread(work, k);
-    work(0);
-    for (auto& t : th) t.join();
-    hdr.swap(part[0]); walked = stop[0];
-    int taken = 1;
-    for (int k = 1; k < WT; k++) {
-        if (!have[k]) break;
-        size_t i = hdr.size();
-        while (i > 0 && hdr[i - 1].off > cand[k]) i--;
-        if (i == 0 || hdr[i - 1].off != cand[k]) break;      // the chain does not pass through the start this thread found: its list is dropped, and those behind it
-        hdr.resize(i - 1);
-        hdr.insert(hdr.end(), part[k].begin(), part[k].end());
-        walked = stop[k]; taken++;
-    }
-    if (lists_taken) *lists_taken = taken;
-}
-// test hook (include/mlst_debug.h): the blocks of a chunk as mlst_submit_fastq_bgzf lists them -- count, text bytes, how many of the four threads' lists counted
+// test hook (include/mlst_debug.h): the blocks of a chunk as bgzf_list (csrc/bgzf_host.h: BGZF framing, the four-thread walk, the lister
+// of every entry below) lists them for mlst_submit_fastq_bgzf -- count, text bytes, how many of the four threads' lists counted
 extern "C" int mlst_debug_bgzf_walk(const uint8_t* data, uint64_t n_bytes, uint64_t* n_blocks, uint64_t* text_bytes, int* lists_taken) {
     if (!data || !n_blocks || !text_bytes) return MLST_E_INVALID;
-    std::vector<BzHdr> hdr; u64 walked = 0;
-    bgzf_walk_parallel(data, n_bytes, hdr, walked, lists_taken);
-    u64 nb = 0, tb = 0; size_t hi_ = 0;
-    for (u64 off = 0; off < n_bytes; ) {
-        u64 total, coff, clen; u32 isize;
-        if (hi_ < hdr.size()) { const BzHdr& q = hdr[hi_++]; off = q.off; total = q.total; isize = q.isize; }
-        else if (off < walked) { off = walked; continue; }
-        else if (!bgzf_block(data + off, n_bytes - off, total, coff, clen, isize)) return MLST_E_INVALID;
-        if (isize) { nb++; tb += isize; }
-        off += total;
-    }
-    *n_blocks = nb; *text_bytes = tb;
+    std::vector<BgzfBlk> blks; BgzfList L;
+    if (bgzf_list(data, n_bytes, false, true, blks, L, nullptr, lists_taken) != BGZF_LIST_OK) return MLST_E_INVALID;
+    *n_blocks = blks.size(); *text_bytes = L.text;
     return MLST_OK;
 }
 
@@ -5256,7 +5179,7 @@ static int bz_flush(mlst_handle* h) {
 static void bz_free(mlst_handle* h) {
     if (h->infl_stream) hipStreamSynchronize(h->infl_stream);
     for (auto& B : h->bz) {
-        hipFree(B.d_blk); hipFree(B.d_err); if (B.h_err) hipHostFree(B.h_err); if (B.h_blk) hipHostFree(B.h_blk);
+        hipFree(B.blk.d); hipFree(B.d_err); if (B.h_err) hipHostFree(B.h_err); if (B.blk.h) hipHostFree(B.blk.h);
         if (B.ev_copied) hipEventDestroy(B.ev_copied); if (B.ev_inflated) hipEventDestroy(B.ev_inflated);
         B = mlst_handle::BzSlot();
     }
@@ -5277,52 +5200,75 @@ static int bz_stream(mlst_handle* h) {
     HIPCHK(h, hipStreamCreateWithFlags(&h->infl_stream, hipStreamNonBlocking));
     return MLST_OK;
 }
+// a slot's first use: its events and error words
+static int bz_slot_init(mlst_handle* h, mlst_handle::BzSlot& B) {
+    if (B.ev_copied) return MLST_OK;
+    HIPCHK(h, hipEventCreateWithFlags(&B.ev_copied, hipEventDisableTiming)); HIPCHK(h, hipEventCreateWithFlags(&B.ev_inflated, hipEventDisableTiming));
+    HIPCHK(h, dmalloc(&B.d_err, (u64)16)); HIPCHK(h, hipHostMalloc((void**)&B.h_err, 64, hipHostMallocDefault));
+    return MLST_OK;
+}
+// A block list onto the device, on stream st in front of the kernels that read it.  Through page-locked memory: a copy from the
+// vector's pageable memory is staged by the runtime on the calling thread.  (The buffers' last user has been finished: its inflate is over.)
+static int blk_upload(mlst_handle* h, mlst_handle::BlkList& L, const std::vector<BgzfBlk>& blks, hipStream_t st) {
+    if (L.cap < blks.size()) {
+        hipFree(L.d); L.d = nullptr; if (L.h) { hipHostFree(L.h); L.h = nullptr; } L.cap = 0;
+        const u64 cap = blks.size() + blks.size() / 8 + 16;
+        HIPCHK(h, dmalloc(&L.d, cap)); HIPCHK(h, hipHostMalloc((void**)&L.h, cap * sizeof(BgzfBlk), hipHostMallocDefault)); L.cap = cap;
+    }
+    if (blks.empty()) return MLST_OK;
+    memcpy(L.h, blks.data(), blks.size() * sizeof(BgzfBlk));
+    HIPCHK(h, hipMemcpyAsync(L.d, L.h, blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice, st));
+    return MLST_OK;
+}
+// The next of the two chunk buffers, grown to n bytes, with stream cs (the one that copies into it) ordered behind its last reader
+static int bz_chunk_take(mlst_handle* h, u64 n, hipStream_t cs, mlst_handle::BzChunk*& C) {
+    C = &h->bzc[h->bz_chunk ^= 1];
+    if (!C->ev_used) { HIPCHK(h, hipEventCreateWithFlags(&C->ev_used, hipEventDisableTiming)); for (auto& e : C->ev) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
+    if (C->cap < n) {
+        if (C->used) HIPCHK(h, hipEventSynchronize(C->ev_used));
+        hipFree(C->d); C->d = nullptr; C->cap = 0;
+        HIPCHK(h, dmalloc(&C->d, n + n / 8 + 32)); C->cap = n + n / 8;
+    }
+    if (C->used) HIPCHK(h, hipStreamWaitEvent(cs, C->ev_used, 0));      // the buffer's last reader (the chunk before the last: finished long ago, unless a sample was dropped half way)
+    return MLST_OK;
+}
+// an error return leaves a copy out of the caller's buffer running: the buffer is read until stream s is idle -- waited for here
+struct CopyGuard { hipStream_t s; bool on; ~CopyGuard() { if (on && s) hipStreamSynchronize(s); } };
+// MLST_BGZF_TRACE: host-side time stamps of a call's and a piece's steps (stderr)
+static bool bz_trace() { static const bool on = getenv("MLST_BGZF_TRACE") != nullptr; return on; }
+static double bz_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // One piece through the three stages: its copy and inflate are queued, the piece before it is finished meanwhile (and, for the last
 // piece of a stream, the piece itself).  blks: the piece's blocks, in_off relative to `data`, out_off from FQ_HEAD on.
 static int bz_piece(mlst_handle* h, mlst_handle::BzChunk& C, u64 lo, u64 hi, const std::vector<BgzfBlk>& blks, u32 blk_base, u64 text_end, int paired, bool final_piece, uint64_t* done) {
-    static const bool bz_trace = getenv("MLST_BGZF_TRACE") != nullptr;      // host-side time stamps of a piece's steps (stderr)
-    auto bz_now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double bt0 = bz_trace ? bz_now() : 0.0;
+    const double bt0 = bz_trace() ? bz_now() : 0.0;
     uint64_t n1 = 0;
     const int sl = h->bz_slot ^= 1;
     mlst_handle::BzSlot& B = h->bz[sl];
-    if (!B.ev_copied) { HIPCHK(h, hipEventCreateWithFlags(&B.ev_copied, hipEventDisableTiming)); HIPCHK(h, hipEventCreateWithFlags(&B.ev_inflated, hipEventDisableTiming));
-                        HIPCHK(h, dmalloc(&B.d_err, (u64)16)); HIPCHK(h, hipHostMalloc((void**)&B.h_err, 64, hipHostMallocDefault)); }
-    // (the slot's last user, piece k - 2, has been finished: its inflate is over)
-    if (B.cap_blk < blks.size()) {
-        hipFree(B.d_blk); B.d_blk = nullptr; if (B.h_blk) { hipHostFree(B.h_blk); B.h_blk = nullptr; }
-        const u64 cap = blks.size() + blks.size() / 8;
-        BgzfBlk* pb = nullptr; HIPCHK(h, dmalloc(&pb, cap)); B.d_blk = pb;
-        HIPCHK(h, hipHostMalloc(&B.h_blk, cap * sizeof(BgzfBlk), hipHostMallocDefault));
-        B.cap_blk = cap;
-    }
-    { int rc = next_text_slot(h, text_end + text_end / 16); if (rc) return rc; }
+    { int rc = bz_slot_init(h, B); if (!rc) rc = next_text_slot(h, text_end + text_end / 16); if (rc) return rc; }
     const int tslot = h->fq_slot;
-    // (the block list through page-locked memory: a copy from the vector's pageable memory is staged by the runtime on the calling
-    // thread; and on the INFLATE stream, in front of the kernels that read it -- the copy stream is busy with the chunk's bytes)
-    memcpy(B.h_blk, blks.data(), blks.size() * sizeof(BgzfBlk));
-    HIPCHK(h, hipMemcpyAsync(B.d_blk, B.h_blk, blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice, h->infl_stream));
+    // (the slot's last user, piece k - 2, has been finished: its inflate is over.  The block list goes on the INFLATE stream, in
+    // front of the kernels that read it -- the copy stream is busy with the chunk's bytes)
+    { int rc = blk_upload(h, B.blk, blks, h->infl_stream); if (rc) return rc; }
     { int k = 0; while (k + 1 < C.n_ev && C.upto[k] < hi) k++;                // the part of the chunk's copy that holds the piece's last byte (parts are queued in order)
       HIPCHK(h, hipStreamWaitEvent(h->infl_stream, C.ev[k], 0)); }
     HIPCHK(h, hipStreamWaitEvent(h->infl_stream, h->ev_packed[tslot], 0));      // the text slot's last reader (an event never recorded counts as complete)
     HIPCHK(h, hipMemsetAsync(B.d_err, 0, 64, h->infl_stream));
-    if (!h->inflate_mode) { const char* e = getenv("MLST_INFLATE_MODE"); h->inflate_mode = e ? atoi(e) : 2; if (h->inflate_mode != 1 && h->inflate_mode != 2) h->inflate_mode = 2; }
-    const bool counted = h->inflate_mode == 2 && !getenv("MLST_BGZF_NOCOUNT");      // the two-kernel inflate counts the newlines of the text it writes
+    const bool counted = inflate_counted(h);
     if (counted) HIPCHK(h, hipMemsetAsync(h->d_fq_nl[tslot], 0, (text_end / FQ_BLOCK + 2) * 4, h->infl_stream));
-    { int rc = launch_inflate(h, C.d + lo, C.cap + 16 - lo, (const BgzfBlk*)B.d_blk, (u32)blks.size(), h->d_fq_slot[tslot], B.d_err, nullptr, h->infl_stream,
+    { int rc = launch_inflate(h, C.d + lo, C.cap + 16 - lo, B.blk.d, (u32)blks.size(), h->d_fq_slot[tslot], B.d_err, nullptr, h->infl_stream,
                               counted ? h->d_fq_nl[tslot] : nullptr); if (rc) return rc; }
     HIPCHK(h, hipMemcpyAsync(B.h_err, B.d_err, h->bgzf_verify ? 16 : 8, hipMemcpyDeviceToHost, h->infl_stream));
     HIPCHK(h, hipEventRecord(B.ev_inflated, h->infl_stream));
     HIPCHK(h, hipEventRecord(C.ev_used, h->infl_stream)); C.used = true;
     // piece k - 1 while the GPU inflates piece k
     int rc = MLST_OK;
-    const double bt1 = bz_trace ? bz_now() : 0.0;
+    const double bt1 = bz_trace() ? bz_now() : 0.0;
     if (h->bz_pend.on) { rc = bz_finish(h, false, &n1); *done += n1; }
-    const double bt2 = bz_trace ? bz_now() : 0.0;
+    const double bt2 = bz_trace() ? bz_now() : 0.0;
     h->bz_pend.on = true; h->bz_pend.counted = counted; h->bz_pend.slot = sl; h->bz_pend.tslot = tslot; h->bz_pend.paired = paired; h->bz_pend.text_bytes = text_end - FQ_HEAD; h->bz_pend.blk_base = blk_base;
     if (!rc && final_piece) { rc = bz_finish(h, true, &n1); *done += n1; }
-    if (bz_trace) fprintf(stderr, "bgzf piece of %zu blocks at %.3f: queueing %.3f ms, piece before %.3f ms, own piece (final) %.3f ms\n",
+    if (bz_trace()) fprintf(stderr, "bgzf piece of %zu blocks at %.3f: queueing %.3f ms, piece before %.3f ms, own piece (final) %.3f ms\n",
                           blks.size(), bt0, bt1 - bt0, bt2 - bt1, bz_now() - bt2);
     if (rc) { if (h->infl_stream) hipStreamSynchronize(h->infl_stream); h->bz_pend.on = false; return rc; }
     return MLST_OK;
@@ -5339,23 +5285,14 @@ extern "C" int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint6
     if (n_bytes >= (1ull << 36)) return fail(h, MLST_E_LIMIT, "BGZF chunk too large");
     hipSetDevice(h->device);
     const bool piped = bz_mode(h) != 0;
-    static const bool bz_trace = getenv("MLST_BGZF_TRACE") != nullptr;
-    auto bz_now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double ct0 = bz_trace ? bz_now() : 0.0;
+    const double ct0 = bz_trace() ? bz_now() : 0.0;
     // (piped) the chunk's bytes are on their way before its block headers are looked at: the walk below is a chain of cache misses,
     // one per block (the next header's place is in this one), 8 ms for 49,152 blocks -- time the inflate stream sat idle for
     mlst_handle::BzChunk* C = nullptr;
     if (piped && n_bytes) {
         { int rc = bz_stream(h); if (rc) return rc; }
         if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        C = &h->bzc[h->bz_chunk ^= 1];
-        if (!C->ev_used) { HIPCHK(h, hipEventCreateWithFlags(&C->ev_used, hipEventDisableTiming)); for (auto& e : C->ev) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
-        if (C->cap < n_bytes) {
-            if (C->used) HIPCHK(h, hipEventSynchronize(C->ev_used));
-            hipFree(C->d); C->d = nullptr; C->cap = 0;
-            HIPCHK(h, dmalloc(&C->d, n_bytes + n_bytes / 8 + 32)); C->cap = n_bytes + n_bytes / 8;
-        }
-        if (C->used) HIPCHK(h, hipStreamWaitEvent(h->copy_stream, C->ev_used, 0));      // the buffer's last reader (the chunk before the last: finished long ago, unless a sample was dropped half way)
+        { int rc = bz_chunk_take(h, n_bytes, h->copy_stream, C); if (rc) return rc; }
         const int n_sub = n_bytes >= (64ull << 20) ? (int)mlst_handle::BZ_SUB : 1;
         u64 at = 0;
         for (int k = 0; k < n_sub; k++) {
@@ -5366,29 +5303,17 @@ extern "C" int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint6
         }
         C->n_ev = n_sub;
     }
-    // (an error return below leaves the copy running: the caller's buffer is read until the copy stream is idle -- waited for here)
-    struct CopyGuard { mlst_handle* h; bool on; ~CopyGuard() { if (on && h->copy_stream) hipStreamSynchronize(h->copy_stream); } } copy_guard{h, C != nullptr};
-    std::vector<BgzfBlk> blks;
+    CopyGuard copy_guard{h->copy_stream, C != nullptr};      // (an error return below leaves the copy running)
+    std::vector<BgzfBlk> blks; BgzfList L;
     std::vector<u64> blk_start;                                   // (piped) where every listed block begins in `data`
     const u64 text_at = piped ? FQ_HEAD : h->fq_carry_len;      // where the first block's text goes in its slot
-    u64 text_bytes = text_at;
-    std::vector<BzHdr> hdr; u64 walked = 0;
-    bgzf_walk_parallel(data, n_bytes, hdr, walked, nullptr);
-    size_t hi_ = 0;      // (headers of `hdr` first, then block by block from `walked`)
-    for (u64 off = 0; off < n_bytes; ) {
-        u64 total, coff, clen; u32 isize;
-        if (hi_ < hdr.size()) { const BzHdr& q = hdr[hi_++]; off = q.off; total = q.total; coff = q.coff; clen = q.clen; isize = q.isize; }
-        else if (off < walked) { off = walked; continue; }
-        else if (!bgzf_block(data + off, n_bytes - off, total, coff, clen, isize)) {
-            // a block cut off by the end of the buffer is left to the caller when it asked how much was taken (and more is to come)
-            const bool cut = n_bytes - off < 18 || (data[off] == 0x1f && data[off + 1] == 0x8b && data[off + 2] == 8 && (data[off + 3] & 4));
-            if (n_consumed_out && !final_chunk && cut) { n_bytes = off; break; }
-            return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu of the chunk", (unsigned long long)off);
-        }
-        if (isize > 65536) return fail(h, MLST_E_INVALID, "BGZF block at byte %llu claims %u bytes of data", (unsigned long long)off, isize);
-        if (isize) { BgzfBlk b; b.in_off = off + coff; b.in_len = (u32)clen; b.out_off = text_bytes; b.out_len = isize; blks.push_back(b); if (piped) blk_start.push_back(off); text_bytes += isize; }
-        off += total;
-    }
+    // a block cut off by the end of the buffer is left to the caller when it asked how much was taken (and more is to come)
+    const BgzfListRc lrc = bgzf_list(data, n_bytes, n_consumed_out && !final_chunk, true, blks, L, piped ? &blk_start : nullptr);
+    if (lrc == BGZF_LIST_NOT_WHOLE) return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu of the chunk", (unsigned long long)L.bad_off);
+    if (lrc == BGZF_LIST_CLAIMS) return fail(h, MLST_E_INVALID, "BGZF block at byte %llu claims %u bytes of data", (unsigned long long)L.bad_off, L.bad_isize);
+    n_bytes = L.taken;
+    for (auto& q : blks) q.out_off += text_at;
+    const u64 text_bytes = text_at + L.text;
     if (text_bytes >= (1ull << 40)) return fail(h, MLST_E_LIMIT, "FASTQ chunk too large");
     if (n_consumed_out) *n_consumed_out = n_bytes;
     if (!h->d_fq_meta) HIPCHK(h, dmalloc(&h->d_fq_meta, (u64)4));
@@ -5431,10 +5356,10 @@ extern "C" int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint6
             if (rc) return rc;
         }
         if (n_reads_out) *n_reads_out = done;
-        const double ct1 = bz_trace ? bz_now() : 0.0;
+        const double ct1 = bz_trace() ? bz_now() : 0.0;
         copy_guard.on = false;
         HIPCHK(h, hipStreamSynchronize(h->copy_stream));      // `data` may be released by the caller after this
-        if (bz_trace) fprintf(stderr, "bgzf chunk of %zu blocks at %.3f: %.3f ms in the call, of which %.3f ms waiting for the copy at its end\n", nb, ct0, bz_now() - ct0, bz_now() - ct1);
+        if (bz_trace()) fprintf(stderr, "bgzf chunk of %zu blocks at %.3f: %.3f ms in the call, of which %.3f ms waiting for the copy at its end\n", nb, ct0, bz_now() - ct0, bz_now() - ct1);
         return MLST_OK;
     }
     if (text_bytes == 0) return MLST_OK;
@@ -5562,23 +5487,12 @@ static int bzp_finish(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
 // the whole BGZF blocks of one file's buffer -> blks (in_off + in_base, out_off from 0 on in the file's region); n_bytes is cut back
 // to the last whole block when may_cut (a non-final buffer whose caller asked how much was taken)
 static int bzp_list(mlst_handle* h, const u8* data, u64& n_bytes, bool may_cut, u64 in_base, int file, std::vector<BgzfBlk>& blks, u64& text) {
-    text = 0;
-    std::vector<BzHdr> hdr; u64 walked = 0;
-    bgzf_walk_parallel(data, n_bytes, hdr, walked, nullptr);
-    size_t hi_ = 0;
-    for (u64 off = 0; off < n_bytes; ) {
-        u64 total, coff, clen; u32 isize;
-        if (hi_ < hdr.size()) { const BzHdr& q = hdr[hi_++]; off = q.off; total = q.total; coff = q.coff; clen = q.clen; isize = q.isize; }
-        else if (off < walked) { off = walked; continue; }
-        else if (!bgzf_block(data + off, n_bytes - off, total, coff, clen, isize)) {
-            const bool cut = n_bytes - off < 18 || (data[off] == 0x1f && data[off + 1] == 0x8b && data[off + 2] == 8 && (data[off + 3] & 4));
-            if (may_cut && cut) { n_bytes = off; break; }
-            return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu of file %d in the chunk", (unsigned long long)off, file);
-        }
-        if (isize > 65536) return fail(h, MLST_E_INVALID, "BGZF block at byte %llu of file %d claims %u bytes of data", (unsigned long long)off, file, isize);
-        if (isize) { BgzfBlk b; b.in_off = in_base + off + coff; b.in_len = (u32)clen; b.out_off = text; b.out_len = isize; blks.push_back(b); text += isize; }
-        off += total;
-    }
+    const size_t b0 = blks.size(); BgzfList L;
+    const BgzfListRc lrc = bgzf_list(data, n_bytes, may_cut, true, blks, L);
+    if (lrc == BGZF_LIST_NOT_WHOLE) return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu of file %d in the chunk", (unsigned long long)L.bad_off, file);
+    if (lrc == BGZF_LIST_CLAIMS) return fail(h, MLST_E_INVALID, "BGZF block at byte %llu of file %d claims %u bytes of data", (unsigned long long)L.bad_off, file, L.bad_isize);
+    n_bytes = L.taken; text = L.text;
+    for (size_t i = b0; i < blks.size(); i++) blks[i].in_off += in_base;
     if (text >= (1ull << 38)) return fail(h, MLST_E_LIMIT, "FASTQ chunk too large");
     return MLST_OK;
 }
@@ -5590,19 +5504,12 @@ static int bzp_submit(mlst_handle* h, const u8* data1, u64 n1, const u8* data2, 
     const u64 off2 = (n1 + 255) & ~(u64)255, n_all = off2 + n2;
     mlst_handle::BzChunk* C = nullptr;
     if (n_all) {
-        C = &h->bzc[h->bz_chunk ^= 1];
-        if (!C->ev_used) { HIPCHK(h, hipEventCreateWithFlags(&C->ev_used, hipEventDisableTiming)); for (auto& ev : C->ev) HIPCHK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming)); }
-        if (C->cap < n_all) {
-            if (C->used) HIPCHK(h, hipEventSynchronize(C->ev_used));
-            hipFree(C->d); C->d = nullptr; C->cap = 0;
-            HIPCHK(h, dmalloc(&C->d, n_all + n_all / 8 + 32)); C->cap = n_all + n_all / 8;
-        }
-        if (C->used) HIPCHK(h, hipStreamWaitEvent(cs, C->ev_used, 0));
+        { int rc = bz_chunk_take(h, n_all, cs, C); if (rc) return rc; }
         if (n1) HIPCHK(h, hipMemcpyAsync(C->d, data1, n1, hipMemcpyHostToDevice, cs));
         if (n2) HIPCHK(h, hipMemcpyAsync(C->d + off2, data2, n2, hipMemcpyHostToDevice, cs));
         HIPCHK(h, hipEventRecord(C->ev[0], cs)); C->upto[0] = n_all; C->n_ev = 1;
     }
-    struct CopyGuard { hipStream_t s; bool on; ~CopyGuard() { if (on) hipStreamSynchronize(s); } } copy_guard{cs, C != nullptr};
+    CopyGuard copy_guard{cs, C != nullptr};
     std::vector<BgzfBlk> blks; u64 t1 = 0, t2 = 0;
     { int rc = bzp_list(h, data1, n1, n_consumed1_out && !final_chunk, 0, 1, blks, t1); if (rc) return rc; }
     const u32 nblk1 = (u32)blks.size();
@@ -5627,32 +5534,20 @@ static int bzp_submit(mlst_handle* h, const u8* data1, u64 n1, const u8* data2, 
     for (u32 i = 0; i < (u32)blks.size(); i++) blks[i].out_off += i < nblk1 ? P.head[0] : P.base[1] + P.head[1];
     const int sl = h->bz_slot ^= 1;
     mlst_handle::BzSlot& B = h->bz[sl];
-    if (!B.ev_copied) { HIPCHK(h, hipEventCreateWithFlags(&B.ev_copied, hipEventDisableTiming)); HIPCHK(h, hipEventCreateWithFlags(&B.ev_inflated, hipEventDisableTiming));
-                        HIPCHK(h, dmalloc(&B.d_err, (u64)16)); HIPCHK(h, hipHostMalloc((void**)&B.h_err, 64, hipHostMallocDefault)); }
-    if (B.cap_blk < blks.size()) {
-        hipFree(B.d_blk); B.d_blk = nullptr; if (B.h_blk) { hipHostFree(B.h_blk); B.h_blk = nullptr; }
-        const u64 cap = blks.size() + blks.size() / 8;
-        BgzfBlk* pb = nullptr; HIPCHK(h, dmalloc(&pb, cap)); B.d_blk = pb;
-        HIPCHK(h, hipHostMalloc(&B.h_blk, cap * sizeof(BgzfBlk), hipHostMallocDefault));
-        B.cap_blk = cap;
-    }
+    { int rc = bz_slot_init(h, B); if (rc) return rc; }
     {   int rc = next_text_slot(h, slot_bytes);
         if (rc && (h->pc_len[0] || h->pc_len[1]))
             return fail(h, MLST_E_LIMIT, "no room on the device for a piece of mate files with the records waiting for their mates (%llu + %llu bytes carried)",
                         (unsigned long long)h->pc_len[0], (unsigned long long)h->pc_len[1]);
         if (rc) return rc; }
     P.tslot = h->fq_slot; P.slot = sl;
-    if (!h->inflate_mode) { const char* ev = getenv("MLST_INFLATE_MODE"); h->inflate_mode = ev ? atoi(ev) : 2; if (h->inflate_mode != 1 && h->inflate_mode != 2) h->inflate_mode = 2; }
-    P.counted = h->inflate_mode == 2 && !getenv("MLST_BGZF_NOCOUNT");
-    if (!blks.empty()) {
-        memcpy(B.h_blk, blks.data(), blks.size() * sizeof(BgzfBlk));
-        HIPCHK(h, hipMemcpyAsync(B.d_blk, B.h_blk, blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice, st));
-    }
+    P.counted = inflate_counted(h);
+    { int rc = blk_upload(h, B.blk, blks, st); if (rc) return rc; }
     if (C && piped) HIPCHK(h, hipStreamWaitEvent(st, C->ev[0], 0));
     HIPCHK(h, hipStreamWaitEvent(st, h->ev_packed[P.tslot], 0));      // the text slot's last reader
     HIPCHK(h, hipMemsetAsync(B.d_err, 0, 64, st));
     HIPCHK(h, hipMemsetAsync(h->d_fq_nl[P.tslot], 0, (slot_bytes / FQ_BLOCK + 2) * 4, st));
-    if (!blks.empty()) { int rc = launch_inflate(h, C->d, C->cap + 16, (const BgzfBlk*)B.d_blk, (u32)blks.size(), h->d_fq_slot[P.tslot], B.d_err, nullptr, st,
+    if (!blks.empty()) { int rc = launch_inflate(h, C->d, C->cap + 16, B.blk.d, (u32)blks.size(), h->d_fq_slot[P.tslot], B.d_err, nullptr, st,
                                                  P.counted ? h->d_fq_nl[P.tslot] : nullptr); if (rc) return rc; }
     HIPCHK(h, hipMemcpyAsync(B.h_err, B.d_err, h->bgzf_verify ? 16 : 8, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipEventRecord(B.ev_inflated, st));
@@ -5683,6 +5578,35 @@ extern "C" int mlst_submit_fastq_bgzf_pair(mlst_handle* h, const uint8_t* data1,
     return rc;
 }
 
+// The scaffold of the two self-tests below: the whole blocks of `data` listed (selftest_list), then (selftest_run) the buffers
+// allocated and filled, the entry's launch on the engine's stream, waited for, the error words read and the entry's results
+// fetched.  The device buffers are released by scope; d_own is the entry's own one (inflate statistics, CRC values).
+struct SelfTest {
+    std::vector<BgzfBlk> blks; u64 text_bytes = 0; bool ran = false;      // ran: the launch was queued and waited for without an error
+    u8* d_in = nullptr; u8* d_out = nullptr; BgzfBlk* d_blk = nullptr; u32* d_err = nullptr; void* d_own = nullptr;
+    ~SelfTest() { hipFree(d_in); hipFree(d_out); hipFree(d_blk); hipFree(d_err); hipFree(d_own); }
+};
+static int selftest_list(mlst_handle* h, const u8* data, u64 n_bytes, SelfTest& T) {
+    BgzfList L; const BgzfListRc lrc = bgzf_list(data, n_bytes, false, false, T.blks, L);
+    if (lrc == BGZF_LIST_NOT_WHOLE) return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu", (unsigned long long)L.bad_off);
+    if (lrc == BGZF_LIST_CLAIMS) return fail(h, MLST_E_INVALID, "BGZF block claims %u bytes of data", L.bad_isize);
+    T.text_bytes = L.text; return MLST_OK;
+}
+template <class Launch, class Fetch>
+static int selftest_run(mlst_handle* h, const u8* data, u64 n_bytes, SelfTest& T, const char* kernel, Launch launch, Fetch fetch) {
+    if (dmalloc(&T.d_in, n_bytes + 16) != hipSuccess || dmalloc(&T.d_out, T.text_bytes + 16) != hipSuccess || dmalloc(&T.d_blk, (u64)T.blks.size()) != hipSuccess || dmalloc(&T.d_err, (u64)8) != hipSuccess)
+        return fail(h, MLST_E_HIP, "device allocation failed");
+    if (hipMemcpy(T.d_in, data, n_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(T.d_blk, T.blks.data(), T.blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice) != hipSuccess
+        || hipMemset(T.d_err, 0, 32) != hipSuccess || hipMemset(T.d_out, 0xEE, T.text_bytes) != hipSuccess) return fail(h, MLST_E_HIP, "copy to the device failed");
+    const int rc = launch();
+    T.ran = hipStreamSynchronize(h->stream) == hipSuccess && !rc;
+    if (rc) return rc;
+    u32 err[4] = {0, 0, 0, 0};
+    if (!T.ran || hipMemcpy(err, T.d_err, 16, hipMemcpyDeviceToHost) != hipSuccess || fetch() != hipSuccess)
+        return fail(h, MLST_E_HIP, "%s failed: %s", kernel, hipGetErrorString(hipGetLastError()));
+    return err[0] ? bz_fail(h, err, err[0] - 1, "") : MLST_OK;
+}
+
 // k_inflate itself on whole BGZF blocks, text back to the host: the test hook of the DEVICE decoder (tests/test_inflate.py
 // compares it with zlib block by block on the GPU box)
 extern "C" int mlst_selftest_inflate_device(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, uint8_t* out, uint64_t cap, uint64_t* produced, double* kernel_ms) {
@@ -5692,64 +5616,48 @@ extern "C" int mlst_selftest_inflate_device(mlst_handle* h, const uint8_t* data,
     if (!data || !out) return fail(h, MLST_E_INVALID, "NULL argument");
     hipSetDevice(h->device);
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
-    std::vector<BgzfBlk> blks; u64 text_bytes = 0;
-    for (u64 off = 0; off < n_bytes; ) {
-        u64 total, coff, clen; u32 isize;
-        if (!bgzf_block(data + off, n_bytes - off, total, coff, clen, isize)) return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu", (unsigned long long)off);
-        if (isize > 65536) return fail(h, MLST_E_INVALID, "BGZF block claims %u bytes of data", isize);
-        if (isize) { BgzfBlk b; b.in_off = off + coff; b.in_len = (u32)clen; b.out_off = text_bytes; b.out_len = isize; blks.push_back(b); text_bytes += isize; }
-        off += total;
-    }
-    if (text_bytes > cap) return fail(h, MLST_E_LIMIT, "output buffer too small (%llu bytes needed)", (unsigned long long)text_bytes);
-    if (produced) *produced = text_bytes;
+    SelfTest T;
+    { int rc_ = selftest_list(h, data, n_bytes, T); if (rc_) return rc_; }
+    const std::vector<BgzfBlk>& blks = T.blks;
+    if (T.text_bytes > cap) return fail(h, MLST_E_LIMIT, "output buffer too small (%llu bytes needed)", (unsigned long long)T.text_bytes);
+    if (produced) *produced = T.text_bytes;
     if (blks.empty()) return MLST_OK;
-    u8* d_in = nullptr; u8* d_out = nullptr; BgzfBlk* d_blk = nullptr; u32* d_err = nullptr; unsigned long long* d_st = nullptr;
-    int rc = MLST_OK; u32 err[4] = {0, 0, 0, 0};
+    unsigned long long* d_st = nullptr;
 #if defined(MLST_INFLATE_STATS)
     const bool want_stats = getenv("MLST_INFLATE_STATS") != nullptr;      // (diagnostic builds: hipcc -DMLST_INFLATE_STATS)
 #else
     const bool want_stats = false;
 #endif
-    if (want_stats && (dmalloc(&d_st, (u64)16) != hipSuccess || hipMemset(d_st, 0, 128) != hipSuccess)) d_st = nullptr;
-    if (dmalloc(&d_in, n_bytes + 16) != hipSuccess || dmalloc(&d_out, text_bytes + 16) != hipSuccess || dmalloc(&d_blk, (u64)blks.size()) != hipSuccess || dmalloc(&d_err, (u64)8) != hipSuccess)
-        rc = fail(h, MLST_E_HIP, "device allocation failed");
-    if (!rc && (hipMemcpy(d_in, data, n_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_blk, blks.data(), blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice) != hipSuccess
-                || hipMemset(d_err, 0, 32) != hipSuccess || hipMemset(d_out, 0xEE, text_bytes) != hipSuccess)) rc = fail(h, MLST_E_HIP, "copy to the device failed");
-    if (!rc) {
-        hipEvent_t e0 = ev_get(h), e1 = ev_get(h);
-        hipEventRecord(e0, h->stream);
-        rc = launch_inflate(h, d_in, (u64)n_bytes + 16, (const BgzfBlk*)d_blk, (u32)blks.size(), d_out, d_err, d_st);
-        const bool launched = rc == MLST_OK;
-        hipEventRecord(e1, h->stream);
-        hipError_t se = hipStreamSynchronize(h->stream);
-        float ms = 0; if (se == hipSuccess) hipEventElapsedTime(&ms, e0, e1);
-        if (kernel_ms) *kernel_ms = (double)ms;
-        h->ev_pool.push_back(e0); h->ev_pool.push_back(e1);
-        if (se != hipSuccess || hipMemcpy(err, d_err, 16, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out, d_out, text_bytes, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(h, MLST_E_HIP, "k_inflate failed: %s", hipGetErrorString(hipGetLastError()));
-        else if (err[0]) rc = bz_fail(h, err, err[0] - 1, "");
-        // (mlst_debug_inflate_paths: what phase 1 left to k_inflate, read from its token counts after the fact)
-        h->dbg_infl_blocks = blks.size(); h->dbg_infl_left = 0;
-        if (launched && se == hipSuccess && (h->inflate_mode == 1 || d_st)) h->dbg_infl_known = true;
-        else if (launched && se == hipSuccess && blks.size() <= h->cap_itok_blocks && blks.size() <= INFL_PASS) {      // (one pass of either phase 1; k_inflate_tok2 would take more in one, not needed here)
-            std::vector<u32> nt(blks.size());
-            if (hipMemcpy(nt.data(), h->d_intok, blks.size() * sizeof(u32), hipMemcpyDeviceToHost) == hipSuccess) {
-                for (u32 v : nt) h->dbg_infl_left += v == (u32)inflate_lane::TOK_OVERFLOW;
-                h->dbg_infl_known = true;
-            }
+    if (want_stats && (dmalloc(&d_st, (u64)16) != hipSuccess || hipMemset(d_st, 0, 128) != hipSuccess)) { hipFree(d_st); d_st = nullptr; }
+    T.d_own = d_st;
+    hipEvent_t e0 = ev_get(h), e1 = ev_get(h);
+    const int rc = selftest_run(h, data, n_bytes, T, "k_inflate",
+        [&] { hipEventRecord(e0, h->stream); const int r = launch_inflate(h, T.d_in, (u64)n_bytes + 16, T.d_blk, (u32)blks.size(), T.d_out, T.d_err, d_st);
+              hipEventRecord(e1, h->stream); return r; },
+        [&] { return hipMemcpy(out, T.d_out, T.text_bytes, hipMemcpyDeviceToHost); });
+    float ms = 0; if (T.ran) hipEventElapsedTime(&ms, e0, e1);
+    if (kernel_ms) *kernel_ms = (double)ms;
+    h->ev_pool.push_back(e0); h->ev_pool.push_back(e1);
+    // (mlst_debug_inflate_paths: what phase 1 left to k_inflate, read from its token counts after the fact)
+    h->dbg_infl_blocks = blks.size(); h->dbg_infl_left = 0;
+    if (T.ran && (h->inflate_mode == 1 || d_st)) h->dbg_infl_known = true;
+    else if (T.ran && blks.size() <= h->cap_itok_blocks && blks.size() <= INFL_PASS) {      // (one pass of either phase 1; k_inflate_tok2 would take more in one, not needed here)
+        std::vector<u32> nt(blks.size());
+        if (hipMemcpy(nt.data(), h->d_intok, blks.size() * sizeof(u32), hipMemcpyDeviceToHost) == hipSuccess) {
+            for (u32 v : nt) h->dbg_infl_left += v == (u32)inflate_lane::TOK_OVERFLOW;
+            h->dbg_infl_known = true;
         }
-#if defined(MLST_PTR_TRACE)
-        { u32 tr[8] = {0}; if (hipMemcpy(tr, d_err, 32, hipMemcpyDeviceToHost) == hipSuccess)
-            fprintf(stderr, "k_inflate_ptr phases over %zu blocks (units of 64 cycles): fill %u, pointer jumping %u (%u rounds), gather %u\n", blks.size(), tr[2], tr[3], tr[5], tr[4]); }
-#endif
     }
+#if defined(MLST_PTR_TRACE)
+    { u32 tr[8] = {0}; if (T.d_err && hipMemcpy(tr, T.d_err, 32, hipMemcpyDeviceToHost) == hipSuccess)
+        fprintf(stderr, "k_inflate_ptr phases over %zu blocks (units of 64 cycles): fill %u, pointer jumping %u (%u rounds), gather %u\n", blks.size(), tr[2], tr[3], tr[5], tr[4]); }
+#endif
     if (d_st && !rc) {
         unsigned long long v[10] = {0};
         if (hipMemcpy(v, d_st, sizeof v, hipMemcpyDeviceToHost) == hipSuccess)
             fprintf(stderr, "k_inflate stats over %zu blocks: look-ups %llu, literal bytes %llu, near matches %llu, far matches deferred %llu / at once %llu, far flushes %llu, fences %llu, "
                             "table builds %llu, cycles in builds %llu / in codes %llu (sums over waves)\n", blks.size(), v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]);
     }
-    hipFree(d_in); hipFree(d_out); hipFree(d_blk); hipFree(d_err); hipFree(d_st);
     return rc;
 }
 
@@ -5770,38 +5678,24 @@ extern "C" int mlst_selftest_bgzf_crc(mlst_handle* h, const uint8_t* data, uint6
     if (!data || !crc_out) return fail(h, MLST_E_INVALID, "NULL argument");
     hipSetDevice(h->device);
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
-    std::vector<BgzfBlk> blks; u64 text_bytes = 0;
-    for (u64 off = 0; off < n_bytes; ) {
-        u64 total, coff, clen; u32 isize;
-        if (!bgzf_block(data + off, n_bytes - off, total, coff, clen, isize)) return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu", (unsigned long long)off);
-        if (isize > 65536) return fail(h, MLST_E_INVALID, "BGZF block claims %u bytes of data", isize);
-        if (isize) { BgzfBlk b; b.in_off = off + coff; b.in_len = (u32)clen; b.out_off = text_bytes; b.out_len = isize; blks.push_back(b); text_bytes += isize; }
-        off += total;
-    }
+    SelfTest T;
+    { int rc_ = selftest_list(h, data, n_bytes, T); if (rc_) return rc_; }
+    const std::vector<BgzfBlk>& blks = T.blks;
     if (blks.size() > cap) return fail(h, MLST_E_LIMIT, "output buffer too small (%llu values needed)", (unsigned long long)blks.size());
     if (blks.size() >= (1ull << 31)) return fail(h, MLST_E_LIMIT, "BGZF chunk too large");
     if (n_blocks) *n_blocks = blks.size();
     if (blks.empty()) return MLST_OK;
-    u8* d_in = nullptr; u8* d_out = nullptr; BgzfBlk* d_blk = nullptr; u32* d_err = nullptr; u32* d_crc = nullptr;
-    int rc = MLST_OK; u32 err[4] = {0, 0, 0, 0};
-    if (dmalloc(&d_in, n_bytes + 16) != hipSuccess || dmalloc(&d_out, text_bytes + 16) != hipSuccess || dmalloc(&d_blk, (u64)blks.size()) != hipSuccess || dmalloc(&d_err, (u64)8) != hipSuccess
-        || dmalloc(&d_crc, (u64)blks.size()) != hipSuccess) rc = fail(h, MLST_E_HIP, "device allocation failed");
-    if (!rc && (hipMemcpy(d_in, data, n_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_blk, blks.data(), blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice) != hipSuccess
-                || hipMemset(d_err, 0, 32) != hipSuccess || hipMemset(d_crc, 0, blks.size() * 4) != hipSuccess)) rc = fail(h, MLST_E_HIP, "copy to the device failed");
-    if (!rc) {
-        h->crc_hook.d_out = d_crc; h->crc_hook.e0 = ev_get(h); h->crc_hook.e1 = ev_get(h);
-        rc = launch_inflate(h, d_in, (u64)n_bytes + 16, (const BgzfBlk*)d_blk, (u32)blks.size(), d_out, d_err, nullptr);
-        hipError_t se = hipStreamSynchronize(h->stream);
-        float ms = 0; if (!rc && se == hipSuccess) hipEventElapsedTime(&ms, h->crc_hook.e0, h->crc_hook.e1);
-        if (kernel_ms) *kernel_ms = (double)ms;
-        h->ev_pool.push_back(h->crc_hook.e0); h->ev_pool.push_back(h->crc_hook.e1);
-        h->crc_hook.d_out = nullptr; h->crc_hook.e0 = h->crc_hook.e1 = nullptr;
-        if (rc) {}
-        else if (se != hipSuccess || hipMemcpy(err, d_err, 16, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(crc_out, d_crc, blks.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(h, MLST_E_HIP, "k_bgzf_crc failed: %s", hipGetErrorString(hipGetLastError()));
-        else if (err[0]) rc = bz_fail(h, err, err[0] - 1, "");
-    }
-    hipFree(d_in); hipFree(d_out); hipFree(d_blk); hipFree(d_err); hipFree(d_crc);
+    u32* d_crc = nullptr; const hipError_t ae = dmalloc(&d_crc, (u64)blks.size()); T.d_own = d_crc;
+    if (ae != hipSuccess) return fail(h, MLST_E_HIP, "device allocation failed");
+    if (hipMemset(d_crc, 0, blks.size() * 4) != hipSuccess) return fail(h, MLST_E_HIP, "copy to the device failed");
+    h->crc_hook.d_out = d_crc; h->crc_hook.e0 = ev_get(h); h->crc_hook.e1 = ev_get(h);
+    const int rc = selftest_run(h, data, n_bytes, T, "k_bgzf_crc",
+        [&] { return launch_inflate(h, T.d_in, (u64)n_bytes + 16, T.d_blk, (u32)blks.size(), T.d_out, T.d_err, nullptr); },
+        [&] { return hipMemcpy(crc_out, d_crc, blks.size() * 4, hipMemcpyDeviceToHost); });
+    float ms = 0; if (T.ran) hipEventElapsedTime(&ms, h->crc_hook.e0, h->crc_hook.e1);
+    if (kernel_ms) *kernel_ms = (double)ms;
+    h->ev_pool.push_back(h->crc_hook.e0); h->ev_pool.push_back(h->crc_hook.e1);
+    h->crc_hook.d_out = nullptr; h->crc_hook.e0 = h->crc_hook.e1 = nullptr;
     return rc;
 }
 
@@ -5812,7 +5706,7 @@ extern "C" int mlst_selftest_bgzf_crc(mlst_handle* h, const uint8_t* data, uint6
 // stays on the device, so nothing waits for the host: the call returns once its bytes have left the caller's buffer, and the
 // piece's errors are looked at by the next call on the handle (bam_flush) -- MLST_BGZF_PIPE=0: by the call itself.
 struct BamSlot {
-    u8* d_comp = nullptr; u64 cap_comp = 0; BgzfBlk* d_blk = nullptr; BgzfBlk* h_blk = nullptr; u64 cap_blk = 0;
+    u8* d_comp = nullptr; u64 cap_comp = 0; mlst_handle::BlkList blk;
     u8* d_text = nullptr; u64 cap_text = 0; u32* d_cells = nullptr; u32* d_list = nullptr; u64 cap_cells = 0;
     u32* d_err = nullptr; u8* h_res = nullptr;      // h_res (pinned): 4 error words of the inflate, then the BamMeta after the piece (a reads stream: and its BamReadsMeta)
     hipEvent_t ev_copied = nullptr, ev_done = nullptr;
@@ -5840,7 +5734,7 @@ static void bam_drop(mlst_handle* h, bool release) {
     B->open = false; B->pend = false; B->counts_ready = false;
     if (!release) return;
     for (auto& S : B->s) {
-        hipFree(S.d_comp); hipFree(S.d_blk); if (S.h_blk) hipHostFree(S.h_blk); hipFree(S.d_text); hipFree(S.d_cells); hipFree(S.d_list); hipFree(S.d_err);
+        hipFree(S.d_comp); hipFree(S.blk.d); if (S.blk.h) hipHostFree(S.blk.h); hipFree(S.d_text); hipFree(S.d_cells); hipFree(S.d_list); hipFree(S.d_err);
         if (S.h_res) hipHostFree(S.h_res); if (S.ev_copied) hipEventDestroy(S.ev_copied); if (S.ev_done) hipEventDestroy(S.ev_done);
         hipFree(S.d_rd); if (S.ev_inflated) hipEventDestroy(S.ev_inflated); if (S.ev_free) hipEventDestroy(S.ev_free);
     }
@@ -5983,19 +5877,13 @@ extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_
     hipSetDevice(h->device);
     BamStream* B = h->bam;
     const bool piped = bz_mode(h) != 0;
-    std::vector<BgzfBlk> blks; u64 text_bytes = BAM_HEAD;
-    for (u64 off = 0; off < n_bytes; ) {
-        u64 total, coff, clen; u32 isize;
-        if (!bgzf_block(data + off, n_bytes - off, total, coff, clen, isize)) {
-            const bool cut = n_bytes - off < 18 || (data[off] == 0x1f && data[off + 1] == 0x8b && data[off + 2] == 8 && (data[off + 3] & 4));
-            if (n_consumed_out && !final_chunk && cut) { n_bytes = off; break; }
-            bam_drop(h, false);
-            return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu of the chunk", (unsigned long long)off);
-        }
-        if (isize > 65536) { bam_drop(h, false); return fail(h, MLST_E_INVALID, "BGZF block at byte %llu claims %u bytes of data", (unsigned long long)off, isize); }
-        if (isize) { BgzfBlk b; b.in_off = off + coff; b.in_len = (u32)clen; b.out_off = text_bytes; b.out_len = isize; blks.push_back(b); text_bytes += isize; }
-        off += total;
-    }
+    std::vector<BgzfBlk> blks; BgzfList L;
+    const BgzfListRc lrc = bgzf_list(data, n_bytes, n_consumed_out && !final_chunk, false, blks, L);      // (may_cut: as in mlst_submit_fastq_bgzf)
+    if (lrc == BGZF_LIST_NOT_WHOLE) { bam_drop(h, false); return fail(h, MLST_E_INVALID, "not a whole BGZF block at byte %llu of the chunk", (unsigned long long)L.bad_off); }
+    if (lrc == BGZF_LIST_CLAIMS) { bam_drop(h, false); return fail(h, MLST_E_INVALID, "BGZF block at byte %llu claims %u bytes of data", (unsigned long long)L.bad_off, L.bad_isize); }
+    n_bytes = L.taken;
+    for (auto& q : blks) q.out_off += BAM_HEAD;
+    const u64 text_bytes = BAM_HEAD + L.text;
     if (text_bytes >= (1ull << 31) - (1ull << 21)) { bam_drop(h, false); return fail(h, MLST_E_LIMIT, "BGZF chunk inflates to more than 2 GiB"); }
     if (n_consumed_out) *n_consumed_out = n_bytes;
     uint64_t done = 0;
@@ -6022,11 +5910,6 @@ extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_
         if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
         const u32 n_cells = (u32)((text_bytes + BAM_CELL - 1) / BAM_CELL);
         if (S.cap_comp < n_bytes) { hipFree(S.d_comp); S.d_comp = nullptr; S.cap_comp = 0; HIPCHK(h, dmalloc(&S.d_comp, n_bytes + n_bytes / 8 + 32)); S.cap_comp = n_bytes + n_bytes / 8; }
-        if (S.cap_blk < blks.size()) {
-            hipFree(S.d_blk); S.d_blk = nullptr; if (S.h_blk) { hipHostFree(S.h_blk); S.h_blk = nullptr; } S.cap_blk = 0;
-            const u64 cap = blks.size() + blks.size() / 8 + 16;
-            HIPCHK(h, dmalloc(&S.d_blk, cap)); HIPCHK(h, hipHostMalloc((void**)&S.h_blk, cap * sizeof(BgzfBlk), hipHostMallocDefault)); S.cap_blk = cap;
-        }
         if (S.cap_text < text_bytes) { hipFree(S.d_text); S.d_text = nullptr; S.cap_text = 0; const u64 cap = text_bytes + text_bytes / 8; HIPCHK(h, dmalloc(&S.d_text, cap + 2 * BAM_CELL + 65536)); S.cap_text = cap; }
         if (S.cap_cells < n_cells) {
             hipFree(S.d_cells); hipFree(S.d_list); S.d_cells = S.d_list = nullptr; S.cap_cells = 0;
@@ -6049,19 +5932,18 @@ extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_
             }
             B->bound_pend += bound; S.bound = bound;
         }
-        if (!blks.empty()) memcpy(S.h_blk, blks.data(), blks.size() * sizeof(BgzfBlk));      // (no blocks: the closing piece of a paired reads stream)
         if (n_bytes) HIPCHK(h, hipMemcpyAsync(S.d_comp, data, n_bytes, hipMemcpyHostToDevice, h->copy_stream));
         HIPCHK(h, hipEventRecord(S.ev_copied, h->copy_stream));
-        struct CopyGuard { mlst_handle* h; ~CopyGuard() { hipStreamSynchronize(h->copy_stream); } } copy_guard{h};      // `data` is the caller's again on return
+        CopyGuard copy_guard{h->copy_stream, true};      // `data` is the caller's again on return
+        if (B->reads) { int rc = bz_stream(h); if (rc) return rc; }
+        hipStream_t const st = B->reads ? h->infl_stream : h->stream;      // (a reads stream inflates beside the engine's stream)
+        { int rc = blk_upload(h, S.blk, blks, st); if (rc) return rc; }      // (no blocks: the closing piece of a paired reads stream)
+        HIPCHK(h, hipMemsetAsync(S.d_err, 0, 64, st));
+        HIPCHK(h, hipStreamWaitEvent(st, S.ev_copied, 0));
+        { int rc = launch_inflate(h, S.d_comp, S.cap_comp + 16, S.blk.d, (u32)blks.size(), S.d_text, S.d_err, nullptr, st); if (rc) { bam_drop(h, false); return rc; } }
         if (B->reads) {      // the call queues the copy and the inflate of its piece; the rest is bamr_finish's
-            { int rc = bz_stream(h); if (rc) return rc; }
-            hipStream_t si = h->infl_stream;
-            if (!blks.empty()) HIPCHK(h, hipMemcpyAsync(S.d_blk, S.h_blk, blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice, si));
-            HIPCHK(h, hipMemsetAsync(S.d_err, 0, 64, si));
-            HIPCHK(h, hipStreamWaitEvent(si, S.ev_copied, 0));
-            { int rc = launch_inflate(h, S.d_comp, S.cap_comp + 16, S.d_blk, (u32)blks.size(), S.d_text, S.d_err, nullptr, si); if (rc) { bam_drop(h, false); return rc; } }
-            HIPCHK(h, hipMemcpyAsync(S.h_res, S.d_err, 16, hipMemcpyDeviceToHost, si));
-            HIPCHK(h, hipEventRecord(S.ev_inflated, si));
+            HIPCHK(h, hipMemcpyAsync(S.h_res, S.d_err, 16, hipMemcpyDeviceToHost, st));
+            HIPCHK(h, hipEventRecord(S.ev_inflated, st));
             if (hipGetLastError() != hipSuccess) { bam_drop(h, false); return fail(h, MLST_E_HIP, "a BAM kernel could not be launched"); }
             S.text_end = (u32)text_bytes; S.n_cells = n_cells; S.final_piece = final_chunk != 0; S.first_piece = B->first;
             if (B->pend) { const int rc = bam_finish(h, &done); if (rc) return rc; }      // the piece before, while the GPU inflates this one
@@ -6072,11 +5954,6 @@ extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_
             B->open = false;
             return MLST_OK;
         }
-        hipStream_t st = h->stream;
-        HIPCHK(h, hipMemcpyAsync(S.d_blk, S.h_blk, blks.size() * sizeof(BgzfBlk), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemsetAsync(S.d_err, 0, 64, st));
-        HIPCHK(h, hipStreamWaitEvent(st, S.ev_copied, 0));
-        { int rc = launch_inflate(h, S.d_comp, S.cap_comp + 16, S.d_blk, (u32)blks.size(), S.d_text, S.d_err, nullptr, st); if (rc) { bam_drop(h, false); return rc; } }
         const u32 text_end = (u32)text_bytes; const bool last = final_chunk != 0;
         u32* d_first = S.d_cells; u32* d_exit = d_first + S.cap_cells; u32* d_count = d_exit + S.cap_cells; u32* d_base = d_count + S.cap_cells;
         hipLaunchKernelGGL(k_bam_carry_in, dim3(64), dim3(256), 0, st, S.d_text, (const u8*)B->d_carry, B->d_meta, B->first ? B->skip : 0u);
