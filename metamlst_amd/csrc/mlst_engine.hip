@@ -3590,7 +3590,9 @@ __host__ __device__ inline long long round_tenths(long long p, u32 q) {
     return (m & 1) ? m + 1 : m;                                          // the double IS the tie: even digit
 }
 // One block per locus: chosen[l] = the allele with the highest rounded penalised average, ties to the lowest allele
-// number (Q5), or -1 when the locus has no accepted record.
+// number (Q5), or -1 when the locus has no accepted record.  Rows of a malformed database that share their number and tie
+// go to the lowest allele INDEX (the first that typing.pick_alleles_fast visits): each of the three compares below orders
+// candidates completely, so the answer does not depend on which thread or wave held which allele.
 __global__ __launch_bounds__(256) void k_choose(const EngineDev* __restrict__ Ep, const int* __restrict__ allele_no, int penalty,
                                                 int* __restrict__ chosen) {
     const EngineDev& E = *Ep;
@@ -3610,16 +3612,16 @@ __global__ __launch_bounds__(256) void k_choose(const EngineDev* __restrict__ Ep
         if (!nh) continue;
         const long long local = E.sum_score[a] - (long long)(mx - nh) * (long long)penalty;     // metamlst.py:146-147
         const long long r = round_tenths(local, nh); const int no = allele_no[a];
-        if (ba < 0 || r > br || (r == br && no < bno)) { br = r; bno = no; ba = (int)a; }
+        if (ba < 0 || r > br || (r == br && (no < bno || (no == bno && (int)a < ba)))) { br = r; bno = no; ba = (int)a; }
     }
     for (int o = 32; o > 0; o >>= 1) {
         long long r2 = __shfl_xor(br, o); int no2 = __shfl_xor(bno, o); int a2 = __shfl_xor(ba, o);
-        if (a2 >= 0 && (ba < 0 || r2 > br || (r2 == br && no2 < bno))) { br = r2; bno = no2; ba = a2; }
+        if (a2 >= 0 && (ba < 0 || r2 > br || (r2 == br && (no2 < bno || (no2 == bno && a2 < ba))))) { br = r2; bno = no2; ba = a2; }
     }
     if (lane == 0) { s_r[wv] = br; s_no[wv] = bno; s_a[wv] = ba; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; k++) if (s_a[k] >= 0 && (ba < 0 || s_r[k] > br || (s_r[k] == br && s_no[k] < bno))) { br = s_r[k]; bno = s_no[k]; ba = s_a[k]; }
+        for (int k = 1; k < 4; k++) if (s_a[k] >= 0 && (ba < 0 || s_r[k] > br || (s_r[k] == br && (s_no[k] < bno || (s_no[k] == bno && s_a[k] < ba))))) { br = s_r[k]; bno = s_no[k]; ba = s_a[k]; }
         chosen[l] = ba;
     }
 }
