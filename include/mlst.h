@@ -179,6 +179,34 @@ int mlst_submit_fastq_bgzf_pair(mlst_handle* h, const uint8_t* data1, uint64_t n
 int mlst_set_bgzf_verify(mlst_handle* h, int on);
 int mlst_get_bgzf_verify(mlst_handle* h, int* on);
 
+/* ---- LONG READS: FASTQ records longer than a tile cut into windows on the GPU (csrc/fastq_tile.h) --------------------------------
+ * A read longer than MLST_MAX_READ_LEN (320) bases cannot be packed (the packed score's fields), and without this
+ * switch every FASTQ entry fails it with MLST_E_LIMIT "a FASTQ read is longer than 320 bases".  mlst_set_read_tiling(h, read_len,
+ * stride) switches tiling on for the handle (0, 0: off, the default -- nothing changes then and nothing more is launched, copied or
+ * waited for).  With it on, the UNPAIRED text entries -- mlst_submit_fastq, mlst_submit_fastq_stream and mlst_submit_fastq_bgzf with
+ * paired == 0 -- apply the rule of metamlst_amd.fastq.tile_fastq on the device, behind the parser:
+ *   - records keep their order.  A record of n <= read_len bases (n = 0 included) is one read, unchanged.
+ *   - a record of n > read_len bases becomes windows of read_len bases at starts 0, stride, 2 * stride, ... <= n - read_len, plus one
+ *     flush with the record's end when (n - read_len) % stride != 0 (mlst_submit_fasta's rule with min_len 0).
+ *   - a window carries the same slice of the sequence line and of the quality line; bases are what the parser makes of them (N, lower
+ *     case, CR as without the switch), and a window's non-ACGT bit (bit 15 of lens) is its own.
+ *   - windows are unpaired reads of their own (MLST_LONG_READ_WINDOWS, mlst_policy.h): read indices continue the handle's count in
+ *     record order, then start order, and n_reads_out counts reads, i.e. windows plus uncut records.
+ * A chunk without a record longer than read_len goes the way it goes without the switch (one flag test).  A chunk with one costs three
+ * small kernels, one host synchronisation (the window count sizes the buffers) and a kernel that writes every window's offsets;
+ * the windows are packed and submitted in rounds of at most MLST_TILE_ROUND windows (environment, read by mlst_create; default
+ * 16,777,216: a bound on the pack buffers, ~3.4 GB at 150 bases).  A chunk that makes 2^32 windows or more fails with MLST_E_LIMIT.
+ * NOT tiled, a long record there fails with MLST_E_LIMIT as before: paired submissions (paired != 0, mlst_submit_fastq_pair,
+ * mlst_submit_fastq_bgzf_pair), the reads of a BAM (mlst_bam_reads_open), mlst_submit_reads / mlst_submit_reads_device and the
+ * host-packed entries (mlst_pack_fastq_host, mlst_submit_packed_host, mlst_submit_packed_device).
+ * Refused: read_len or stride of 0 when the other is not (MLST_E_INVALID); read_len > 320 (MLST_E_LIMIT); a change while a FASTQ or
+ * BAM stream is open on the handle (MLST_E_INVALID "a FASTQ stream is open", as mlst_set_bgzf_verify).
+ * mlst_get_read_tiling_info: since the last mlst_reset_sample, out[0] = records seen by tiled submissions, out[1] = records cut,
+ * out[2] = windows made of them, out[3] = bases of the longest record. */
+int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t stride);
+int mlst_get_read_tiling(mlst_handle* h, uint32_t* read_len, uint32_t* stride);
+int mlst_get_read_tiling_info(mlst_handle* h, uint64_t out[4]);
+
 /* Host-packed input: what crosses the link is 2-bit bases + lengths (42 bytes per 150-base read instead of the 316 of its
  * FASTQ text); the Phred rows stay on the host and only those of the reads that pass the seed sieve (one in ~400 of a
  * metagenome) follow.  mlst_pack_fastq_host: FASTQ text (whole 4-line records) -> `packed` in the engine's resident layout
@@ -471,7 +499,8 @@ int mlst_import_stats_device_async(mlst_handle* h, const int64_t* d_sum, const i
 
 int mlst_set_profiling(mlst_handle* h, int on);   /* 0 = off, 1 = events + sieve window, 2 = sieve window only (keeps the hipGraph replay of the launch sequences, which event profiling turns off) */
 /* Per-kernel device time measured with HIP events on the engine's stream.
- * which: 0=sieve (all its kernels) 1=seed 2=extend (k_extend + k_extend_pairs) 3=banded-SW 4=accumulate 5=pileup 6=pack 12=k_ext_prep (the item records of k_extend); 9 = k_route, 10 =
+ * which: 0=sieve (all its kernels) 1=seed 2=extend (k_extend + k_extend_pairs) 3=banded-SW 4=accumulate 5=pileup 6=pack 12=k_ext_prep (the item records of k_extend);
+ * 13 = k_fqt_count + k_fqt_scan + k_fqt_add and 14 = k_fqt_emit (long reads cut into windows, csrc/fastq_tile.h; outside 6); 9 = k_route, 10 =
  * k_route_probe and 11 = k_route_verify, the three kernels of the routed sieve (inside 0) (events bracket the launch on the engine's
  * stream, so with several engines on one GPU they include the time a kernel queues behind another stream's kernel);
  * 7 = the sieve's execution window measured inside the kernel (wall clock at the first workgroup's start and the last

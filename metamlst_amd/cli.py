@@ -2,6 +2,7 @@
 
     python -m metamlst_amd.cli type  SAMPLE.fastq[.gz] [-2 MATES.fastq] -d DB [-o out] [--penalty ...]   (metamlst.py:34-49)
     python -m metamlst_amd.cli type  READS.bam -d DB [-o out]            (the reads of a BAM, as `samtools fastq` takes them)
+    python -m metamlst_amd.cli type  LONG.fastq --long-reads [--tile LEN,STEP] -d DB   (reads longer than 320 bases, cut into windows)
     python -m metamlst_amd.cli merge FOLDER -d DB [-z 5] [--filter ...] [--meta ...] [--idField ...]       (metamlst-merge.py:35-49)
     python -m metamlst_amd.cli index -d DB [-s seqs.fasta,...] [-t typings.txt,...] [-q dump.fa] [--list]   (metamlst-index.py:24-33)
 
@@ -39,6 +40,10 @@ def _type_parser(sub):
     p.add_argument("--contigs", action="store_true",
                    help="READS is a FASTA of contigs or an assembled genome (the input of the reference's mlst.py): it is cut into "
                         "overlapping windows (--tile LEN,STEP) that go through the same path as reads")
+    p.add_argument("--long-reads", dest="long_reads", action="store_true",
+                   help="READS holds reads longer than the 320 bases a packed read takes (merged pairs, amplicons, ONT / HiFi): a record "
+                        "longer than LEN is cut into overlapping windows (--tile LEN,STEP; 300,150 suits merged pairs) that keep their "
+                        "slice of the quality line and are typed as unpaired reads of their own; shorter records are typed as they are")
     p.add_argument("--tile", default="150,25", metavar="LEN,STEP")
     p.add_argument("-2", dest="mates",
                    help="second FASTQ of a paired-end sample: record k of it is the mate of record k of READS.  Mates are aligned as "
@@ -140,20 +145,38 @@ def expand_samples(reads: list[str], contigs: bool = False) -> list[list[str]]:
     return out
 
 
+def _parse_tile(text: str):
+    """--tile LEN,STEP -> (read_len, stride), None (said) when it is not two positive numbers"""
+    try:
+        read_len, stride = (int(x) for x in text.split(","))
+        if read_len < 1 or stride < 1:
+            raise ValueError
+    except ValueError:
+        print("--tile LEN,STEP takes two positive numbers, not %r" % text)
+        return None
+    return read_len, stride
+
+
 def run_type(a, argv=None) -> int:
-    tile = None
+    tile = long_reads = None
+    if a.long_reads:
+        if a.mates or a.alignments or a.contigs:
+            print("--long-reads takes unpaired FASTQ: it goes with none of -2, --alignments and --contigs")
+            return 1
+        long_reads = _parse_tile(a.tile)
+        if long_reads is None:
+            return 1
+        if long_reads[0] > 320:
+            print("--tile LEN,STEP: a window of --long-reads holds at most 320 bases, not %d" % long_reads[0])
+            return 1
     if a.contigs:
         if a.mates or a.alignments:
             print("--contigs takes assemblies (FASTA): it goes with neither -2 nor --alignments")
             return 1
-        try:
-            read_len, stride = (int(x) for x in a.tile.split(","))
-            if read_len < 1 or stride < 1:
-                raise ValueError
-        except ValueError:
-            print("--tile LEN,STEP takes two positive numbers, not %r" % a.tile)
+        t = _parse_tile(a.tile)
+        if t is None:
             return 1
-        tile = (read_len, stride, a.min_read_len)
+        tile = (t[0], t[1], a.min_read_len)
     samples = expand_samples(a.READS, contigs=bool(a.contigs))
     if not samples:
         print("no %s file found in " % ("FASTA" if a.contigs else "FASTQ") + ", ".join(a.READS))
@@ -165,6 +188,9 @@ def run_type(a, argv=None) -> int:
     a.READS, extra_files = samples[0][0], samples[0][1:]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     has_bam = not a.alignments and not a.contigs and any(_is_reads_bam(f) for smp in samples for f in smp)
+    if has_bam and long_reads:
+        print("--long-reads takes FASTQ: the reads of a BAM are packed whole (convert it with `samtools fastq`)")
+        return 1
     if has_bam and a.mates:
         print("-2 names the second FASTQ file of a pair: the mates of a BAM are records of the BAM itself (collate it by name)")
         return 1
@@ -193,6 +219,8 @@ def run_type(a, argv=None) -> int:
         return 1
     eng = Engine(a.device, prm)
     eng.set_bgzf_verify(a.verify_crc)
+    if long_reads:
+        eng.set_read_tiling(*long_reads)
     # the built host index is kept next to the database (as the reference keeps <idx>.1.bt2: metamlst-index.py:224-225) unless a
     # species filter made this index a one-off or MLST_INDEX_CACHE=0
     ref_cache = (a.database + ".mlstref") if (not a.filter and os.environ.get("MLST_INDEX_CACHE", "1") != "0") else ""
@@ -212,6 +240,8 @@ def run_type(a, argv=None) -> int:
             e2 = Engine(a.device, prm)
             e2.load_reference(idx)      # (the host index is cached inside the library: an upload, not a build)
             e2.set_bgzf_verify(a.verify_crc)
+            if long_reads:
+                e2.set_read_tiling(*long_reads)
             if a.depth_cap:
                 e2.set_depth_cap(a.depth_cap)
             engines.append(e2)
@@ -221,7 +251,7 @@ def run_type(a, argv=None) -> int:
     if many:
         from .multigpu import type_many_samples
         rc = type_many_samples(engines, idx, database, targs, samples, rank, world, a.o, a.log, chunk_bytes,
-                               printer=None if a.quiet else (lambda results: _print_results(a, results)), tile=tile)
+                               printer=None if a.quiet else (lambda results: _print_results(a, results)), tile=tile, long_reads=long_reads)
         database.closeConnection()
         return rc
     if a.alignments:
@@ -276,7 +306,7 @@ def run_type(a, argv=None) -> int:
         return 0
     # FASTQ text goes to the GPU as is and is parsed there (mlst_submit_fastq); a reader thread stays two chunks ahead
     try:
-        submit_sample_files(eng, paths, paired, chunk_bytes, report=None if a.quiet else print)
+        submit_sample_files(eng, paths, paired, chunk_bytes, report=None if a.quiet else print, long_reads=long_reads)
     except CorruptInput as e:      # nothing of the sample is typed: no .nfo
         print(e, file=sys.stderr)
         database.closeConnection()
@@ -350,13 +380,25 @@ def submit_contigs(eng, path: str, tile) -> int:
     return n
 
 
-def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader=None, report=None, tile=None) -> None:
+def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader=None, report=None, tile=None, long_reads=None) -> None:
     """All reads of one sample's file(s) into one engine: FASTQ (first_reader: open_sample_reader(paths, ...), if opened ahead), or
     BAMs whose records are taken as reads (report: see submit_bam_reads).  tile = (read_len, stride, min_len): the files are
-    assemblies (FASTA), cut into windows on the GPU (submit_contigs)."""
+    assemblies (FASTA), cut into windows on the GPU (submit_contigs).  long_reads = (read_len, stride): unpaired FASTQ whose records
+    longer than read_len are cut into windows on the GPU (Engine.set_read_tiling: plain text and bgzip on the device path, single-
+    stream .gz inflated on the host as always and cut on the device); report gets one line on what was cut."""
     if tile is not None:
         for path in paths:
             submit_contigs(eng, path, tile)
+        return
+    if long_reads is not None:
+        if paired or any(_is_reads_bam(p) for p in paths):
+            raise ValueError("long reads are unpaired FASTQ: neither mate files nor a BAM")
+        if eng.get_read_tiling() != tuple(long_reads):
+            eng.set_read_tiling(*long_reads)
+        submit_sample_files(eng, paths, False, chunk_bytes, first_reader=first_reader)
+        if report is not None:
+            info = eng.read_tiling_info()
+            report("%s: %d records, %d longer than %d cut into %d windows" % (",".join(paths), info["records"], info["cut"], long_reads[0], info["windows"]))
         return
     if paired and is_bgzf(paths[0]) and is_bgzf(paths[1]):      # bgzip'd mates: inflated and paired on the GPU
         crc_checked(paths, lambda: eng.submit_fastq_bgzf_pair_files(paths[0], paths[1]))

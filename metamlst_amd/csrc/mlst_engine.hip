@@ -1561,20 +1561,29 @@ __global__ __launch_bounds__(256) void k_fq_lines(const u8* __restrict__ text, u
 // pass D: per record the byte ranges of the sequence line (4r+1) and the quality line (4r+3); CR stripped
 // pair_k != 0: the text is two files of mates one after the other, pair_k records each; record j of the first becomes read
 // 2j, record j of the second read 2j + 1 (mates side by side, the order a paired submission expects)
+// (shared with csrc/fastq_tile.h, which needs a record's length in 64 bits)
+__device__ inline void fq_record_span(const u8* __restrict__ text, u64 n_bytes, const u64* __restrict__ line_start, u64 n_lines, u64 r, u64& s0, u64& q0, u64& ls, u64& lq) {
+    s0 = line_start[4 * r + 1]; const u64 s1 = line_start[4 * r + 2]; q0 = line_start[4 * r + 3];
+    u64 se = s1 - 1;
+    u64 qe = (4 * r + 4 < n_lines) ? line_start[4 * r + 4] - 1 : n_bytes;      // last record: up to the end of the chunk ...
+    if (qe > q0 && text[qe - 1] == '\n') qe--;                                 // ... minus its newline when there is one
+    if (se > s0 && text[se - 1] == '\r') se--;
+    if (qe > q0 && text[qe - 1] == '\r') qe--;
+    ls = se - s0; lq = qe - q0;
+}
+// TILE (mlst_set_read_tiling; unpaired text only): a record longer than tile_len bases is no error: bit 2 of flags[1] says that
+// the chunk holds one (csrc/fastq_tile.h cuts it; lens and flags[0] are not used then)
+template <bool TILE>
 __global__ __launch_bounds__(256) void k_fq_records(const u8* __restrict__ text, u64 n_bytes, const u64* __restrict__ line_start, u64 n_lines, u64 n_reads,
                                                      u64* __restrict__ seq_off, u64* __restrict__ qual_off, u16* __restrict__ lens, u32* __restrict__ flags /* [0]=max len, [1]=errors */,
-                                                     u64 pair_k) {
+                                                     u64 pair_k, u32 tile_len) {
     u32 mx = 0, err = 0;
     for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += (u64)gridDim.x * blockDim.x) {
-        u64 s0 = line_start[4 * r + 1], s1 = line_start[4 * r + 2], q0 = line_start[4 * r + 3];
-        u64 se = s1 - 1;
-        u64 qe = (4 * r + 4 < n_lines) ? line_start[4 * r + 4] - 1 : n_bytes;      // last record: up to the end of the chunk ...
-        if (qe > q0 && text[qe - 1] == '\n') qe--;                                 // ... minus its newline when there is one
-        if (se > s0 && text[se - 1] == '\r') se--;
-        if (qe > q0 && text[qe - 1] == '\r') qe--;
-        u64 ls = se - s0, lq = qe - q0;
+        u64 s0, q0, ls, lq;
+        fq_record_span(text, n_bytes, line_start, n_lines, r, s0, q0, ls, lq);
         if (text[line_start[4 * r]] != '@' || ls != lq) err = 1;
-        if (ls > MLST_MAX_READ_LEN) { err |= 2; ls = MLST_MAX_READ_LEN; }
+        if (TILE) { if (ls > tile_len) { err |= 4; ls = tile_len; } }
+        else if (ls > MLST_MAX_READ_LEN) { err |= 2; ls = MLST_MAX_READ_LEN; }
         const u64 o = pair_k ? (r < pair_k ? 2 * r : 2 * (r - pair_k) + 1) : r;
         seq_off[o] = s0; qual_off[o] = q0; lens[o] = (u16)ls;
         if ((u32)ls > mx) mx = (u32)ls;
@@ -3672,6 +3681,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "bam_dev.h"
 #include "bam_reads.h"
 #include "fasta_dev.h"
+#include "fastq_tile.h"
 
 // ================================================================== host side
 struct EvPair { hipEvent_t a, b; int which; };
@@ -3787,6 +3797,12 @@ struct mlst_handle {
     struct { FaDev* d_desc = nullptr; FaMeta* d_meta = nullptr; u8* h_fa = nullptr; u8* d_flat = nullptr; u64 cap_flat = 0;
              u32* d_kind = nullptr; u64* d_cseq = nullptr; u64* d_chdr = nullptr; u64 cap_cells = 0; u64* d_cstart = nullptr; u64* d_wcnt = nullptr; u64 cap_contigs = 0;
              u64 last_cells = 0, last_contigs = 0; u32 last_passes = 0; } fa;      // (last_*: mlst_debug_fasta_info; last_passes = 0: no call has reached the device)
+    // long FASTQ records cut into windows on the device (mlst_set_read_tiling; csrc/fastq_tile.h): the tile (0, 0 = off), the windows of
+    // one round (MLST_TILE_ROUND, read by mlst_create), the sample's counts (mlst_get_read_tiling_info), descriptor and results with their
+    // pinned mirrors (h_fqt: FqtDev, then FqtMeta), the per-record and per-workgroup tables, the windows' offsets of a round
+    struct { u32 read_len = 0, stride = 0; u64 round = 16ull << 20; u64 info[4] = {0, 0, 0, 0};
+             FqtDev* d_desc = nullptr; FqtMeta* d_meta = nullptr; u8* h_fqt = nullptr; u64* d_rlen = nullptr; u64* d_wex = nullptr; u64 cap_recs = 0;
+             u64* d_gsum = nullptr; u64 cap_groups = 0; u64* d_soff = nullptr; u64* d_qoff = nullptr; u64 cap_win = 0; } tile;
 };
 
 static std::string g_create_err;
@@ -3901,6 +3917,7 @@ extern "C" int mlst_create(int device, const mlst_params* p, mlst_handle** out) 
     h->own_stream = h->stream;
     { const char* g = getenv("MLST_GRAPHS"); if (g && g[0] == '0') h->use_graphs = false; }
     { const char* g = getenv("MLST_BGZF_CRC"); h->bgzf_verify = g && g[0] == '1'; }      // initial value of mlst_set_bgzf_verify
+    { const char* g = getenv("MLST_TILE_ROUND"); if (g && atoll(g) > 0) h->tile.round = (u64)atoll(g); }      // windows per round of a tiled FASTQ chunk: a memory bound
     { int khz = 0; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) h->wall_khz = (double)khz; }
     KParams& k = h->kp;
     k.minscore = prm.minscore; k.max_xm = prm.max_xm; k.min_read_len = prm.min_read_len; k.minqual = prm.minqual;
@@ -3970,6 +3987,8 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta);
     hipFree(h->fa.d_desc); hipFree(h->fa.d_meta); hipFree(h->fa.d_flat); hipFree(h->fa.d_kind); hipFree(h->fa.d_cseq); hipFree(h->fa.d_chdr); hipFree(h->fa.d_cstart); hipFree(h->fa.d_wcnt);
     if (h->fa.h_fa) hipHostFree(h->fa.h_fa);
+    hipFree(h->tile.d_desc); hipFree(h->tile.d_meta); hipFree(h->tile.d_rlen); hipFree(h->tile.d_wex); hipFree(h->tile.d_gsum); hipFree(h->tile.d_soff); hipFree(h->tile.d_qoff);
+    if (h->tile.h_fqt) hipHostFree(h->tile.h_fqt);
     hipFree(h->d_bgzf); hipFree(h->d_bgzf_blk); hipFree(h->d_fq_carry); h->d_bgzf = nullptr; h->d_bgzf_blk = nullptr; h->d_fq_carry = nullptr; h->cap_bgzf = h->cap_bgzf_blk = h->cap_fq_carry = h->fq_carry_len = 0;
     hipFree(h->d_packed); hipFree(h->d_qrows); hipFree(h->d_lens); hipFree(h->d_counts); hipFree(h->d_dist); hipFree(h->d_query);
     for (auto* g : {&h->g_submit, &h->g_typing}) if (g->exec) hipGraphExecDestroy(g->exec);
@@ -3987,6 +4006,7 @@ static int reset_sample_state(mlst_handle* h) {
     if (h->d_acc64 && h->n_alleles) HIPCHK(h, hipMemsetAsync(h->d_acc64, 0, (u64)h->n_alleles * 8, h->stream));      // (zero after every complete submission already: k_accumulate; this is for one that was cut short)
     h->reads_seen = 0; h->fq_carry_len = 0; h->max_wpr = 0;
     h->last_pack.n_reads = 0; h->last_pack.wpr = h->last_pack.qstride = 0;
+    for (u64& x : h->tile.info) x = 0;
     h->pc_len[0] = h->pc_len[1] = 0; h->pair_open = false;      // (mlst_submit_fastq_bgzf_pair: both files' carries)
     bam_drop(h, false);
     return MLST_OK;
@@ -4793,6 +4813,7 @@ static int next_text_slot(mlst_handle* h, u64 bytes) {
 }
 
 static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, int paired, uint64_t* n_reads_out);
+static int fq_tile_submit(mlst_handle* h, u64 n_bytes, u64 n_lines, u64 n_recs, int tslot, uint64_t* n_reads_out);
 // FASTQ text in h->d_fq_text[0 .. n_bytes) -> packed reads -> pass 1.  whole: the text consists of whole records; else
 // the partial record at its end is kept (h->d_fq_carry) for the next chunk.
 // pair_boundary != 0 (whole text only): the text is two mate files back to back, the second starting at that byte; both
@@ -4849,11 +4870,19 @@ static int fastq_pipeline(mlst_handle* h, u64 n_bytes, int paired, bool whole, u
     // lengths are needed before the packed buffers can be sized: worst-case row width first, then the real one
     int rc = ensure_pack_buffers(h, n_reads, 2, 8); if (rc) return rc;
     u32* d_flags = reinterpret_cast<u32*>(h->d_fq_meta + 1);
-    hipLaunchKernelGGL(k_fq_records, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, h->d_fq_text, (u64)n_bytes, h->d_fq_lines, n_lines, n_reads,
-                       h->d_fq_soff, h->d_fq_qoff, h->d_lens, d_flags, pair_k);
+    const bool tile = h->tile.read_len && !paired && !pair_boundary;      // mlst_set_read_tiling: unpaired text only
+    if (tile) hipLaunchKernelGGL(k_fq_records<true>, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, h->d_fq_text, (u64)n_bytes, h->d_fq_lines, n_lines, n_reads,
+                                 h->d_fq_soff, h->d_fq_qoff, h->d_lens, d_flags, pair_k, h->tile.read_len);
+    else hipLaunchKernelGGL(k_fq_records<false>, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, h->d_fq_text, (u64)n_bytes, h->d_fq_lines, n_lines, n_reads,
+                            h->d_fq_soff, h->d_fq_qoff, h->d_lens, d_flags, pair_k, 0u);
     u32 flags[2] = {0, 0};
     HIPCHK(h, hipMemcpyAsync(flags, d_flags, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (tile && !(flags[1] & 1)) {
+        h->tile.info[0] += n_reads;
+        if (flags[1] & 4) return fq_tile_submit(h, n_bytes, n_lines, n_reads, tslot, n_reads_out);      // a record to cut: csrc/fastq_tile.h
+        if (flags[0] > h->tile.info[3]) h->tile.info[3] = flags[0];      // (no record is longer than the tile: the chunk goes on as without the switch)
+    }
     if (flags[1] & 2) return fail(h, MLST_E_LIMIT, "a FASTQ read is longer than %d bases", MLST_MAX_READ_LEN);
     if (flags[1] & 1) return fail(h, MLST_E_INVALID, "malformed FASTQ: a record does not start with '@' or its sequence and quality lengths differ");
     return fq_pack_submit(h, n_reads, flags[0], tslot, paired, n_reads_out);
@@ -4881,6 +4910,62 @@ static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, i
     if (n_reads_out) *n_reads_out = n_reads;
     h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
     return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired);
+}
+
+// the tail of a FASTQ parse whose chunk holds a record longer than the tile (mlst_set_read_tiling; kernels: csrc/fastq_tile.h): windows
+// per record, their prefix sums, and the total back to the host -- the one synchronisation added, it sizes the buffers, as in
+// mlst_submit_fasta.  The windows are then emitted, packed and submitted in record order, at most h->tile.round of them at a time
+// (a bound on the pack buffers); the text slot is free behind the last round's k_pack_text.
+static int fq_tile_submit(mlst_handle* h, u64 n_bytes, u64 n_lines, u64 n_recs, int tslot, uint64_t* n_reads_out) {
+    auto& T = h->tile;
+    if (!T.d_desc) HIPCHK(h, dmalloc(&T.d_desc, (u64)1));
+    if (!T.d_meta) HIPCHK(h, dmalloc(&T.d_meta, (u64)1));
+    if (!T.h_fqt) { void* p = nullptr; HIPCHK(h, hipHostMalloc(&p, sizeof(FqtDev) + sizeof(FqtMeta), hipHostMallocDefault)); T.h_fqt = (u8*)p; }
+    const u64 n_groups = (n_recs + FQT_GROUP - 1) / FQT_GROUP;
+    // (tables of the chunk before are free: its last kernel that reads them was queued on this stream, and hipFree waits for the device)
+    if (T.cap_recs < n_recs) { hipFree(T.d_rlen); hipFree(T.d_wex); T.d_rlen = T.d_wex = nullptr; T.cap_recs = 0;
+                               HIPCHK(h, dmalloc(&T.d_rlen, n_recs)); HIPCHK(h, dmalloc(&T.d_wex, n_recs)); T.cap_recs = n_recs; }
+    if (T.cap_groups < n_groups) { hipFree(T.d_gsum); T.d_gsum = nullptr; T.cap_groups = 0; HIPCHK(h, dmalloc(&T.d_gsum, n_groups)); T.cap_groups = n_groups; }
+    FqtDev* D = (FqtDev*)T.h_fqt;      // (the copy of the chunk before has been waited for)
+    D->text = h->d_fq_text; D->lines = h->d_fq_lines; D->rs = h->d_fq_soff; D->rq = h->d_fq_qoff; D->rlen = T.d_rlen; D->wex = T.d_wex; D->gsum = T.d_gsum; D->meta = T.d_meta;
+    D->n_bytes = n_bytes; D->n_lines = n_lines; D->n_recs = n_recs; D->read_len = T.read_len; D->stride = T.stride;
+    HIPCHK(h, hipMemcpyAsync(T.d_desc, D, sizeof(FqtDev), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.d_meta, 0, sizeof(FqtMeta), h->stream));
+    {
+        Prof pf(h, 13);
+        hipLaunchKernelGGL(k_fqt_count, dim3((u32)n_groups), dim3(1024), 0, h->stream, (const FqtDev*)T.d_desc);
+        hipLaunchKernelGGL(k_fqt_scan, dim3(1), dim3(1024), 0, h->stream, (const FqtDev*)T.d_desc, n_groups);
+        hipLaunchKernelGGL(k_fqt_add, dim3((u32)n_groups), dim3(1024), 0, h->stream, (const FqtDev*)T.d_desc);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(T.h_fqt + sizeof(FqtDev), T.d_meta, sizeof(FqtMeta), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // the one host synchronisation the cut adds
+    FqtMeta m; memcpy(&m, T.h_fqt + sizeof(FqtDev), sizeof m);
+    const u64 total = m.n_windows;
+    if (total < n_recs || m.n_cut == 0 || m.n_cut > n_recs || m.max_len > T.read_len) return fail(h, MLST_E_HIP, "FASTQ window tables inconsistent");
+    if (total >= (1ull << 32)) return fail(h, MLST_E_LIMIT, "more than 2^32 windows from one FASTQ chunk");
+    const u32 max_len = m.max_len;
+    u32 wpr = (max_len + 15) / 16; if (wpr < 2) wpr = 2; wpr = (wpr + 1) & ~1u;
+    u32 qstride = (max_len + 7) & ~7u; if (qstride < 8) qstride = 8;
+    const u64 round = total < T.round ? total : T.round;
+    if (T.cap_win < round) { hipFree(T.d_soff); hipFree(T.d_qoff); T.d_soff = T.d_qoff = nullptr; T.cap_win = 0;
+                             HIPCHK(h, dmalloc(&T.d_soff, round)); HIPCHK(h, dmalloc(&T.d_qoff, round)); T.cap_win = round; }
+    for (u64 w0 = 0; w0 < total; w0 += round) {
+        const u64 n = total - w0 < round ? total - w0 : round;
+        { int rc = ensure_pack_buffers(h, n, wpr, qstride); if (rc) return rc; }      // (the first round is the largest: later ones find the buffers as they are)
+        { Prof pf(h, 14);
+          hipLaunchKernelGGL(k_fqt_emit, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const FqtDev*)T.d_desc, w0, w0 + n, T.d_soff, T.d_qoff, h->d_lens); }
+        { Prof pf(h, 6);
+          hipLaunchKernelGGL(k_pack_text, dim3(grid_for((n + 63) / 64, 1, 8192)), dim3(256), 0, h->stream, h->d_fq_text, (const u64*)T.d_soff, (const u64*)T.d_qoff,
+                             h->d_lens, n, h->d_packed, h->d_qrows, wpr, qstride); }
+        HIPCHK(h, hipGetLastError());
+        if (w0 + n == total) HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
+        h->last_pack.n_reads = n; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
+        { int rc = mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n, wpr, qstride, 0); if (rc) return rc; }
+    }
+    T.info[1] += m.n_cut; T.info[2] += total - (n_recs - m.n_cut); if (m.max_rec > T.info[3]) T.info[3] = m.max_rec;
+    if (n_reads_out) *n_reads_out = total;
+    return MLST_OK;
 }
 
 // ---- Host-packed input (VERDICT r3 missing 8).  FASTQ text costs the link 2 L + ~16 bytes per read, and all of
@@ -6260,6 +6345,29 @@ extern "C" int mlst_set_bgzf_verify(mlst_handle* h, int on) {
 extern "C" int mlst_get_bgzf_verify(mlst_handle* h, int* on) {
     if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
     *on = h->bgzf_verify ? 1 : 0;
+    return MLST_OK;
+}
+
+// long FASTQ records cut into windows (include/mlst.h; csrc/fastq_tile.h): like the CRC switch, the tile may change only between
+// streams -- the partial record a stream carries over was begun under the tile it will be finished with
+extern "C" int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t stride) {
+    if (!h) return MLST_E_INVALID;
+    if ((read_len == 0) != (stride == 0)) return fail(h, MLST_E_INVALID, "read_len and stride must both be positive (or both 0: no tiling)");
+    if (read_len > (u32)MLST_MAX_READ_LEN) return fail(h, MLST_E_LIMIT, "read_len %u exceeds %d bases", read_len, MLST_MAX_READ_LEN);
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    h->tile.read_len = read_len; h->tile.stride = stride;
+    return MLST_OK;
+}
+extern "C" int mlst_get_read_tiling(mlst_handle* h, uint32_t* read_len, uint32_t* stride) {
+    if (!h || !read_len || !stride) return fail(h, MLST_E_INVALID, "NULL argument");
+    *read_len = h->tile.read_len; *stride = h->tile.stride;
+    return MLST_OK;
+}
+extern "C" int mlst_get_read_tiling_info(mlst_handle* h, uint64_t out[4]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
+    for (int k = 0; k < 4; k++) out[k] = h->tile.info[k];
     return MLST_OK;
 }
 

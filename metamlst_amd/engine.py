@@ -135,6 +135,9 @@ def load_library(path: str | None = None):
         "mlst_debug_inflate_paths": (C.c_int, [H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mlst_set_bgzf_verify": (C.c_int, [H, C.c_int]),
         "mlst_get_bgzf_verify": (C.c_int, [H, C.POINTER(C.c_int)]),
+        "mlst_set_read_tiling": (C.c_int, [H, C.c_uint32, C.c_uint32]),
+        "mlst_get_read_tiling": (C.c_int, [H, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "mlst_get_read_tiling_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_submit_reads_device": (C.c_int, [H, u8p, u8p, u64p, C.c_uint64, C.c_uint32, C.c_int]),
         "mlst_pack_reads_device": (C.c_int, [H, u8p, u8p, u64p, C.c_uint64, u32p, u8p, u16p, C.c_uint32, C.c_uint32]),
         "mlst_submit_packed_device": (C.c_int, [H, u32p, u8p, u16p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int]),
@@ -637,6 +640,24 @@ class Engine:
         """Check the CRC-32 of every BGZF block on the GPU before its reads are typed (mlst_set_bgzf_verify; off by default,
         MLST_BGZF_CRC=1 switches it on for new engines).  Only while no stream is open."""
         self._check(self.lib.mlst_set_bgzf_verify(self._h, int(bool(on))), "mlst_set_bgzf_verify")
+
+    def set_read_tiling(self, read_len: int = 150, stride: int = 25) -> None:
+        """Cut FASTQ records longer than read_len bases into windows of read_len bases every stride bases on the GPU, each with its
+        slice of the quality line (mlst_set_read_tiling; the rule: fastq.tile_fastq).  0, 0 = off, the default.  Unpaired
+        submit_fastq / submit_fastq_stream / submit_fastq_bgzf only; may change only while no stream is open on the handle."""
+        self._check(self.lib.mlst_set_read_tiling(self._h, int(read_len), int(stride)), "mlst_set_read_tiling")
+
+    def get_read_tiling(self) -> tuple[int, int]:
+        """(read_len, stride) of set_read_tiling; (0, 0) = off"""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.lib.mlst_get_read_tiling(self._h, C.byref(a), C.byref(b)), "mlst_get_read_tiling")
+        return int(a.value), int(b.value)
+
+    def read_tiling_info(self) -> dict:
+        """Since the last reset_sample: records seen by tiled submissions, records cut, windows made of them, bases of the longest record"""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.mlst_get_read_tiling_info(self._h, out), "mlst_get_read_tiling_info")
+        return {"records": int(out[0]), "cut": int(out[1]), "windows": int(out[2]), "longest": int(out[3])}
 
     @property
     def bgzf_verify(self) -> bool:

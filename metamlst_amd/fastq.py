@@ -671,6 +671,50 @@ def tile_fasta(path: str, read_len: int = 150, stride: int = 25, min_len: int = 
         yield b"".join(out)
 
 
+def tile_fastq(path: str, read_len: int = 150, stride: int = 25, chunk_reads: int = 500_000):
+    """Long reads as input (merged pairs, amplicons, ONT / HiFi): the packed formats hold 320 bases, so a record of more than
+    read_len bases is cut into overlapping windows the way tile_fasta cuts a contig (read_len bases every stride bases, the last
+    window flush with the record's end), each window with the same slice of the quality line.  Yields FASTQ text in chunks of
+    chunk_reads records for Engine.submit_fastq.  Records keep their order; a record of at most read_len bases (an empty one
+    included) goes out unchanged as one record; there is no min_len (short reads are filtered where they always were).  Bases
+    are not touched (N, lower case: the parser's business); line ends become LF.  Window names: <name>_<0-based start>.
+    The windows are unpaired reads of their own (MLST_LONG_READ_WINDOWS, include/mlst_policy.h).  This is the rule
+    mlst_set_read_tiling applies on the device; it serves single-stream .gz input and the tests."""
+    if read_len < 1 or stride < 1:
+        raise ValueError("read_len and stride must be positive")
+    out, n_out = [], 0
+    with _open(path) as f:
+        while True:
+            h = f.readline()
+            if not h:
+                break
+            s = f.readline().rstrip(b"\r\n")
+            f.readline()
+            q = f.readline().rstrip(b"\r\n")
+            h = h.rstrip(b"\r\n")
+            if not h and not s and not q:
+                continue                                     # blank lines at the end of the file
+            if len(q) != len(s):
+                raise ValueError("FASTQ record with different sequence and quality lengths: %r" % h[:60])
+            n = len(s)
+            if n <= read_len:
+                out.append(b"%s\n%s\n+\n%s\n" % (h, s, q))
+                n_out += 1
+            else:
+                name = h.split()[0] if h.split() else b"@"
+                starts = list(range(0, n - read_len + 1, stride))
+                if starts[-1] != n - read_len:
+                    starts.append(n - read_len)
+                for st in starts:
+                    out.append(b"%s_%d\n%s\n+\n%s\n" % (name, st, s[st:st + read_len], q[st:st + read_len]))
+                n_out += len(starts)
+            if n_out >= chunk_reads:
+                yield b"".join(out)
+                out, n_out = [], 0
+    if out:
+        yield b"".join(out)
+
+
 def _bgzf_block_size(buf, off: int) -> int:
     """Total size of the BGZF block that starts at buf[off], 0 if the header is incomplete, -1 if it is not BGZF."""
     if len(buf) - off < 18:
