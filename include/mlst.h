@@ -179,7 +179,7 @@ int mlst_submit_fastq_bgzf_pair(mlst_handle* h, const uint8_t* data1, uint64_t n
 int mlst_set_bgzf_verify(mlst_handle* h, int on);
 int mlst_get_bgzf_verify(mlst_handle* h, int* on);
 
-/* ---- LONG READS: FASTQ records longer than a tile cut into windows on the GPU (csrc/fastq_tile.h) --------------------------------
+/* ---- LONG READS: FASTQ records and BAM reads longer than a tile cut into windows on the GPU (csrc/fastq_tile.h, csrc/bam_tile.h) ----
  * A read longer than MLST_MAX_READ_LEN (320) bases cannot be packed (the packed score's fields), and without this
  * switch every FASTQ entry fails it with MLST_E_LIMIT "a FASTQ read is longer than 320 bases".  mlst_set_read_tiling(h, read_len,
  * stride) switches tiling on for the handle (0, 0: off, the default -- nothing changes then and nothing more is launched, copied or
@@ -192,17 +192,37 @@ int mlst_get_bgzf_verify(mlst_handle* h, int* on);
  *     case, CR as without the switch), and a window's non-ACGT bit (bit 15 of lens) is its own.
  *   - windows are unpaired reads of their own (MLST_LONG_READ_WINDOWS, mlst_policy.h): read indices continue the handle's count in
  *     record order, then start order, and n_reads_out counts reads, i.e. windows plus uncut records.
+ * An UNPAIRED reads stream of a BAM (mlst_bam_reads_open with paired == 0) opened while the switch is on applies the same rule to the
+ * reads `samtools fastq` would write (metamlst_amd.samin.bam_reads_fastq, then tile_fastq) -- windows are cut from the READ, not from the
+ * stored SEQ (csrc/bam_tile.h):
+ *   - kept records keep their order; secondary, supplementary and empty records are skipped and counted as without the switch.
+ *   - a kept read of n <= read_len bases is one read, unchanged; one of n > read_len bases becomes the windows above.
+ *   - FLAG 0x10: the read is the reverse complement of SEQ with QUAL reversed, so window st of the read is bases n - 1 - st ... n - st - len
+ *     of SEQ, complemented; the window flush with the read's end lies at the front of the stored SEQ.
+ *   - a window's Phred values are the same slice of the read's, clamped to 127; a first quality byte of 0xFF gives Phred 1 to every base
+ *     of every window; non-ACGT nibbles pack as A with bit 7 in qrows, a window's bit 15 of lens is its own; the filler nibble of an
+ *     odd l_seq is never a base.
+ *   - read indices continue the handle's count in record order, then start order.  MLST_CNT_READS_SEEN and mlst_bam_reads_info[0] count
+ *     reads (windows plus uncut reads); n_records_out of mlst_submit_bam_bgzf keeps counting BAM records.
+ *   A piece (the blocks of one call) without a kept read longer than read_len goes exactly the way it goes without the switch; one with
+ *   such a read costs what a FASTQ chunk costs, below.  Unchanged: with the switch off, and on a PAIRED reads stream whatever the switch,
+ *   l_seq > 320 fails with MLST_E_LIMIT "a BAM read is longer than 320 bases"; a record larger than the 1 MiB head room
+ *   (MLST_BAM_MAX_RECORD: about 698,900 bases with qualities) fails with MLST_E_LIMIT "a BAM record of more than ... bytes"; a piece
+ *   that makes 2^32 windows or more fails with MLST_E_LIMIT.  A long read whose l_seq claims more bases and qualities than its
+ *   block_size holds ends the stream with MLST_E_INVALID "malformed BAM record <n>: its bases and qualities do not fit its size".
  * A chunk without a record longer than read_len goes the way it goes without the switch (one flag test).  A chunk with one costs three
  * small kernels, one host synchronisation (the window count sizes the buffers) and a kernel that writes every window's offsets;
  * the windows are packed and submitted in rounds of at most MLST_TILE_ROUND windows (environment, read by mlst_create; default
  * 16,777,216: a bound on the pack buffers, ~3.4 GB at 150 bases).  A chunk that makes 2^32 windows or more fails with MLST_E_LIMIT.
  * NOT tiled, a long record there fails with MLST_E_LIMIT as before: paired submissions (paired != 0, mlst_submit_fastq_pair,
- * mlst_submit_fastq_bgzf_pair), the reads of a BAM (mlst_bam_reads_open), mlst_submit_reads / mlst_submit_reads_device and the
+ * mlst_submit_fastq_bgzf_pair), paired reads streams of a BAM (mlst_bam_reads_open with paired != 0), mlst_submit_reads /
+ * mlst_submit_reads_device and the
  * host-packed entries (mlst_pack_fastq_host, mlst_submit_packed_host, mlst_submit_packed_device).
  * Refused: read_len or stride of 0 when the other is not (MLST_E_INVALID); read_len > 320 (MLST_E_LIMIT); a change while a FASTQ or
- * BAM stream is open on the handle (MLST_E_INVALID "a FASTQ stream is open", as mlst_set_bgzf_verify).
- * mlst_get_read_tiling_info: since the last mlst_reset_sample, out[0] = records seen by tiled submissions, out[1] = records cut,
- * out[2] = windows made of them, out[3] = bases of the longest record. */
+ * BAM stream is open on the handle (MLST_E_INVALID "a FASTQ stream is open", as mlst_set_bgzf_verify): the switch governs the streams
+ * opened after it.
+ * mlst_get_read_tiling_info: since the last mlst_reset_sample, out[0] = records seen by tiled submissions (FASTQ records, and the kept
+ * records of tiled reads streams), out[1] = records cut, out[2] = windows made of them, out[3] = bases of the longest record. */
 int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t stride);
 int mlst_get_read_tiling(mlst_handle* h, uint32_t* read_len, uint32_t* stride);
 int mlst_get_read_tiling_info(mlst_handle* h, uint64_t out[4]);
@@ -361,7 +381,9 @@ int mlst_bam_pileup_fetch(mlst_handle* h, uint32_t* counts);
  *     1 <-> 8 and 2 <-> 4; anything else stays non-ACGT.
  *   - Phred: the raw byte clamped to 0..127 (what the text path makes of chr(q + 33)).  A first quality byte of 0xFF means no
  *     qualities: every base gets Phred 1 (the default of samtools fastq -v).
- *   - l_seq > 320 (MLST_MAX_READ_LEN): MLST_E_LIMIT "a BAM read is longer than 320 bases"; the stream ends.
+ *   - l_seq > 320 (MLST_MAX_READ_LEN): MLST_E_LIMIT "a BAM read is longer than 320 bases"; the stream ends.  Not so on an unpaired
+ *     stream opened behind mlst_set_read_tiling: there a read longer than the tile is cut into windows (LONG READS above), and
+ *     mlst_bam_reads_info[0] counts windows plus uncut reads.  A paired stream is never tiled.
  *   - the read index is the number of reads kept before it: locus_first_read and mlst_set_read_index_base as after FASTQ.
  *   - ref_id, pos, CIGAR and the optional fields are stepped over.
  * mlst_bam_reads_open: n_ref = the header's reference count (0 for an unaligned BAM; it bounds the ref_id of a plausible record
@@ -500,7 +522,8 @@ int mlst_import_stats_device_async(mlst_handle* h, const int64_t* d_sum, const i
 int mlst_set_profiling(mlst_handle* h, int on);   /* 0 = off, 1 = events + sieve window, 2 = sieve window only (keeps the hipGraph replay of the launch sequences, which event profiling turns off) */
 /* Per-kernel device time measured with HIP events on the engine's stream.
  * which: 0=sieve (all its kernels) 1=seed 2=extend (k_extend + k_extend_pairs) 3=banded-SW 4=accumulate 5=pileup 6=pack 12=k_ext_prep (the item records of k_extend);
- * 13 = k_fqt_count + k_fqt_scan + k_fqt_add and 14 = k_fqt_emit (long reads cut into windows, csrc/fastq_tile.h; outside 6); 9 = k_route, 10 =
+ * 13 = k_fqt_count (a BAM piece: k_bamt_count) + k_fqt_scan + k_fqt_add and 14 = k_fqt_emit (k_bamt_emit) (long reads cut into windows,
+ * csrc/fastq_tile.h, csrc/bam_tile.h; outside 6); 9 = k_route, 10 =
  * k_route_probe and 11 = k_route_verify, the three kernels of the routed sieve (inside 0) (events bracket the launch on the engine's
  * stream, so with several engines on one GPU they include the time a kernel queues behind another stream's kernel);
  * 7 = the sieve's execution window measured inside the kernel (wall clock at the first workgroup's start and the last

@@ -61,7 +61,7 @@
 #define MLST_BAM_MAX_RECORD (1048576 - 64)   /* largest BAM record (block_size): the head room of a piece, MLST_E_LIMIT beyond */
 
 /* ---- long reads (mlst_set_read_tiling) ---- */
-#define MLST_LONG_READ_WINDOWS  1   /* a FASTQ record longer than the tile is typed as overlapping windows that are unpaired reads of
+#define MLST_LONG_READ_WINDOWS  1   /* a FASTQ record or a BAM read longer than the tile is typed as overlapping windows that are unpaired reads of
                                        their own, exactly as a contig's windows are: one long read that covers a locus adds several
                                        records and several sequenceBank lengths to it, where bowtie2 would report one local alignment
                                        per allele.  The reference states nothing for reads its aligner handles and the packed score

@@ -3,6 +3,7 @@
     python -m metamlst_amd.cli type  SAMPLE.fastq[.gz] [-2 MATES.fastq] -d DB [-o out] [--penalty ...]   (metamlst.py:34-49)
     python -m metamlst_amd.cli type  READS.bam -d DB [-o out]            (the reads of a BAM, as `samtools fastq` takes them)
     python -m metamlst_amd.cli type  LONG.fastq --long-reads [--tile LEN,STEP] -d DB   (reads longer than 320 bases, cut into windows)
+    python -m metamlst_amd.cli type  HIFI.bam --long-bam-reads [--tile LEN,STEP] -d DB  (the same for the reads of an unaligned BAM)
     python -m metamlst_amd.cli merge FOLDER -d DB [-z 5] [--filter ...] [--meta ...] [--idField ...]       (metamlst-merge.py:35-49)
     python -m metamlst_amd.cli index -d DB [-s seqs.fasta,...] [-t typings.txt,...] [-q dump.fa] [--list]   (metamlst-index.py:24-33)
 
@@ -44,6 +45,10 @@ def _type_parser(sub):
                    help="READS holds reads longer than the 320 bases a packed read takes (merged pairs, amplicons, ONT / HiFi): a record "
                         "longer than LEN is cut into overlapping windows (--tile LEN,STEP; 300,150 suits merged pairs) that keep their "
                         "slice of the quality line and are typed as unpaired reads of their own; shorter records are typed as they are")
+    p.add_argument("--long-bam-reads", dest="long_bam_reads", action="store_true",
+                   help="--long-reads for the reads of BAM files (PacBio HiFi, ONT, merged pairs kept as unaligned BAM): the reads "
+                        "`samtools fastq` would write are cut into windows (--tile LEN,STEP) on the GPU; every READS file is a BAM "
+                        "of unpaired reads, one sample each")
     p.add_argument("--tile", default="150,25", metavar="LEN,STEP")
     p.add_argument("-2", dest="mates",
                    help="second FASTQ of a paired-end sample: record k of it is the mate of record k of READS.  Mates are aligned as "
@@ -158,7 +163,7 @@ def _parse_tile(text: str):
 
 
 def run_type(a, argv=None) -> int:
-    tile = long_reads = None
+    tile = long_reads = long_bam = None
     if a.long_reads:
         if a.mates or a.alignments or a.contigs:
             print("--long-reads takes unpaired FASTQ: it goes with none of -2, --alignments and --contigs")
@@ -168,6 +173,16 @@ def run_type(a, argv=None) -> int:
             return 1
         if long_reads[0] > 320:
             print("--tile LEN,STEP: a window of --long-reads holds at most 320 bases, not %d" % long_reads[0])
+            return 1
+    if a.long_bam_reads:
+        if a.mates or a.alignments or a.contigs or a.long_reads or a.gpus > 1:
+            print("--long-bam-reads takes the unpaired reads of BAM files on one GPU: it goes with none of -2, --alignments, --contigs, --long-reads and --gpus N")
+            return 1
+        long_bam = _parse_tile(a.tile)
+        if long_bam is None:
+            return 1
+        if long_bam[0] > 320:
+            print("--tile LEN,STEP: a window of --long-bam-reads holds at most 320 bases, not %d" % long_bam[0])
             return 1
     if a.contigs:
         if a.mates or a.alignments:
@@ -188,9 +203,19 @@ def run_type(a, argv=None) -> int:
     a.READS, extra_files = samples[0][0], samples[0][1:]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     has_bam = not a.alignments and not a.contigs and any(_is_reads_bam(f) for smp in samples for f in smp)
-    if has_bam and long_reads:
-        print("--long-reads takes FASTQ: the reads of a BAM are packed whole (convert it with `samtools fastq`)")
+    if has_bam and a.long_reads:
+        print("--long-reads takes FASTQ: the long reads of a BAM are cut into windows by --long-bam-reads")
         return 1
+    if a.long_bam_reads:      # every file a BAM of unpaired reads: windows are unpaired reads of their own
+        from .samin import bam_first_read_flags
+        for f in (f for smp in samples for f in smp):
+            if not _is_reads_bam(f):
+                print("--long-bam-reads takes BAM files: %s is none (FASTQ goes with --long-reads)" % f)
+                return 1
+            flags = bam_first_read_flags(f)
+            if flags is not None and flags & 1:
+                print("--long-bam-reads takes unpaired reads: the first read of %s carries FLAG 0x1 (a paired BAM is typed as pairs without the switch)" % f)
+                return 1
     if has_bam and a.mates:
         print("-2 names the second FASTQ file of a pair: the mates of a BAM are records of the BAM itself (collate it by name)")
         return 1
@@ -219,8 +244,8 @@ def run_type(a, argv=None) -> int:
         return 1
     eng = Engine(a.device, prm)
     eng.set_bgzf_verify(a.verify_crc)
-    if long_reads:
-        eng.set_read_tiling(*long_reads)
+    if long_reads or long_bam:
+        eng.set_read_tiling(*(long_reads or long_bam))
     # the built host index is kept next to the database (as the reference keeps <idx>.1.bt2: metamlst-index.py:224-225) unless a
     # species filter made this index a one-off or MLST_INDEX_CACHE=0
     ref_cache = (a.database + ".mlstref") if (not a.filter and os.environ.get("MLST_INDEX_CACHE", "1") != "0") else ""
@@ -240,8 +265,8 @@ def run_type(a, argv=None) -> int:
             e2 = Engine(a.device, prm)
             e2.load_reference(idx)      # (the host index is cached inside the library: an upload, not a build)
             e2.set_bgzf_verify(a.verify_crc)
-            if long_reads:
-                e2.set_read_tiling(*long_reads)
+            if long_reads or long_bam:
+                e2.set_read_tiling(*(long_reads or long_bam))
             if a.depth_cap:
                 e2.set_depth_cap(a.depth_cap)
             engines.append(e2)
@@ -251,7 +276,8 @@ def run_type(a, argv=None) -> int:
     if many:
         from .multigpu import type_many_samples
         rc = type_many_samples(engines, idx, database, targs, samples, rank, world, a.o, a.log, chunk_bytes,
-                               printer=None if a.quiet else (lambda results: _print_results(a, results)), tile=tile, long_reads=long_reads)
+                               printer=None if a.quiet else (lambda results: _print_results(a, results)), tile=tile, long_reads=long_reads,
+                               long_bam_reads=long_bam)
         database.closeConnection()
         return rc
     if a.alignments:
@@ -306,7 +332,7 @@ def run_type(a, argv=None) -> int:
         return 0
     # FASTQ text goes to the GPU as is and is parsed there (mlst_submit_fastq); a reader thread stays two chunks ahead
     try:
-        submit_sample_files(eng, paths, paired, chunk_bytes, report=None if a.quiet else print, long_reads=long_reads)
+        submit_sample_files(eng, paths, paired, chunk_bytes, report=None if a.quiet else print, long_reads=long_reads, long_bam_reads=long_bam)
     except CorruptInput as e:      # nothing of the sample is typed: no .nfo
         print(e, file=sys.stderr)
         database.closeConnection()
@@ -350,16 +376,28 @@ def _is_reads_bam(path: str) -> bool:
     return os.path.isfile(path) and is_bgzf_bam(path)
 
 
-def submit_bam_reads(eng, path: str, report=None) -> int:
+def submit_bam_reads(eng, path: str, report=None, long_reads=None) -> int:
     """The reads of a BGZF BAM into one engine (Engine.submit_bam_reads_file): as pairs iff the first record kept carries FLAG 0x1
-    (decided on the first record, as mates_share_names does for mate files).  report: called with one line on what was taken."""
+    (decided on the first record, as mates_share_names does for mate files).  report: called with one line on what was taken.
+    long_reads = (read_len, stride): the reads are unpaired and those longer than read_len are cut into windows on the GPU
+    (Engine.set_read_tiling); the line then says how many were cut into how many windows."""
     from .samin import bam_first_read_flags
     flags = bam_first_read_flags(path)
     paired = bool(flags is not None and flags & 1)
+    if long_reads is not None:
+        if paired:
+            raise ValueError("long BAM reads are unpaired: the first read of %s carries FLAG 0x1" % path)
+        if eng.get_read_tiling() != tuple(long_reads):
+            eng.set_read_tiling(*long_reads)
+        before = eng.read_tiling_info()
     n = crc_checked([path], lambda: eng.submit_bam_reads_file(path, paired=paired))
     if report is not None:
         _, n_sec, n_empty, _ = eng.bam_reads_info()
-        report("%s: %d reads taken%s, %d secondary / supplementary and %d empty records skipped" % (path, n, " as pairs" if paired else "", n_sec, n_empty))
+        line = "%s: %d reads taken%s, %d secondary / supplementary and %d empty records skipped" % (path, n, " as pairs" if paired else "", n_sec, n_empty)
+        if long_reads is not None:
+            info = eng.read_tiling_info()
+            line += ", %d longer than %d cut into %d windows" % (info["cut"] - before["cut"], long_reads[0], info["windows"] - before["windows"])
+        report(line)
     return n
 
 
@@ -380,12 +418,20 @@ def submit_contigs(eng, path: str, tile) -> int:
     return n
 
 
-def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader=None, report=None, tile=None, long_reads=None) -> None:
+def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader=None, report=None, tile=None, long_reads=None,
+                        long_bam_reads=None) -> None:
     """All reads of one sample's file(s) into one engine: FASTQ (first_reader: open_sample_reader(paths, ...), if opened ahead), or
     BAMs whose records are taken as reads (report: see submit_bam_reads).  tile = (read_len, stride, min_len): the files are
     assemblies (FASTA), cut into windows on the GPU (submit_contigs).  long_reads = (read_len, stride): unpaired FASTQ whose records
     longer than read_len are cut into windows on the GPU (Engine.set_read_tiling: plain text and bgzip on the device path, single-
-    stream .gz inflated on the host as always and cut on the device); report gets one line on what was cut."""
+    stream .gz inflated on the host as always and cut on the device); report gets one line on what was cut.  long_bam_reads =
+    (read_len, stride): the files are BAMs of unpaired reads, cut into windows the same way (submit_bam_reads)."""
+    if long_bam_reads is not None:
+        if paired or not all(_is_reads_bam(p) for p in paths):
+            raise ValueError("long BAM reads are the unpaired reads of BAM files")
+        for path in paths:
+            submit_bam_reads(eng, path, report, long_reads=long_bam_reads)
+        return
     if tile is not None:
         for path in paths:
             submit_contigs(eng, path, tile)

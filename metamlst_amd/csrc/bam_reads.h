@@ -10,27 +10,31 @@
 //                  strand and "no qualities" bits and its record index; the longest read, the skipped records by kind, and the
 //                  first record that cannot be taken (atomicMin on record index << 4 | reason, as bam_flag does)
 //   k_bamr_mates : paired streams: reads 2k and 2k + 1 carry the same QNAME, byte by byte
-//   k_bamr_pack  : k_pack_text for nibble input: 4-bit bases -> the resident 2-bit rows, raw Phred -> qrows, lens
+//   k_bamr_pack  : k_pack_text for nibble input: 4-bit bases -> the resident 2-bit rows, raw Phred -> qrows, lens; its windowed
+//                  instantiation packs windows of reads (mlst_set_read_tiling on an unpaired stream: csrc/bam_tile.h)
 // The offsets of SEQ and QUAL follow from the record's start and three bytes of its head (l_read_name, n_cigar_op); k_bamr_pack
 // derives them once per read into LDS instead of k_bamr_select storing them per record of the piece.
-// gfx950 build (hipcc -O3): no kernel of this file uses scratch; the register / LDS figures are in profiles/bam_reads.md.
+// gfx950 build (hipcc -O3): no kernel of this file uses scratch; the register / LDS figures are in profiles/bam_reads.md
+// and, with those of the windowed pack, in profiles/bam_long_reads.md.
 // Bytes of the text are loaded one by one and assembled (records have no alignment); no unaligned wide loads.
 #ifndef MLST_BAM_READS_H
 #define MLST_BAM_READS_H
 
 // reasons a reads stream ends at a record (low 4 bits of BamReadsMeta.err_key)
-#define BAMR_ERR_LONG   1u                /* l_seq > MLST_MAX_READ_LEN */
+#define BAMR_ERR_LONG   1u                /* l_seq > MLST_MAX_READ_LEN (tiling off, or a paired stream) */
 #define BAMR_ERR_MATE   2u                /* paired: no FLAG bit 0x1, another QNAME than its neighbour's, or no neighbour at the file's end */
-// BamReadsMeta.info of a kept read
-#define BAMR_REV        (1u << 16)        /* FLAG 0x10: stored on the reference strand */
-#define BAMR_NOQUAL     (1u << 17)        /* first quality byte 0xFF: no qualities */
+#define BAMR_ERR_SPAN   3u                /* tiling on: l_seq > MLST_MAX_READ_LEN and SEQ + QUAL do not fit the record's block_size */
+// rd_info of a kept read: l_seq (a record is at most BAM_REC_MAX = 2^20 - 64 bytes: l_seq < 2^20) and two flags
+#define BAMR_LEN        0x3FFFFFFFu
+#define BAMR_REV        (1u << 30)        /* FLAG 0x10: stored on the reference strand */
+#define BAMR_NOQUAL     (1u << 31)        /* first quality byte 0xFF: no qualities */
 
 struct BamReadsMeta {       // device-resident, next to BamMeta, lives as long as the stream
     u64 err_key;            // smallest (record index << 4 | BAMR_ERR_*) (~0: none)
     u64 n_secondary;        // records skipped for FLAG 0x100 / 0x800 (all pieces)
     u64 n_empty;            // records skipped for l_seq == 0 (all pieces)
     u32 n_reads;            // this piece: kept records (even on a paired stream)
-    u32 max_len;            // this piece: its longest read
+    u32 max_len;            // this piece: l_seq of its longest kept read (32 bits hold every l_seq the record split lets through: < 2^20)
 };
 
 // 0: a read; 1: secondary / supplementary; 2: no bases
@@ -97,7 +101,7 @@ __global__ __launch_bounds__(1024) void k_bamr_scan(const u8* __restrict__ text,
 
 __global__ __launch_bounds__(256) void k_bamr_select(const u8* __restrict__ text, u32 n_cells, const BamMeta* __restrict__ meta, BamReadsMeta* __restrict__ rm,
                                                      const u32* __restrict__ count, const u32* __restrict__ base, const u32* __restrict__ list, const u32* __restrict__ kbase,
-                                                     u32* __restrict__ rd_rec, u32* __restrict__ rd_info, u32* __restrict__ rd_ridx, int paired) {
+                                                     u32* __restrict__ rd_rec, u32* __restrict__ rd_info, u32* __restrict__ rd_ridx, int paired, int tiled) {
     __shared__ u32 s_w[4];
     const u64 rec_base = meta->rec_total; const u32 n_rec = meta->n_rec, n_reads = rm->n_reads;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -115,8 +119,14 @@ __global__ __launch_bounds__(256) void k_bamr_select(const u8* __restrict__ text
                 else {
                     keep = true;
                     const u32 flag = bam_ld16(text + s + 18), lseq = bam_ld32(text + s + 20);
-                    const u32 q0 = s + 36u + text[s + 12] + 4u * bam_ld16(text + s + 16) + (lseq + 1u) / 2u;
-                    if (lseq > (u32)MLST_MAX_READ_LEN) atomicMin((unsigned long long*)&rm->err_key, (unsigned long long)(((rec_base + b + j) << 4) | BAMR_ERR_LONG));
+                    const u32 var = 36u + text[s + 12] + 4u * bam_ld16(text + s + 16);      // bytes in front of SEQ, block_size included
+                    const u32 q0 = s + var + (lseq + 1u) / 2u;
+                    // tiled (mlst_set_read_tiling on an unpaired stream): a long read is cut into windows later -- if its SEQ and QUAL lie inside
+                    // the record (a short read reaches at most 480 bytes past its head, which the slack behind the text covers, as before)
+                    u32 bad = 0;
+                    if (lseq > (u32)MLST_MAX_READ_LEN)
+                        bad = !tiled ? BAMR_ERR_LONG : ((u64)var + ((u64)lseq + 1u) / 2u + lseq > (u64)bam_ld32(text + s) + 4u ? BAMR_ERR_SPAN : 0u);
+                    if (bad) atomicMin((unsigned long long*)&rm->err_key, (unsigned long long)(((rec_base + b + j) << 4) | bad));
                     else {
                         info = lseq | ((flag & 0x10u) ? BAMR_REV : 0u) | (text[q0] == 0xFFu ? BAMR_NOQUAL : 0u);
                         if (lseq > c_max) c_max = lseq;
@@ -161,30 +171,41 @@ __global__ __launch_bounds__(256) void k_bamr_mates(const u8* __restrict__ text,
 // for a read stored on the reference strand, back to front with the complement.  Nibbles 1 2 4 8 are A C G T; every other one is a
 // non-ACGT base (packed as A, bit 7 of its quality byte, bit 15 of the length).  Phase two: the words leave LDS in the resident
 // (transposed) order; one thread per read stores its length.
-__global__ __launch_bounds__(256) void k_bamr_pack(const u8* __restrict__ text, const u32* __restrict__ rd_rec, const u32* __restrict__ rd_info, u64 n_reads,
+// WIN: the rows are windows of reads (k_bamt_emit, csrc/bam_tile.h): win_a[r] = record start | rd_info << 32, win_b[r] = the window's
+// start in the READ | its length << 32.  Base p of a window is base st + p of the read; where that lies in SEQ / QUAL follows from
+// the read's l_seq, the word count and lens from the window's length.  !WIN: win_a = rd_rec, win_b = rd_info, a window is its read.
+template <bool WIN>
+__global__ __launch_bounds__(256) void k_bamr_pack(const u8* __restrict__ text, const void* __restrict__ win_a, const void* __restrict__ win_b, u64 n_reads,
                                                    u32* __restrict__ packed, u8* __restrict__ qrows, u16* __restrict__ lens, u32 wpr, u32 qstride) {
-    __shared__ u32 s_words[64 * RW]; __shared__ u32 s_anyn[2]; __shared__ u32 s_seq[64], s_info[64];
+    __shared__ u32 s_words[64 * RW]; __shared__ u32 s_anyn[2]; __shared__ u32 s_seq[64], s_info[64]; __shared__ u32 s_st[WIN ? 64 : 1], s_wl[WIN ? 64 : 1];
     const int tid = threadIdx.x;
     const u64 n_groups = (n_reads + 63) >> 6; const u32 total = 64u * wpr;
     for (u64 grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
         if (tid < 2) s_anyn[tid] = 0;
         if (tid < 64) {
             const u64 r = grp * 64 + tid; u32 seq = 0, info = 0;
-            if (r < n_reads) { const u32 s = rd_rec[r]; info = rd_info[r]; seq = s + 36u + text[s + 12] + 4u * bam_ld16(text + s + 16); }
+            u32 s = 0, st = 0, wl = 0;
+            if (r < n_reads) {
+                if (WIN) { const u64 a = ((const u64*)win_a)[r], b = ((const u64*)win_b)[r]; s = (u32)a; info = (u32)(a >> 32); st = (u32)b; wl = (u32)(b >> 32); }
+                else { s = ((const u32*)win_a)[r]; info = ((const u32*)win_b)[r]; }
+                seq = s + 36u + text[s + 12] + 4u * bam_ld16(text + s + 16);
+            }
             s_seq[tid] = seq; s_info[tid] = info;
+            if (WIN) { s_st[tid] = st; s_wl[tid] = wl; }
         }
         __syncthreads();
         for (u32 idx = (u32)tid; idx < total; idx += 256u) {
             const u32 i = idx / wpr, w = idx - i * wpr; const u64 r = grp * 64 + i;
-            const u32 info = s_info[i]; const int n = (int)(info & 0xFFFFu);
+            const u32 info = s_info[i]; const int n = (int)(info & BAMR_LEN);      // bases of the read
+            const int st = WIN ? (int)s_st[i] : 0, wl = WIN ? (int)s_wl[i] : n;      // the window: its first base in the read, its bases
             u32 word = 0;
             if (r < n_reads) {
                 u32 qw[4] = {0, 0, 0, 0}, anyn = 0;
-                if ((int)(w * 16u) < n) {
+                if ((int)(w * 16u) < wl) {
                     const bool rev = (info & BAMR_REV) != 0, noq = (info & BAMR_NOQUAL) != 0;
                     const u8* __restrict__ sq = text + s_seq[i]; const u8* __restrict__ ql = sq + ((u32)n + 1u) / 2u;
-                    // base p = w * 16 + k of the read is base hi - k (reverse) or lo + k (forward) of SEQ
-                    const int lo = (int)(w * 16u), hi = n - 1 - lo;
+                    // base p = w * 16 + k of the window is base lo + k of the read: base hi - k (reverse) or lo + k (forward) of SEQ
+                    const int lo = st + (int)(w * 16u), hi = n - 1 - lo;
                     const int first = rev ? hi - 15 : lo;                       // (may be negative: those bases lie beyond the read)
                     const int b0 = first >> 1, n_bytes = (n + 1) >> 1;          // (arithmetic shift: floor)
                     u64 nibs = 0; u32 nib16 = 0;                                // nibbles 2 * b0 ... 2 * b0 + 15 (the first one on top), and the 17th
@@ -194,7 +215,7 @@ __global__ __launch_bounds__(256) void k_bamr_pack(const u8* __restrict__ text, 
                     #pragma unroll
                     for (int k = 0; k < 16; k++) {
                         const int sp = rev ? hi - k : lo + k;                   // position in SEQ / QUAL
-                        if (lo + k < n) {                                       // (the filler nibble of an odd l_seq is never a base)
+                        if ((int)(w * 16u) + k < wl) {                          // (st + wl <= n: the filler nibble of an odd l_seq is never a base)
                             const int t = sp - 2 * b0;                          // 0 .. 16
                             const u32 nib = t < 16 ? (u32)(nibs >> (t < 16 ? 60 - 4 * t : 0)) & 15u : nib16;
                             u32 code = nib == 1u ? 0u : nib == 2u ? 1u : nib == 4u ? 2u : nib == 8u ? 3u : 4u;
@@ -217,7 +238,7 @@ __global__ __launch_bounds__(256) void k_bamr_pack(const u8* __restrict__ text, 
         __syncthreads();
         u32* out = packed + grp * total;
         for (u32 o = (u32)tid; o < total; o += 256u) out[o] = s_words[((o >> 1) & 63u) * wpr + ((o >> 7) << 1) + (o & 1u)];
-        if (tid < 64) { const u64 r = grp * 64 + tid; if (r < n_reads) lens[r] = (u16)((s_info[tid] & 0xFFFFu) | (((s_anyn[tid >> 5] >> (tid & 31)) & 1u) << 15)); }
+        if (tid < 64) { const u64 r = grp * 64 + tid; if (r < n_reads) lens[r] = (u16)((WIN ? s_wl[tid] : (s_info[tid] & BAMR_LEN)) | (((s_anyn[tid >> 5] >> (tid & 31)) & 1u) << 15)); }
         __syncthreads();
     }
 }

@@ -3682,6 +3682,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "bam_reads.h"
 #include "fasta_dev.h"
 #include "fastq_tile.h"
+#include "bam_tile.h"
 
 // ================================================================== host side
 struct EvPair { hipEvent_t a, b; int which; };
@@ -3797,7 +3798,8 @@ struct mlst_handle {
     struct { FaDev* d_desc = nullptr; FaMeta* d_meta = nullptr; u8* h_fa = nullptr; u8* d_flat = nullptr; u64 cap_flat = 0;
              u32* d_kind = nullptr; u64* d_cseq = nullptr; u64* d_chdr = nullptr; u64 cap_cells = 0; u64* d_cstart = nullptr; u64* d_wcnt = nullptr; u64 cap_contigs = 0;
              u64 last_cells = 0, last_contigs = 0; u32 last_passes = 0; } fa;      // (last_*: mlst_debug_fasta_info; last_passes = 0: no call has reached the device)
-    // long FASTQ records cut into windows on the device (mlst_set_read_tiling; csrc/fastq_tile.h): the tile (0, 0 = off), the windows of
+    // long FASTQ records and long BAM reads cut into windows on the device (mlst_set_read_tiling; csrc/fastq_tile.h, csrc/bam_tile.h;
+    // a handle has one of the two streams open at a time, they share these tables): the tile (0, 0 = off), the windows of
     // one round (MLST_TILE_ROUND, read by mlst_create), the sample's counts (mlst_get_read_tiling_info), descriptor and results with their
     // pinned mirrors (h_fqt: FqtDev, then FqtMeta), the per-record and per-workgroup tables, the windows' offsets of a round
     struct { u32 read_len = 0, stride = 0; u64 round = 16ull << 20; u64 info[4] = {0, 0, 0, 0};
@@ -4916,16 +4918,22 @@ static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, i
 // per record, their prefix sums, and the total back to the host -- the one synchronisation added, it sizes the buffers, as in
 // mlst_submit_fasta.  The windows are then emitted, packed and submitted in record order, at most h->tile.round of them at a time
 // (a bound on the pack buffers); the text slot is free behind the last round's k_pack_text.
-static int fq_tile_submit(mlst_handle* h, u64 n_bytes, u64 n_lines, u64 n_recs, int tslot, uint64_t* n_reads_out) {
+// the window tables of a chunk (a BAM piece) of n_recs records, grown as needed: descriptor, results, per-record and per-workgroup tables
+static int tile_tables(mlst_handle* h, u64 n_recs, u64 n_groups) {
     auto& T = h->tile;
     if (!T.d_desc) HIPCHK(h, dmalloc(&T.d_desc, (u64)1));
     if (!T.d_meta) HIPCHK(h, dmalloc(&T.d_meta, (u64)1));
     if (!T.h_fqt) { void* p = nullptr; HIPCHK(h, hipHostMalloc(&p, sizeof(FqtDev) + sizeof(FqtMeta), hipHostMallocDefault)); T.h_fqt = (u8*)p; }
-    const u64 n_groups = (n_recs + FQT_GROUP - 1) / FQT_GROUP;
     // (tables of the chunk before are free: its last kernel that reads them was queued on this stream, and hipFree waits for the device)
     if (T.cap_recs < n_recs) { hipFree(T.d_rlen); hipFree(T.d_wex); T.d_rlen = T.d_wex = nullptr; T.cap_recs = 0;
                                HIPCHK(h, dmalloc(&T.d_rlen, n_recs)); HIPCHK(h, dmalloc(&T.d_wex, n_recs)); T.cap_recs = n_recs; }
     if (T.cap_groups < n_groups) { hipFree(T.d_gsum); T.d_gsum = nullptr; T.cap_groups = 0; HIPCHK(h, dmalloc(&T.d_gsum, n_groups)); T.cap_groups = n_groups; }
+    return MLST_OK;
+}
+static int fq_tile_submit(mlst_handle* h, u64 n_bytes, u64 n_lines, u64 n_recs, int tslot, uint64_t* n_reads_out) {
+    auto& T = h->tile;
+    const u64 n_groups = (n_recs + FQT_GROUP - 1) / FQT_GROUP;
+    { int rc = tile_tables(h, n_recs, n_groups); if (rc) return rc; }
     FqtDev* D = (FqtDev*)T.h_fqt;      // (the copy of the chunk before has been waited for)
     D->text = h->d_fq_text; D->lines = h->d_fq_lines; D->rs = h->d_fq_soff; D->rq = h->d_fq_qoff; D->rlen = T.d_rlen; D->wex = T.d_wex; D->gsum = T.d_gsum; D->meta = T.d_meta;
     D->n_bytes = n_bytes; D->n_lines = n_lines; D->n_recs = n_recs; D->read_len = T.read_len; D->stride = T.stride;
@@ -5808,6 +5816,7 @@ struct BamStream {
     BamEntry* d_entries = nullptr; u64 cap_entries = 0, entries_done = 0, bound_pend = 0; u32 last_carry = 0;
     int* d_allele_slot = nullptr; u64 cap_slot = 0; u32* d_counts = nullptr; u64 cap_counts = 0, n_cols = 0; bool counts_ready = false;
     u64 rewalked = 0;
+    u32 tile_len = 0, tile_stride = 0;      // a reads stream: the handle's tile when it was opened unpaired (0, 0: reads are packed whole)
     bool reads = false; int paired = 0; BamReadsMeta* d_rmeta = nullptr; u64 reads_done = 0, n_secondary = 0, n_empty = 0;      // mlst_bam_reads_open
     u64* d_sort_k[2] = {nullptr, nullptr}; u32* d_sort_v[2] = {nullptr, nullptr}; void* d_sort_tmp = nullptr; u64 cap_sort = 0, cap_sort_tmp = 0;      // bam_bank's buffers, kept between streams
 };
@@ -6079,6 +6088,10 @@ extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_
 // inflate stream) and finished here, on the engine's stream, by the next call on the handle (or bam_flush): record split as for
 // alignments, then the records that are reads are chosen and numbered, mates checked, and -- after the one host synchronisation
 // that sizes the pack buffers (read count, longest read), as fastq_pipeline has for its line count -- packed and submitted to pass 1.
+// Tiling on (an unpaired stream opened behind mlst_set_read_tiling): a piece whose longest kept read exceeds the tile goes through
+// bamr_tile_submit instead -- windows per kept read, their prefix sums, the total back to the host (the one synchronisation the cut
+// adds), then rounds of emit / pack / submit as in fq_tile_submit; every other piece goes exactly the way it goes without the switch.
+static int bamr_tile_submit(mlst_handle* h, BamSlot& S, const u32* rd_rec, const u32* rd_info, u64 n_recs, u32 longest);
 static int bamr_finish(mlst_handle* h, uint64_t* n_records_out) {
     BamStream* B = h->bam;
     B->pend = false;
@@ -6098,7 +6111,7 @@ static int bamr_finish(mlst_handle* h, uint64_t* n_records_out) {
     hipLaunchKernelGGL(k_bamr_scan, dim3(1), dim3(1024), 0, st, (const u8*)S.d_text, text_end, n_cells, B->d_meta, B->d_rmeta, (const u32*)d_count, (const u32*)d_base,
                        (const u32*)S.d_list, (const u32*)d_kept, d_kbase, B->paired, S.final_piece ? 1 : 0);
     hipLaunchKernelGGL(k_bamr_select, dim3(std::min(n_cells, 8192u)), dim3(256), 0, st, (const u8*)S.d_text, n_cells, (const BamMeta*)B->d_meta, B->d_rmeta, (const u32*)d_count,
-                       (const u32*)d_base, (const u32*)S.d_list, (const u32*)d_kbase, rd_rec, rd_info, rd_ridx, B->paired);
+                       (const u32*)d_base, (const u32*)S.d_list, (const u32*)d_kbase, rd_rec, rd_info, rd_ridx, B->paired, B->tile_len ? 1 : 0);
     if (B->paired) hipLaunchKernelGGL(k_bamr_mates, dim3(1024), dim3(256), 0, st, (const u8*)S.d_text, (const BamMeta*)B->d_meta, B->d_rmeta, (const u32*)rd_rec, (const u32*)rd_ridx);
     HIPCHK(h, hipMemcpyAsync(S.h_res + 16, B->d_meta, sizeof(BamMeta), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipMemcpyAsync(S.h_res + 16 + sizeof(BamMeta), B->d_rmeta, sizeof(BamReadsMeta), hipMemcpyDeviceToHost, st));
@@ -6118,16 +6131,26 @@ static int bamr_finish(mlst_handle* h, uint64_t* n_records_out) {
     if (r.err_key != ~0ull) {
         bam_drop(h, false);
         if ((r.err_key & 15u) == BAMR_ERR_LONG) return fail(h, MLST_E_LIMIT, "a BAM read is longer than %d bases", MLST_MAX_READ_LEN);
+        if ((r.err_key & 15u) == BAMR_ERR_SPAN) return fail(h, MLST_E_INVALID, "malformed BAM record %llu: its bases and qualities do not fit its size", (unsigned long long)(r.err_key >> 4));
         return fail(h, MLST_E_INVALID, "record %llu has no mate next to it (a paired BAM must be collated by name)", (unsigned long long)(r.err_key >> 4));
     }
     B->last_carry = m.carry_len; B->rewalked = m.rewalked; B->n_secondary = r.n_secondary; B->n_empty = r.n_empty;
     if (n_records_out) *n_records_out += m.n_rec;
     const u64 n_reads = r.n_reads;
+    if (B->tile_len && n_reads) {
+        h->tile.info[0] += n_reads;
+        if (r.max_len > B->tile_len) {      // a read to cut: csrc/bam_tile.h
+            const int rc = bamr_tile_submit(h, S, rd_rec, rd_info, n_reads, r.max_len);
+            if (rc) bam_drop(h, false);
+            return rc;
+        }
+        if (r.max_len > h->tile.info[3]) h->tile.info[3] = r.max_len;      // (no read is longer than the tile: the piece goes on as without the switch)
+    }
     if (n_reads) {
         u32 wpr = (r.max_len + 15) / 16; if (wpr < 2) wpr = 2; wpr = (wpr + 1) & ~1u;
         u32 qstride = (r.max_len + 7) & ~7u; if (qstride < 8) qstride = 8;
         { int rc = ensure_pack_buffers(h, n_reads, wpr, qstride); if (rc) { bam_drop(h, false); return rc; } }
-        hipLaunchKernelGGL(k_bamr_pack, dim3(grid_for((n_reads + 63) / 64, 1, 8192)), dim3(256), 0, st, (const u8*)S.d_text, (const u32*)rd_rec, (const u32*)rd_info, n_reads,
+        hipLaunchKernelGGL(k_bamr_pack<false>, dim3(grid_for((n_reads + 63) / 64, 1, 8192)), dim3(256), 0, st, (const u8*)S.d_text, (const void*)rd_rec, (const void*)rd_info, n_reads,
                            h->d_packed, h->d_qrows, h->d_lens, wpr, qstride);
         HIPCHK(h, hipGetLastError());
         h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
@@ -6138,6 +6161,54 @@ static int bamr_finish(mlst_handle* h, uint64_t* n_records_out) {
         if (rc) { bam_drop(h, false); return rc; }
         B->reads_done += n_reads;
     }
+    return MLST_OK;
+}
+
+// the tail of a reads piece that holds a kept read longer than the tile: fq_tile_submit with the kept-read table in place of the line
+// table.  Rows are as wide as the tile in every round (the piece's longest read exceeds it); the slot is free behind the LAST round's
+// pack, which is also the one last_pack describes.
+static int bamr_tile_submit(mlst_handle* h, BamSlot& S, const u32* rd_rec, const u32* rd_info, u64 n_recs, u32 longest) {
+    BamStream* B = h->bam; auto& T = h->tile; hipStream_t st = h->stream;
+    const u64 n_groups = (n_recs + FQT_GROUP - 1) / FQT_GROUP;
+    { int rc = tile_tables(h, n_recs, n_groups); if (rc) return rc; }
+    FqtDev* D = (FqtDev*)T.h_fqt;      // (the copy of the piece before has been waited for)
+    memset(D, 0, sizeof(FqtDev));
+    D->wex = T.d_wex; D->gsum = T.d_gsum; D->meta = T.d_meta; D->n_recs = n_recs; D->read_len = B->tile_len; D->stride = B->tile_stride;
+    HIPCHK(h, hipMemcpyAsync(T.d_desc, D, sizeof(FqtDev), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemsetAsync(T.d_meta, 0, sizeof(FqtMeta), st));
+    {
+        Prof pf(h, 13);
+        hipLaunchKernelGGL(k_bamt_count, dim3((u32)n_groups), dim3(1024), 0, st, (const FqtDev*)T.d_desc, rd_info);
+        hipLaunchKernelGGL(k_fqt_scan, dim3(1), dim3(1024), 0, st, (const FqtDev*)T.d_desc, n_groups);
+        hipLaunchKernelGGL(k_fqt_add, dim3((u32)n_groups), dim3(1024), 0, st, (const FqtDev*)T.d_desc);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(T.h_fqt + sizeof(FqtDev), T.d_meta, sizeof(FqtMeta), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));      // the one host synchronisation the cut adds
+    FqtMeta m; memcpy(&m, T.h_fqt + sizeof(FqtDev), sizeof m);
+    const u64 total = m.n_windows;
+    if (total <= n_recs || m.n_cut == 0 || m.n_cut > n_recs || m.max_len != B->tile_len || m.max_rec != longest) return fail(h, MLST_E_HIP, "BAM window tables inconsistent");
+    if (total >= (1ull << 32)) return fail(h, MLST_E_LIMIT, "more than 2^32 windows from one piece of a BAM");
+    const u32 max_len = m.max_len;
+    u32 wpr = (max_len + 15) / 16; if (wpr < 2) wpr = 2; wpr = (wpr + 1) & ~1u;
+    u32 qstride = (max_len + 7) & ~7u; if (qstride < 8) qstride = 8;
+    const u64 round = total < T.round ? total : T.round;
+    if (T.cap_win < round) { hipFree(T.d_soff); hipFree(T.d_qoff); T.d_soff = T.d_qoff = nullptr; T.cap_win = 0;
+                             HIPCHK(h, dmalloc(&T.d_soff, round)); HIPCHK(h, dmalloc(&T.d_qoff, round)); T.cap_win = round; }
+    for (u64 w0 = 0; w0 < total; w0 += round) {
+        const u64 n = total - w0 < round ? total - w0 : round;
+        { int rc = ensure_pack_buffers(h, n, wpr, qstride); if (rc) return rc; }      // (the first round is the largest: later ones find the buffers as they are)
+        { Prof pf(h, 14);
+          hipLaunchKernelGGL(k_bamt_emit, dim3(grid_for(n, 256)), dim3(256), 0, st, (const FqtDev*)T.d_desc, rd_rec, rd_info, w0, w0 + n, T.d_soff, T.d_qoff); }
+        hipLaunchKernelGGL(k_bamr_pack<true>, dim3(grid_for((n + 63) / 64, 1, 8192)), dim3(256), 0, st, (const u8*)S.d_text, (const void*)T.d_soff, (const void*)T.d_qoff, n,
+                           h->d_packed, h->d_qrows, h->d_lens, wpr, qstride);
+        HIPCHK(h, hipGetLastError());
+        if (w0 + n == total) HIPCHK(h, hipEventRecord(S.ev_free, st));      // the slot's buffers may be overwritten from here on
+        h->last_pack.n_reads = n; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
+        { int rc = mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n, wpr, qstride, 0); if (rc) return rc; }
+    }
+    T.info[1] += m.n_cut; T.info[2] += total - (n_recs - m.n_cut); if (m.max_rec > T.info[3]) T.info[3] = m.max_rec;
+    B->reads_done += total;
     return MLST_OK;
 }
 
@@ -6162,6 +6233,7 @@ extern "C" int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (m and r are this frame's)
     B->counts_ready = false;
     B->open = true; B->pend = false; B->first = true; B->pass = 1; B->n_ref = n_ref; B->skip = skip_bytes; B->reads = true; B->paired = paired;
+    B->tile_len = paired ? 0u : h->tile.read_len; B->tile_stride = paired ? 0u : h->tile.stride;      // (mlst_set_read_tiling refuses while the stream is open)
     B->entries_done = B->bound_pend = 0; B->s[0].bound = B->s[1].bound = 0; B->last_carry = 0;
     B->reads_done = B->n_secondary = B->n_empty = 0; B->rewalked = 0;
     return MLST_OK;
@@ -6355,6 +6427,8 @@ extern "C" int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t 
     if ((read_len == 0) != (stride == 0)) return fail(h, MLST_E_INVALID, "read_len and stride must both be positive (or both 0: no tiling)");
     if (read_len > (u32)MLST_MAX_READ_LEN) return fail(h, MLST_E_LIMIT, "read_len %u exceeds %d bases", read_len, MLST_MAX_READ_LEN);
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    // (a reads stream took its tile when it was opened: include/mlst.h gives one message for every stream of reads)
+    if (bam_is_open(h) && h->bam->reads) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (the reads stream of a BAM: its last chunk was not marked final)");
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
     h->tile.read_len = read_len; h->tile.stride = stride;
     return MLST_OK;

@@ -493,7 +493,9 @@ class Engine:
     def submit_bam_reads_file(self, path: str, paired: bool = False, chunk_bytes: int = 64 << 20) -> int:
         """Pass 1 over the READS of a BGZF BAM (the rules of `samtools fastq`, include/mlst.h): inflated, chosen, strand-corrected
         and packed on the device; returns the reads submitted (bam_reads_info() has the records skipped).  paired: the reads kept
-        come as neighbours with one QNAME and are submitted as pairs.  With set_bgzf_verify on, the blocks of the header are
+        come as neighbours with one QNAME and are submitted as pairs.  With set_read_tiling on and paired False, a read longer
+        than the tile is cut into windows on the device (the rule: samin.bam_reads_fastq, then fastq.tile_fastq); the count
+        returned is then windows plus uncut reads, read_tiling_info() has the reads cut.  With set_bgzf_verify on, the blocks of the header are
         checked on the host (fastq.BgzfCrcError), those of the records on the device."""
         from .samin import read_bam_header
         names, lo, skip = read_bam_header(path, self.bgzf_verify)      # (the header's blocks are the host's to check)
@@ -642,9 +644,11 @@ class Engine:
         self._check(self.lib.mlst_set_bgzf_verify(self._h, int(bool(on))), "mlst_set_bgzf_verify")
 
     def set_read_tiling(self, read_len: int = 150, stride: int = 25) -> None:
-        """Cut FASTQ records longer than read_len bases into windows of read_len bases every stride bases on the GPU, each with its
-        slice of the quality line (mlst_set_read_tiling; the rule: fastq.tile_fastq).  0, 0 = off, the default.  Unpaired
-        submit_fastq / submit_fastq_stream / submit_fastq_bgzf only; may change only while no stream is open on the handle."""
+        """Cut FASTQ records and BAM reads longer than read_len bases into windows of read_len bases every stride bases on the GPU,
+        each with its slice of the qualities (mlst_set_read_tiling; the rule: fastq.tile_fastq, for a BAM applied to the reads
+        samin.bam_reads_fastq writes).  0, 0 = off, the default.  Unpaired submit_fastq / submit_fastq_stream / submit_fastq_bgzf
+        and unpaired BAM reads streams (bam_reads_open, submit_bam_reads_file) only; may change only while no stream is open on
+        the handle."""
         self._check(self.lib.mlst_set_read_tiling(self._h, int(read_len), int(stride)), "mlst_set_read_tiling")
 
     def get_read_tiling(self) -> tuple[int, int]:
@@ -654,7 +658,8 @@ class Engine:
         return int(a.value), int(b.value)
 
     def read_tiling_info(self) -> dict:
-        """Since the last reset_sample: records seen by tiled submissions, records cut, windows made of them, bases of the longest record"""
+        """Since the last reset_sample: records (FASTQ records, kept BAM reads) seen by tiled submissions, records cut, windows made of
+        them, bases of the longest record"""
         out = (C.c_uint64 * 4)()
         self._check(self.lib.mlst_get_read_tiling_info(self._h, out), "mlst_get_read_tiling_info")
         return {"records": int(out[0]), "cut": int(out[1]), "windows": int(out[2]), "longest": int(out[3])}

@@ -214,7 +214,8 @@ def deal_samples(sizes: list[int], world: int) -> list[int]:
 
 
 def type_many_samples(engines, idx, database, targs, samples: list[list[str]], rank: int, world: int, out_dir: str, log: bool,
-                      chunk_bytes: int, printer=None, timing: dict | None = None, tile=None, long_reads=None) -> int:
+                      chunk_bytes: int, printer=None, timing: dict | None = None, tile=None, long_reads=None,
+                      long_bam_reads=None) -> int:
     """Multi-sample mode (BASELINE configs[3]: "RCCL gather of per-species ST tables"; the reference's real use is many
     samples into one folder, one metamlst.py run each, metamlst-merge.py:93-107 reads the folder).  Whole samples are
     dealt to the ranks -- no collective on the data path --, every rank sends its samples through the pipelined typing
@@ -223,7 +224,8 @@ def type_many_samples(engines, idx, database, targs, samples: list[list[str]], r
     rank 0 gathers the .nfo lines (and --log tables) and writes them, sample by sample in the order given: byte for
     byte what one run per sample writes.  tile = (read_len, stride, min_len): the samples are assemblies (FASTA files), cut into
     windows on the GPU (cli.submit_contigs).  long_reads = (read_len, stride): FASTQ records longer than read_len are cut into windows
-    on the GPU (Engine.set_read_tiling, made sure of per engine by cli.submit_sample_files)."""
+    on the GPU (Engine.set_read_tiling, made sure of per engine by cli.submit_sample_files).  long_bam_reads = (read_len, stride): the
+    samples are BAMs of unpaired reads, cut into windows the same way."""
     import time
     from .cli import submit_sample_files
     from .pipeline import TypingPipeline
@@ -256,7 +258,7 @@ def type_many_samples(engines, idx, database, targs, samples: list[list[str]], r
         try:
             # (a BAM's "reads taken" line: unless --quiet, as for a single sample; feeder threads print whole lines)
             submit_sample_files(e, job[1], False, chunk_bytes, report=None if printer is None else (lambda line: print(line, flush=True)), tile=tile,
-                                long_reads=long_reads)
+                                long_reads=long_reads, long_bam_reads=long_bam_reads)
         except CorruptInput as ex:
             print(ex, file=sys.stderr, flush=True)
             corrupt.add(job[0])
