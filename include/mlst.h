@@ -361,12 +361,55 @@ int mlst_pileup_alignments(mlst_handle* h, const uint32_t* chosen_allele_idx, ui
  *   stream is open.
  * mlst_bam_set_capacity: most accepted records on known loci a pass-1 stream may list for sequenceBank (32 bytes each, allocated
  *   as the file needs them; 0 = default 2^26); MLST_E_CAPACITY beyond it.
- * mlst_bam_pileup_fetch: the counts of a finished pass-2 stream, layout of mlst_pileup (alleles in the order given). */
+ * mlst_bam_pileup_fetch: the counts of the finished pass-2 stream, BAM or SAM (mlst_sam_open below), layout of mlst_pileup (alleles in
+ *   the order given). */
 int mlst_bam_open(mlst_handle* h, int pass, const int32_t* ref_allele, const int32_t* ref_locus, const uint8_t* ref_flags, uint32_t n_ref,
                   uint32_t skip_bytes, const uint32_t* chosen_allele_idx, uint32_t n_chosen);
 int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_t n_bytes, int final_chunk, uint64_t* n_records_out, uint64_t* n_consumed_out);
 int mlst_bam_set_capacity(mlst_handle* h, uint64_t max_entries);
 int mlst_bam_pileup_fetch(mlst_handle* h, uint32_t* counts);
+
+/* ---- ready-made alignments straight from SAM text (what the documented bowtie2 command writes with -S) -------------------------------
+ * The text is streamed twice like a BAM (pass 1: metamlst.py:101-130, pass 2: the pile-up of the chosen contigs), and parsed on the
+ * GPU (csrc/sam_dev.h): line starts from the newline table of the FASTQ parser, then one thread per line.  Device memory is the text
+ * of one chunk plus the sequenceBank list, whatever the file's size.  The rules are samin.AlignmentSample's (its _iter_sam_lines, add
+ * and pileup), and a line the device cannot treat exactly as that reader would is never guessed (below).
+ * mlst_sam_open: names / name_off[n_ref + 1] are the SN: names of the file's @SQ lines, back to back (name i = bytes name_off[i] ..
+ *   name_off[i + 1], name_off[0] = 0, under 4 GiB in all); ref_allele / ref_locus / ref_flags per name as for mlst_bam_open.  The
+ *   library builds an open-addressing hash table of the names (a power of two of slots, at least 2 * n_ref) and uploads it with the
+ *   names: the device hashes a line's RNAME, probes, and takes a hit only when length and bytes agree.  A name that comes twice
+ *   keeps its first entry.  pass, chosen_allele_idx, n_chosen as for mlst_bam_open.  Refuses while any other stream is open; while a
+ *   SAM stream is open the other submit entries, mlst_bam_open, mlst_bam_reads_open, mlst_bam_set_capacity, mlst_set_bgzf_verify
+ *   and mlst_set_read_tiling refuse ("a SAM stream is open ...").
+ * mlst_submit_sam_text: the file's bytes from its first byte on (header lines included), cut anywhere; the partial line at a chunk's
+ *   end stays on the device and is completed by the next chunk.  The last call passes final_chunk != 0 (its text may be empty, and
+ *   its last line need not end with LF).  A call is finished when it returns; n_records_out = record lines completed by it.
+ *   - a line ends with LF; a CR directly in front of it is no part of the line.  A line whose first byte is '@' is no record,
+ *     wherever it stands.  The record index (locus_first_read, error messages) is the number of record lines in front.
+ *   - columns are cut at TAB.  The 12th and the 15th column are taken BY POSITION (Q1); their value is the text between the second
+ *     colon and the third colon or the column's end (split(":")[2]).  len(SEQ) is the byte length of column 10: '*' counts 1.
+ *     Species filter, accept test, counters, per-allele sums, locus_first and sequenceBank (QNAME key: MLST_BAM_QNAME_KEY) as for
+ *     mlst_submit_bam_bgzf; mlst_bam_set_capacity bounds the list of either format.
+ *   - pass 2, records on a chosen contig: AS and XM are taken BY NAME among columns 12 and later (a column counts when it holds
+ *     two colons and its first part is the tag; the last occurrence wins; an absent tag fails the test); POS - 1 is the leftmost
+ *     column; the CIGAR text is walked as mlst_pileup_alignments walks its operations (M = X count, I S advance the read, D N the
+ *     reference, H P nothing, '*' no operation); the base is the SEQ byte & 0xDF, Phred the QUAL byte - 33, QUAL '*' Phred 0.
+ *   - a line longer than MLST_BAM_MAX_RECORD bytes (its LF not counted): MLST_E_LIMIT "a SAM line of more than ... bytes".
+ *   - NEVER GUESSED.  Each of these ends the stream with MLST_E_INVALID "host path needed: <reason> at record <n>", the smallest
+ *     record index first; the caller runs the host reader, which raises or answers as the reference does:
+ *       a CR that does not stand directly in front of an LF, in any line (Python ends a line there);
+ *       a byte >= 0x80 or a NUL in a record line;  fewer than 15 columns (an empty line is such a line);
+ *       FLAG, POS, the 12th or the 15th column's value not of the form -?[0-9]{1,9} (int() also takes "+5", " 5", "5_0");
+ *       an RNAME that is not among the names (or '*'), or one that does not split in three at '_' (ref_flags bit 1);
+ *       on a loaded contig (ref_allele >= 0), in either pass: an AS or XM column found by name whose value is no such integer, a
+ *       CIGAR byte that is neither a digit nor one of MIDNSHP=X, an operation length >= 2^28 (the host reader parses all three
+ *       for every record it keeps);
+ *       pass 2, on a loaded contig: QUAL neither '*' nor as long as SEQ; on a chosen contig: a QUAL byte below 33.
+ *   After any error the stream is closed and the sample's state is undefined (mlst_reset_sample). */
+int mlst_sam_open(mlst_handle* h, int pass, const uint8_t* names, const uint64_t* name_off /* n_ref + 1 */,
+                  const int32_t* ref_allele, const int32_t* ref_locus, const uint8_t* ref_flags, uint32_t n_ref,
+                  const uint32_t* chosen_allele_idx, uint32_t n_chosen);
+int mlst_submit_sam_text(mlst_handle* h, const uint8_t* text, uint64_t n_bytes, int final_chunk, uint64_t* n_records_out);
 
 /* ---- the READS of a BGZF BAM (unaligned BAMs, the unmapped remainder of a host depletion, a BAM aligned to something else) -----
  * The records are taken as reads the way `samtools fastq` takes them with its defaults, chosen, strand-corrected and packed on the
@@ -523,7 +566,8 @@ int mlst_set_profiling(mlst_handle* h, int on);   /* 0 = off, 1 = events + sieve
 /* Per-kernel device time measured with HIP events on the engine's stream.
  * which: 0=sieve (all its kernels) 1=seed 2=extend (k_extend + k_extend_pairs) 3=banded-SW 4=accumulate 5=pileup 6=pack 12=k_ext_prep (the item records of k_extend);
  * 13 = k_fqt_count (a BAM piece: k_bamt_count) + k_fqt_scan + k_fqt_add and 14 = k_fqt_emit (k_bamt_emit) (long reads cut into windows,
- * csrc/fastq_tile.h, csrc/bam_tile.h; outside 6); 9 = k_route, 10 =
+ * csrc/fastq_tile.h, csrc/bam_tile.h; outside 6); 15 = the line table of a SAM chunk (k_fq_count, k_fq_scan, k_fq_lines, k_sam_flags), 16 =
+ * k_sam_accumulate and 17 = k_sam_pileup (csrc/sam_dev.h; two entries of 15 per chunk); 9 = k_route, 10 =
  * k_route_probe and 11 = k_route_verify, the three kernels of the routed sieve (inside 0) (events bracket the launch on the engine's
  * stream, so with several engines on one GPU they include the time a kernel queues behind another stream's kernel);
  * 7 = the sieve's execution window measured inside the kernel (wall clock at the first workgroup's start and the last

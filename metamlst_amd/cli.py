@@ -282,19 +282,24 @@ def run_type(a, argv=None) -> int:
         return rc
     if a.alignments:
         from .engine import HostPathNeeded
-        from .samin import AlignmentSample, BamSample, is_bgzf_bam
-        if is_bgzf_bam(a.READS):      # inflate, record split, accumulation and pile-up on the device (two passes over the file)
+        from .samin import AlignmentSample, BamSample, SamSample, is_bgzf_bam, is_sam_text, read_sam_header
+        # a BGZF BAM: inflate, record split, accumulation and pile-up on the device; SAM text (plain or .gz): line table, parse,
+        # accumulation and pile-up on the device (two passes over the file either way).  SAM text without @SQ lines gives the
+        # device no names to look an RNAME up in: its first record would come back as "host path needed", so the host reader
+        # takes such a file at once, as before
+        Device = BamSample if is_bgzf_bam(a.READS) else SamSample if is_sam_text(a.READS) and read_sam_header(a.READS) else None
+        if Device is not None:
             def said(e):      # which path typed the sample is the user's to know: the host reader is ~10^3 times slower
                 print("%s: %s -- reading the file on the host instead" % (a.READS, str(e).split(": ", 1)[-1]), file=sys.stderr)
 
             def device_pileup(chosen):
                 try:
                     return crc_checked([a.READS], lambda: bam.pileup(eng, chosen))
-                except HostPathNeeded as e:      # (pass 2 only: an AS / XM tag by name that is no integer.  The statistics stay the
-                    said(e)                      # device's -- pass 1 treated every record; the host reader is built for the pile-up alone)
+                except HostPathNeeded as e:      # (pass 2 only: a BAM's AS / XM tag by name that is no integer, a SAM line's QUAL.  The statistics stay
+                    said(e)                      # the device's -- pass 1 treated every record; the host reader is built for the pile-up alone)
                     return AlignmentSample(idx, targs).add_file(a.READS).pileup(eng, chosen)
             try:
-                bam = crc_checked([a.READS], lambda: BamSample(idx, targs, eng).add_file(a.READS))
+                bam = crc_checked([a.READS], lambda: Device(idx, targs, eng).add_file(a.READS))
                 return _finish_type(a, idx, database, targs, bam.stats(), device_pileup)
             except HostPathNeeded as e:      # a record only the host reader treats: today's path, which raises or answers as the reference
                 said(e)

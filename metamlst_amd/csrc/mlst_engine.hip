@@ -3679,6 +3679,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 }
 
 #include "bam_dev.h"
+#include "sam_dev.h"
 #include "bam_reads.h"
 #include "fasta_dev.h"
 #include "fastq_tile.h"
@@ -3788,7 +3789,7 @@ struct mlst_handle {
     GraphSlot g_submit, g_typing; bool use_graphs = true;
     std::vector<EvPair> events;
     std::vector<hipEvent_t> ev_pool;
-    double k_ms[16] = {0}; u64 k_n[16] = {0};      // see mlst_get_kernel_time
+    double k_ms[20] = {0}; u64 k_n[20] = {0};      // see mlst_get_kernel_time
     double wall_khz = 100000.0;                  // wall_clock64 rate (hipDeviceAttributeWallClockRate)
     struct BamStream* bam = nullptr;             // BAM input (mlst_bam_open / mlst_submit_bam_bgzf), allocated by the first stream
     u32 bam_force_miss = 0; u64 bam_max_entries = 0;      // mlst_debug_bam_split, mlst_bam_set_capacity
@@ -3822,6 +3823,7 @@ static void bz_free(mlst_handle* h);
 static int bam_flush(mlst_handle* h);     // BAM input: the piece in flight is finished (its errors are this call's)
 static void bam_drop(mlst_handle* h, bool release);      // the BAM stream is closed and forgotten (release: its buffers too)
 static bool bam_is_open(const mlst_handle* h);
+static const char* bam_kind(const mlst_handle* h);      // "BAM" or "SAM": what the open stream of ready-made alignments takes
 template <typename T> static hipError_t dmalloc(T** p, u64 n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
 template <typename T> static hipError_t dmalloc(GP<T>* p, u64 n) { return hipMalloc((void**)&p->p, (n ? n : 1) * sizeof(T)); }
 
@@ -4763,7 +4765,7 @@ static int h2d_overlapped(mlst_handle* h, void* d_dst, const void* src, u64 n, h
 extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, const uint8_t* d_quals, const uint64_t* d_off,
                                         uint64_t n_reads, uint32_t max_len, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     hipSetDevice(h->device);
     if (n_reads == 0) return MLST_OK;
@@ -4778,7 +4780,7 @@ extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, 
 extern "C" int mlst_submit_reads(mlst_handle* h, const uint8_t* bases, const uint8_t* quals, const uint64_t* off,
                                  uint64_t n_reads, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (n_reads == 0) return MLST_OK;
     if (!bases || !quals || !off) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -5051,7 +5053,7 @@ extern "C" int mlst_pack_fastq_host(const uint8_t* text, uint64_t n_bytes, uint3
 extern "C" int mlst_submit_packed_host(mlst_handle* h, const uint32_t* packed, const uint8_t* qrows, const uint16_t* lens, uint64_t n_reads,
                                        uint32_t wpr, uint32_t qstride, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (!packed || !qrows || !lens) return fail(h, MLST_E_INVALID, "NULL argument");
     hipSetDevice(h->device);
@@ -5164,7 +5166,7 @@ extern "C" int mlst_submit_fastq(mlst_handle* h, const uint8_t* text, uint64_t n
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (n_reads_out) *n_reads_out = 0;
     if (n_bytes == 0) return MLST_OK;
     if (!text) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -5182,7 +5184,7 @@ extern "C" int mlst_submit_fastq_stream(mlst_handle* h, const uint8_t* text, uin
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (n_reads_out) *n_reads_out = 0;
     if (n_bytes && !text) return fail(h, MLST_E_INVALID, "NULL argument");
     const u64 total = h->fq_carry_len + n_bytes;
@@ -5201,7 +5203,7 @@ extern "C" int mlst_submit_fastq_pair(mlst_handle* h, const uint8_t* text1, uint
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (n_reads_out) *n_reads_out = 0;
     if (n1 == 0 && n2 == 0) return MLST_OK;
     if (!text1 || !text2 || n1 == 0 || n2 == 0) return fail(h, MLST_E_INVALID, "mate files hold different numbers of records (one chunk is empty)");
@@ -5373,7 +5375,7 @@ extern "C" int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint6
                                       uint64_t* n_consumed_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     if (h->pair_open) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (n_reads_out) *n_reads_out = 0;
     if (n_consumed_out) *n_consumed_out = 0;
     if (n_bytes && !data) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -5660,7 +5662,7 @@ static int bzp_submit(mlst_handle* h, const u8* data1, u64 n1, const u8* data2, 
 extern "C" int mlst_submit_fastq_bgzf_pair(mlst_handle* h, const uint8_t* data1, uint64_t n1, const uint8_t* data2, uint64_t n2, int final_chunk,
                                            uint64_t* n_reads_out, uint64_t* n_consumed1_out, uint64_t* n_consumed2_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (n_reads_out) *n_reads_out = 0;
     if (n_consumed1_out) *n_consumed1_out = 0;
     if (n_consumed2_out) *n_consumed2_out = 0;
@@ -5819,10 +5821,17 @@ struct BamStream {
     u32 tile_len = 0, tile_stride = 0;      // a reads stream: the handle's tile when it was opened unpaired (0, 0: reads are packed whole)
     bool reads = false; int paired = 0; BamReadsMeta* d_rmeta = nullptr; u64 reads_done = 0, n_secondary = 0, n_empty = 0;      // mlst_bam_reads_open
     u64* d_sort_k[2] = {nullptr, nullptr}; u32* d_sort_v[2] = {nullptr, nullptr}; void* d_sort_tmp = nullptr; u64 cap_sort = 0, cap_sort_tmp = 0;      // bam_bank's buffers, kept between streams
+    // a stream of SAM text (mlst_sam_open; csrc/sam_dev.h): slot 0's text, the carry, the tables and the list are the BAM stream's.  The
+    // header's names (hash table, offsets, arena), the line table (newlines per FQ_BLOCK, line starts, record lines per 256 lines,
+    // two totals) and what the host keeps between chunks (records so far; the carry's length is last_carry)
+    bool sam = false; u64 sam_records = 0;
+    u32* d_sam_htab = nullptr; u32* d_sam_noff = nullptr; u8* d_sam_names = nullptr; u64 cap_sam_htab = 0, cap_sam_noff = 0, cap_sam_names = 0; u32 sam_mask = 0;
+    u32* d_sam_blk = nullptr; u64* d_sam_lines = nullptr; u32* d_sam_wg = nullptr; u64* d_sam_tot = nullptr; u64 cap_sam_blk = 0, cap_sam_lines = 0, cap_sam_wg = 0;
 };
 static_assert(MLST_BAM_MAX_RECORD == BAM_REC_MAX, "mlst_policy.h and csrc/bam_dev.h state the largest BAM record differently");
 #define BAM_DEFAULT_ENTRIES (1ull << 26)      /* sequenceBank list: 32 bytes an entry, allocated as the file needs it */
 static bool bam_is_open(const mlst_handle* h) { return h->bam && h->bam->open; }
+static const char* bam_kind(const mlst_handle* h) { return h->bam && h->bam->sam ? "SAM" : "BAM"; }
 static void bam_drop(mlst_handle* h, bool release) {
     BamStream* B = h->bam;
     if (!B) return;
@@ -5837,6 +5846,7 @@ static void bam_drop(mlst_handle* h, bool release) {
     hipFree(B->d_ref_allele); hipFree(B->d_ref_locus); hipFree(B->d_ref_flags); hipFree(B->d_carry); hipFree(B->d_meta); hipFree(B->d_entries);
     hipFree(B->d_allele_slot); hipFree(B->d_counts); hipFree(B->d_rmeta);
     for (int k = 0; k < 2; k++) { hipFree(B->d_sort_k[k]); hipFree(B->d_sort_v[k]); } hipFree(B->d_sort_tmp);
+    hipFree(B->d_sam_htab); hipFree(B->d_sam_noff); hipFree(B->d_sam_names); hipFree(B->d_sam_blk); hipFree(B->d_sam_lines); hipFree(B->d_sam_wg); hipFree(B->d_sam_tot);
     delete B; h->bam = nullptr;
 }
 static const char* bam_reason(u32 r) {
@@ -5880,7 +5890,7 @@ static int bam_flush(mlst_handle* h) { return (h->bam && h->bam->pend) ? bam_fin
 
 extern "C" int mlst_bam_set_capacity(mlst_handle* h, uint64_t max_entries) {
     if (!h) return MLST_E_INVALID;
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     h->bam_max_entries = max_entries;
     return MLST_OK;
 }
@@ -5889,7 +5899,7 @@ extern "C" int mlst_bam_open(mlst_handle* h, int pass, const int32_t* ref_allele
                              uint32_t skip_bytes, const uint32_t* chosen_allele_idx, uint32_t n_chosen) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
     if ((pass != 1 && pass != 2) || (n_ref && (!ref_allele || !ref_locus || !ref_flags)) || (n_chosen && !chosen_allele_idx)) return fail(h, MLST_E_INVALID, "bad argument");
     if (n_ref >= 0x7FFFFFFFu || skip_bytes >= 65536u) return fail(h, MLST_E_INVALID, "bad argument");
@@ -5927,7 +5937,7 @@ extern "C" int mlst_bam_open(mlst_handle* h, int pass, const int32_t* ref_allele
         B->n_cols = cols;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (the tables came from the caller's pageable memory)
-    B->open = true; B->pend = false; B->first = true; B->pass = pass; B->n_ref = n_ref; B->skip = skip_bytes; B->reads = false;
+    B->open = true; B->pend = false; B->first = true; B->pass = pass; B->n_ref = n_ref; B->skip = skip_bytes; B->reads = false; B->sam = false;
     B->entries_done = B->bound_pend = 0; B->s[0].bound = B->s[1].bound = 0; B->last_carry = 0;
     return MLST_OK;
 }
@@ -5968,6 +5978,7 @@ extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_
     if (n_records_out) *n_records_out = 0;
     if (n_consumed_out) *n_consumed_out = 0;
     if (!bam_is_open(h)) return fail(h, MLST_E_INVALID, "no BAM stream is open (mlst_bam_open)");
+    if (h->bam->sam) return fail(h, MLST_E_INVALID, "a SAM stream is open (its last chunk was not marked final)");
     if (n_bytes && !data) return fail(h, MLST_E_INVALID, "NULL argument");
     if (n_bytes >= (1ull << 30)) return fail(h, MLST_E_LIMIT, "BGZF chunk too large");
     hipSetDevice(h->device);
@@ -6081,6 +6092,159 @@ extern "C" int mlst_submit_bam_bgzf(mlst_handle* h, const uint8_t* data, uint64_
     if (B->reads) {}
     else if (B->pass == 1) rc = bam_bank(h); else B->counts_ready = true;
     B->open = false;
+    return rc;
+}
+
+// ================================================================== SAM text (mlst_sam_open / mlst_submit_sam_text; kernels: csrc/sam_dev.h)
+// The stream is a BAM stream whose pieces are text: slot 0, the carry buffer, the reference tables, the sequenceBank list and the
+// pile-up counts are BamStream's, bam_bank and mlst_bam_pileup_fetch serve both.  A call is finished by itself: its text is copied
+// behind the head room, the carry in front of it, the lines are listed, typed by one thread each, and the partial line at the
+// end goes back to the carry buffer (the host knows where it begins: behind the chunk's last LF).  Two synchronisations per
+// chunk: the line table is sized by the line count, and the chunk's errors are the call's.
+static const char* sam_reason(u32 r) {
+    switch (r) {
+        case SAM_FLAG_CR: return "a CR that does not stand in front of an LF";
+        case SAM_FLAG_BYTE: return "a byte that is not 7-bit text";
+        case SAM_FLAG_COLUMNS: return "fewer than 15 columns";
+        case SAM_FLAG_INT: return "a FLAG, POS, 12th or 15th column that is not a plain integer";
+        case SAM_FLAG_RNAME: return "an RNAME that is not among the header's @SQ names";
+        case SAM_FLAG_NAME: return "a contig name that does not split in three at '_'";
+        case SAM_FLAG_TAG: return "an AS / XM tag that is not a plain integer";
+        case SAM_FLAG_CIGAR: return "a CIGAR byte that is no operation";
+        case SAM_FLAG_CIGLEN: return "a CIGAR operation of 2^28 bases or more";
+        case SAM_FLAG_QUALLEN: return "a QUAL that is neither * nor as long as SEQ";
+        case SAM_FLAG_QUALBYTE: return "a QUAL byte below 33";
+        default: return "?";
+    }
+}
+
+extern "C" int mlst_sam_open(mlst_handle* h, int pass, const uint8_t* names, const uint64_t* name_off, const int32_t* ref_allele, const int32_t* ref_locus,
+                             const uint8_t* ref_flags, uint32_t n_ref, const uint32_t* chosen_allele_idx, uint32_t n_chosen) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    if (n_ref && !name_off) return fail(h, MLST_E_INVALID, "bad argument");
+    const u64 arena = n_ref ? name_off[n_ref] : 0;
+    if (n_ref >= (1u << 30) || arena >= (1ull << 32) || (arena && !names)) return fail(h, MLST_E_INVALID, "bad argument");
+    for (u32 i = 0; i < n_ref; i++) if (name_off[i] > name_off[i + 1]) return fail(h, MLST_E_INVALID, "name offsets must not decrease");
+    if (n_ref && name_off[0] != 0) return fail(h, MLST_E_INVALID, "name offsets must begin at 0");
+    { int rc = mlst_bam_open(h, pass, ref_allele, ref_locus, ref_flags, n_ref, 0, chosen_allele_idx, n_chosen); if (rc) return rc; }
+    BamStream* B = h->bam;
+    B->open = false;      // (until the names are there)
+    u32 cap = 2; while (cap < 2ull * n_ref) cap <<= 1;
+    std::vector<u32> tab(cap, 0u), off32((u64)n_ref + 1, 0u);
+    for (u32 i = 0; i <= n_ref && n_ref; i++) off32[i] = (u32)name_off[i];
+    for (u32 i = 0; i < n_ref; i++) {      // (a name that comes twice keeps its first entry: the triple is a function of the name)
+        const u32 o = off32[i], n = off32[i + 1] - o;
+        u32 slot = sam_name_hash(names + o, n) & (cap - 1u); bool twice = false;
+        while (tab[slot]) {
+            const u32 r = tab[slot] - 1u;
+            if (off32[r + 1] - off32[r] == n && memcmp(names + off32[r], names + o, n) == 0) { twice = true; break; }
+            slot = (slot + 1u) & (cap - 1u);
+        }
+        if (!twice) tab[slot] = i + 1u;
+    }
+    if (B->cap_sam_htab < cap) { hipFree(B->d_sam_htab); B->d_sam_htab = nullptr; B->cap_sam_htab = 0; HIPCHK(h, dmalloc(&B->d_sam_htab, (u64)cap)); B->cap_sam_htab = cap; }
+    if (B->cap_sam_noff < (u64)n_ref + 1) { hipFree(B->d_sam_noff); B->d_sam_noff = nullptr; B->cap_sam_noff = 0; HIPCHK(h, dmalloc(&B->d_sam_noff, (u64)n_ref + 1)); B->cap_sam_noff = (u64)n_ref + 1; }
+    if (B->cap_sam_names < arena || !B->d_sam_names) { hipFree(B->d_sam_names); B->d_sam_names = nullptr; B->cap_sam_names = 0; HIPCHK(h, dmalloc(&B->d_sam_names, arena)); B->cap_sam_names = arena; }
+    if (!B->d_sam_tot) HIPCHK(h, dmalloc(&B->d_sam_tot, (u64)4));
+    HIPCHK(h, hipMemcpyAsync(B->d_sam_htab, tab.data(), (u64)cap * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(B->d_sam_noff, off32.data(), ((u64)n_ref + 1) * 4, hipMemcpyHostToDevice, h->stream));
+    if (arena) HIPCHK(h, hipMemcpyAsync(B->d_sam_names, names, arena, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // (the tables came from pageable memory)
+    B->sam_mask = cap - 1u; B->sam = true; B->sam_records = 0; B->open = true;
+    return MLST_OK;
+}
+
+extern "C" int mlst_submit_sam_text(mlst_handle* h, const uint8_t* text, uint64_t n_bytes, int final_chunk, uint64_t* n_records_out) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    if (n_records_out) *n_records_out = 0;
+    if (!bam_is_open(h) || !h->bam->sam) return fail(h, MLST_E_INVALID, "no SAM stream is open (mlst_sam_open)");
+    if (n_bytes && !text) return fail(h, MLST_E_INVALID, "NULL argument");
+    if (n_bytes >= (1ull << 30)) return fail(h, MLST_E_LIMIT, "SAM chunk too large");
+    hipSetDevice(h->device);
+    BamStream* B = h->bam; BamSlot& S = B->s[0]; hipStream_t st = h->stream;
+    const u64 carry = B->last_carry, total = carry + n_bytes;
+    // where the partial line at the end begins: behind the chunk's last LF (the final chunk leaves none)
+    u64 keep = 0;
+    if (!final_chunk) {
+        const void* nl = n_bytes ? memrchr(text, '\n', n_bytes) : nullptr;
+        keep = nl ? n_bytes - (u64)((const u8*)nl + 1 - text) : total;
+        if (keep > BAM_REC_MAX) { bam_drop(h, false); return fail(h, MLST_E_LIMIT, "a SAM line of more than %u bytes", (unsigned)BAM_REC_MAX); }
+    }
+    if (total) {
+        const u64 s0 = BAM_HEAD - carry, base = s0 & ~(u64)(FQ_BLOCK - 1), skip = s0 - base, text_end = BAM_HEAD + n_bytes;
+        const u32 nb = (u32)(text_end - base); const u64 n_blocks = ((u64)nb + FQ_BLOCK - 1) / FQ_BLOCK;
+        if (S.cap_text < text_end) { hipFree(S.d_text); S.d_text = nullptr; S.cap_text = 0; const u64 cap = text_end + text_end / 8; HIPCHK(h, dmalloc(&S.d_text, cap + 2 * BAM_CELL + 65536)); S.cap_text = cap; }
+        if (B->cap_sam_blk < n_blocks) { hipFree(B->d_sam_blk); B->d_sam_blk = nullptr; B->cap_sam_blk = 0; const u64 cap = n_blocks + n_blocks / 8 + 8; HIPCHK(h, dmalloc(&B->d_sam_blk, cap)); B->cap_sam_blk = cap; }
+        u8* const t = S.d_text + base;
+        if (skip) HIPCHK(h, hipMemsetAsync(t, 'X', skip, st));      // (filler without a newline in front of the first line, see k_fq_lines)
+        if (carry) HIPCHK(h, hipMemcpyAsync(S.d_text + s0, B->d_carry, carry, hipMemcpyDeviceToDevice, st));
+        if (n_bytes) HIPCHK(h, hipMemcpyAsync(S.d_text + BAM_HEAD, text, n_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemsetAsync(B->d_sam_tot, 0, 32, st));
+        u64 n_lines = 0;
+        {
+            Prof pf(h, 15);
+            hipLaunchKernelGGL(k_fq_count, dim3((u32)n_blocks), dim3(256), 0, st, (const u8*)t, (u64)nb, B->d_sam_blk);
+            hipLaunchKernelGGL(k_fq_scan, dim3(1), dim3(1024), 0, st, B->d_sam_blk, (u32)n_blocks, B->d_sam_tot, (u64)nb, (const u8*)t, final_chunk ? 1 : 0);
+        }
+        HIPCHK(h, hipMemcpyAsync(&n_lines, B->d_sam_tot, 8, hipMemcpyDeviceToHost, st));
+        if (hipStreamSynchronize(st) != hipSuccess) { bam_drop(h, false); return fail(h, MLST_E_HIP, "the SAM line count failed: %s", hipGetErrorString(hipGetLastError())); }      // (`text` is the caller's again)
+        // the last line of the final chunk need not end with LF: it is a line all the same (k_fq_scan counted it)
+        const bool open_end = final_chunk && (n_bytes ? text[n_bytes - 1] != '\n' : true);
+        if (n_lines >= (1ull << 31) || (open_end && !n_lines)) { bam_drop(h, false); return fail(h, MLST_E_HIP, "SAM line table inconsistent"); }
+        const u32 nl_ = (u32)n_lines, n_nl = nl_ - (open_end ? 1u : 0u), n_wg = (nl_ + 255u) / 256u;
+        u64 n_rec = 0;
+        const u64 cap_max = h->bam_max_entries ? h->bam_max_entries : BAM_DEFAULT_ENTRIES;      // (the bound holds whatever an earlier stream left allocated)
+        if (nl_) {
+            if (B->cap_sam_lines < n_lines + 2) { hipFree(B->d_sam_lines); B->d_sam_lines = nullptr; B->cap_sam_lines = 0; const u64 cap = n_lines + n_lines / 8 + 2; HIPCHK(h, dmalloc(&B->d_sam_lines, cap)); B->cap_sam_lines = cap; }
+            if (B->cap_sam_wg < n_wg) { hipFree(B->d_sam_wg); B->d_sam_wg = nullptr; B->cap_sam_wg = 0; const u64 cap = (u64)n_wg + n_wg / 8 + 8; HIPCHK(h, dmalloc(&B->d_sam_wg, cap)); B->cap_sam_wg = cap; }
+            if (B->pass == 1) {      // the list grows with the file: what the chunks before filled, plus at most an entry per line of this one
+                const u64 need = std::min(cap_max, B->entries_done + n_lines);
+                if (B->cap_entries < need || !B->d_entries) {
+                    const u64 cap = std::min(cap_max, std::max(need, B->cap_entries * 2));
+                    BamEntry* d_new = nullptr; HIPCHK(h, dmalloc(&d_new, cap));
+                    if (B->d_entries && B->entries_done) HIPCHK(h, hipMemcpy(d_new, B->d_entries, std::min(B->entries_done, B->cap_entries) * sizeof(BamEntry), hipMemcpyDeviceToDevice));
+                    hipFree(B->d_entries); B->d_entries = d_new; B->cap_entries = cap;
+                }
+            }
+            const SamNames N{B->d_sam_htab, B->d_sam_noff, B->d_sam_names, B->sam_mask};
+            {
+                Prof pf(h, 15);
+                hipLaunchKernelGGL(k_fq_lines, dim3((u32)n_blocks), dim3(256), 0, st, (const u8*)t, (u64)nb, (const u32*)B->d_sam_blk, B->d_sam_lines, skip);
+                hipLaunchKernelGGL(k_sam_flags, dim3(n_wg), dim3(256), 0, st, (const u8*)t, nb, (const u64*)B->d_sam_lines, nl_, n_nl, B->d_sam_wg);
+                hipLaunchKernelGGL(k_fq_scan, dim3(1), dim3(1024), 0, st, B->d_sam_wg, n_wg, B->d_sam_tot + 1, (u64)0, (const u8*)t, 0);
+            }
+            if (B->pass == 1) {
+                Prof pf(h, 16);
+                hipLaunchKernelGGL(k_sam_accumulate, dim3(std::min(n_wg, 8192u)), dim3(256), 0, st, (const EngineDev*)h->d_E, h->kp, (const u8*)t, nb, (const u64*)B->d_sam_lines, nl_, n_nl,
+                                   (const u32*)B->d_sam_wg, B->sam_records, B->d_meta, N, (const int*)B->d_ref_allele, (const int*)B->d_ref_locus, (const u8*)B->d_ref_flags,
+                                   B->d_entries, std::min(B->cap_entries, cap_max));
+            } else {
+                Prof pf(h, 17);
+                hipLaunchKernelGGL(k_sam_pileup, dim3(std::min(n_wg, 8192u)), dim3(256), 0, st, (const u8*)t, nb, (const u64*)B->d_sam_lines, nl_, n_nl, (const u32*)B->d_sam_wg,
+                                   B->sam_records, B->d_meta, N, (const int*)B->d_ref_allele, (const u8*)B->d_ref_flags, (const int*)B->d_allele_slot, (const u64*)h->d_aoff,
+                                   h->kp.minscore, h->kp.max_xm, h->kp.minqual, B->d_counts);
+            }
+            if (hipGetLastError() != hipSuccess) { bam_drop(h, false); return fail(h, MLST_E_HIP, "a SAM kernel could not be launched"); }
+        }
+        if (keep) HIPCHK(h, hipMemcpyAsync(B->d_carry, S.d_text + (text_end - keep), keep, hipMemcpyDeviceToDevice, st));
+        BamMeta m;
+        HIPCHK(h, hipMemcpyAsync(&m, B->d_meta, sizeof m, hipMemcpyDeviceToHost, st));
+        if (nl_) HIPCHK(h, hipMemcpyAsync(&n_rec, B->d_sam_tot + 1, 8, hipMemcpyDeviceToHost, st));
+        if (hipStreamSynchronize(st) != hipSuccess) { bam_drop(h, false); return fail(h, MLST_E_HIP, "the SAM kernels failed: %s", hipGetErrorString(hipGetLastError())); }
+        if (m.err) {
+            const u64 cap = std::min(B->cap_entries, cap_max);
+            bam_drop(h, false);
+            if (m.err == BAM_ERR_LIMIT) return fail(h, MLST_E_LIMIT, "a SAM line of more than %u bytes", (unsigned)BAM_REC_MAX);
+            return fail(h, MLST_E_CAPACITY, "more than %llu accepted records on known loci (mlst_bam_set_capacity)", (unsigned long long)cap);
+        }
+        if (m.flag_key != ~0ull) { bam_drop(h, false); return fail(h, MLST_E_INVALID, "host path needed: %s at record %llu", sam_reason((u32)(m.flag_key & 15u)), (unsigned long long)(m.flag_key >> 4)); }
+        B->entries_done = m.n_entries; B->sam_records += n_rec; B->last_carry = (u32)keep;
+        if (n_records_out) *n_records_out = n_rec;
+    }
+    if (!final_chunk) return MLST_OK;
+    int rc = MLST_OK;
+    if (B->pass == 1) rc = bam_bank(h); else B->counts_ready = true;
+    B->open = false; B->sam = false;
     return rc;
 }
 
@@ -6215,7 +6379,7 @@ static int bamr_tile_submit(mlst_handle* h, BamSlot& S, const u32* rd_rec, const
 extern "C" int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip_bytes, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
     if (n_ref >= 0x7FFFFFFFu || skip_bytes >= 65536u) return fail(h, MLST_E_INVALID, "bad argument");
     paired = paired ? 1 : 0;
@@ -6232,7 +6396,7 @@ extern "C" int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip
     HIPCHK(h, hipMemcpyAsync(B->d_rmeta, &r, sizeof r, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));      // (m and r are this frame's)
     B->counts_ready = false;
-    B->open = true; B->pend = false; B->first = true; B->pass = 1; B->n_ref = n_ref; B->skip = skip_bytes; B->reads = true; B->paired = paired;
+    B->open = true; B->pend = false; B->first = true; B->pass = 1; B->n_ref = n_ref; B->skip = skip_bytes; B->reads = true; B->sam = false; B->paired = paired;
     B->tile_len = paired ? 0u : h->tile.read_len; B->tile_stride = paired ? 0u : h->tile.stride;      // (mlst_set_read_tiling refuses while the stream is open)
     B->entries_done = B->bound_pend = 0; B->s[0].bound = B->s[1].bound = 0; B->last_carry = 0;
     B->reads_done = B->n_secondary = B->n_empty = 0; B->rewalked = 0;
@@ -6258,7 +6422,7 @@ extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n
                                  uint64_t* n_contigs_out, uint64_t* n_reads_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
     if (n_contigs_out) *n_contigs_out = 0;
     if (n_reads_out) *n_reads_out = 0;
@@ -6389,7 +6553,7 @@ extern "C" int mlst_bam_pileup_fetch(mlst_handle* h, uint32_t* counts) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     BamStream* B = h->bam;
-    if (!B || B->open || !B->counts_ready) return fail(h, MLST_E_INVALID, "no finished pass-2 BAM stream");
+    if (!B || B->open || !B->counts_ready) return fail(h, MLST_E_INVALID, "no finished pass-2 stream (BAM or SAM)");
     if (B->n_cols && !counts) return fail(h, MLST_E_INVALID, "NULL argument");
     hipSetDevice(h->device);
     if (B->n_cols) { HIPCHK(h, hipMemcpyAsync(counts, B->d_counts, B->n_cols * 16, hipMemcpyDeviceToHost, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream)); }
@@ -6399,7 +6563,7 @@ extern "C" int mlst_bam_pileup_fetch(mlst_handle* h, uint32_t* counts) {
 // test hook (include/mlst_debug.h): every `force_miss_every`-th cell's guess is thrown away, so that k_bam_link walks it itself
 extern "C" int mlst_debug_bam_split(mlst_handle* h, uint32_t force_miss_every, uint64_t* cells_rewalked_out) {
     if (!h) return MLST_E_INVALID;
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     h->bam_force_miss = force_miss_every;
     if (cells_rewalked_out) *cells_rewalked_out = h->bam ? h->bam->rewalked : 0;
     return MLST_OK;
@@ -6410,7 +6574,7 @@ extern "C" int mlst_debug_bam_split(mlst_handle* h, uint32_t force_miss_every, u
 extern "C" int mlst_set_bgzf_verify(mlst_handle* h, int on) {
     if (!h) return MLST_E_INVALID;
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     h->bgzf_verify = on != 0;
     return MLST_OK;
 }
@@ -6429,7 +6593,7 @@ extern "C" int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t 
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
     // (a reads stream took its tile when it was opened: include/mlst.h gives one message for every stream of reads)
     if (bam_is_open(h) && h->bam->reads) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (the reads stream of a BAM: its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a BAM stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     h->tile.read_len = read_len; h->tile.stride = stride;
     return MLST_OK;
 }
@@ -6996,13 +7160,13 @@ extern "C" int mlst_get_items(mlst_handle* h, mlst_item* out, uint64_t cap, uint
 
 extern "C" int mlst_set_profiling(mlst_handle* h, int on) { if (!h) return MLST_E_INVALID; drain_events(h); h->profiling = on == 1; h->window = on != 0; return MLST_OK; }
 extern "C" int mlst_get_kernel_time(mlst_handle* h, int which, double* total_ms, uint64_t* launches) {
-    if (!h || which < 0 || which >= 16) return MLST_E_INVALID;
+    if (!h || which < 0 || which >= 20) return MLST_E_INVALID;
     hipSetDevice(h->device); drain_events(h);
     if (total_ms) *total_ms = h->k_ms[which];
     if (launches) *launches = h->k_n[which];
     return MLST_OK;
 }
-extern "C" int mlst_reset_kernel_time(mlst_handle* h) { if (!h) return MLST_E_INVALID; drain_events(h); for (int i = 0; i < 16; i++) { h->k_ms[i] = 0; h->k_n[i] = 0; } return MLST_OK; }
+extern "C" int mlst_reset_kernel_time(mlst_handle* h) { if (!h) return MLST_E_INVALID; drain_events(h); for (int i = 0; i < 20; i++) { h->k_ms[i] = 0; h->k_n[i] = 0; } return MLST_OK; }
 extern "C" int mlst_get_index_bytes(mlst_handle* h, uint64_t out[4]) {
     if (!h || !out) return MLST_E_INVALID;
     out[0] = h->bytes_arena + h->bytes_hap; out[1] = h->bytes_sieve; out[2] = h->bytes_table; out[3] = (u64)(h->bitmap_fill * 1e6); return MLST_OK;

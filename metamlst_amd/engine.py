@@ -67,8 +67,9 @@ class BgzfCrcMismatch(MlstError):
 
 
 class HostPathNeeded(MlstError):
-    """The library's "host path needed: <reason> at record <n>" (mlst_submit_bam_bgzf): the BAM holds a record the device does not
-    treat; the caller runs samin.AlignmentSample on the file, which raises or answers as the reference would.  Also "... at byte
+    """The library's "host path needed: <reason> at record <n>" (mlst_submit_bam_bgzf, mlst_submit_sam_text): the BAM or the SAM
+    text holds a record the device does not treat; the caller runs samin.AlignmentSample on the file, which raises or answers as
+    the reference would.  Also "... at byte
     <n>" (mlst_submit_fasta): a sequence line only Python's strip() treats; the caller tiles the file with fastq.tile_fasta."""
 
 
@@ -195,6 +196,8 @@ def load_library(path: str | None = None):
         "mlst_bam_set_capacity": (C.c_int, [H, C.c_uint64]),
         "mlst_bam_pileup_fetch": (C.c_int, [H, u32p]),
         "mlst_debug_bam_split": (C.c_int, [H, C.c_uint32, C.POINTER(C.c_uint64)]),
+        "mlst_sam_open": (C.c_int, [H, C.c_int, u8p, u64p, i32p, i32p, u8p, C.c_uint32, u32p, C.c_uint32]),
+        "mlst_submit_sam_text": (C.c_int, [H, u8p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
         "mlst_bam_reads_open": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_int]),
         "mlst_bam_reads_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_debug_last_packed": (C.c_int, [H, u32p, C.c_uint64, u8p, C.c_uint64, u16p, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -476,6 +479,89 @@ class Engine:
         ch = np.ascontiguousarray(chosen, np.uint32)
         self.bam_open(2, *bam_ref_table(self.index, names, None), skip_bytes=skip, chosen=ch)
         self._bam_stream_file(path, lo, chunk_bytes)
+        lens = [int(self.index.off[a + 1] - self.index.off[a]) for a in ch]
+        counts = np.zeros((max(1, sum(lens)), 4), np.uint32)
+        self._check(self.lib.mlst_bam_pileup_fetch(self._h, _ptr(counts)), "mlst_bam_pileup_fetch")
+        out, at = {}, 0
+        for a, L in zip(ch, lens):
+            out[int(a)] = counts[at:at + L]
+            at += L
+        return out
+
+    # ---- SAM text (ready-made alignments) ----
+    def sam_open(self, which: int, names, ref_allele, ref_locus, ref_flags, chosen=None) -> None:
+        """Open a stream of SAM text (mlst_sam_open): which = 1 accumulates, 2 piles the records of `chosen` up; names are the
+        SN: names of the file's @SQ lines (samin.read_sam_header), the three tables samin.bam_ref_table's for them."""
+        enc = [n.encode("utf-8", "surrogateescape") if isinstance(n, str) else bytes(n) for n in names]
+        off = np.zeros(len(enc) + 1, np.uint64)
+        off[1:] = np.cumsum([len(n) for n in enc], dtype=np.uint64)
+        arena = np.frombuffer(b"".join(enc) or b"\0", np.uint8)
+        ra, rl, rf = np.ascontiguousarray(ref_allele, np.int32), np.ascontiguousarray(ref_locus, np.int32), np.ascontiguousarray(ref_flags, np.uint8)
+        if not ra.size == rl.size == rf.size == len(enc):
+            raise ValueError("one (allele, locus, flags) triple per name")
+        ch = np.ascontiguousarray([] if chosen is None else chosen, np.uint32)
+        self._check(self.lib.mlst_sam_open(self._h, int(which), _ptr(arena), _ptr(off), _ptr(ra), _ptr(rl), _ptr(rf), len(enc),
+                                           _ptr(ch) if ch.size else None, ch.size), "mlst_sam_open")
+
+    def submit_sam_text(self, text, final: bool) -> int:
+        """One chunk of the open SAM stream (bytes / bytearray / uint8 array), cut anywhere; returns the record lines it completed."""
+        buf = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, np.uint8)
+        n = C.c_uint64()
+        self._check(self.lib.mlst_submit_sam_text(self._h, _ptr(buf) if buf.size else None, buf.size, int(final), C.byref(n)), "mlst_submit_sam_text")
+        return int(n.value)
+
+    def _sam_stream_file(self, path: str, chunk_bytes: int) -> int:
+        """The bytes of a SAM file into the open stream, chunk by chunk: a plain file through the reader ring and the pooled
+        (page-locked) buffers of _bam_stream_file; a gzip file (plain or bgzip'd) inflated by the host's gzip, a chunk ahead."""
+        from .fastq import prefetch, raw_chunks, release_buffers
+        if chunk_bytes < 1:
+            raise ValueError("chunk_bytes must be positive")
+        chunk_bytes = min(int(chunk_bytes), (1 << 30) - 1)
+        with open(path, "rb") as f:
+            zipped = f.read(2) == b"\x1f\x8b"
+        total = 0
+        if zipped:
+            import gzip
+
+            def pieces():
+                with gzip.open(path, "rb") as z:
+                    while True:
+                        piece = z.read(chunk_bytes)
+                        if not piece:
+                            return
+                        yield piece
+            for piece in prefetch(pieces()):
+                total += self.submit_sam_text(piece, False)
+            return total + self.submit_sam_text(b"", True)
+        size = os.path.getsize(path)
+        if size == 0:
+            return self.submit_sam_text(b"", True)
+        ring: list = []
+        at = 0
+        try:
+            for buf, got in prefetch(raw_chunks(path, chunk_bytes, 0, size, 0, reuse=True, ring=ring)):
+                at += got
+                total += self.submit_sam_text(buf[:got], at >= size)      # (returns when the chunk has left the host buffer)
+        finally:
+            release_buffers(ring)
+        return total
+
+    def submit_sam_file(self, path: str, species_filter: str | None = None, chunk_bytes: int = 64 << 20) -> int:
+        """Pass 1 over SAM text, plain or .gz (hit accumulation, metamlst.py:101-130), parsed on the device; returns the number of
+        records.  The statistics are the engine's (stats(), typing_*).  HostPathNeeded: a line only the host reader treats."""
+        from .samin import bam_ref_table, read_sam_header
+        names = read_sam_header(path)
+        self.sam_open(1, names, *bam_ref_table(self.index, names, species_filter))
+        return self._sam_stream_file(path, chunk_bytes)
+
+    def pileup_sam_file(self, path: str, chosen, chunk_bytes: int = 64 << 20) -> dict[int, np.ndarray]:
+        """Pass 2 over SAM text: {allele idx: uint32[len, 4]} of the chosen contigs, counted on the device from the lines in
+        place (true AS / XM by name, the engine's minscore / max_xm / minqual)."""
+        from .samin import bam_ref_table, read_sam_header
+        names = read_sam_header(path)
+        ch = np.ascontiguousarray(chosen, np.uint32)
+        self.sam_open(2, names, *bam_ref_table(self.index, names, None), chosen=ch)
+        self._sam_stream_file(path, chunk_bytes)
         lens = [int(self.index.off[a + 1] - self.index.off[a]) for a in ch]
         counts = np.zeros((max(1, sum(lens)), 4), np.uint32)
         self._check(self.lib.mlst_bam_pileup_fetch(self._h, _ptr(counts)), "mlst_bam_pileup_fetch")

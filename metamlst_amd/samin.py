@@ -15,6 +15,9 @@ The reference reads `samtools view -h` text (metamlst.py:96-130) and later lets 
     (mlst_pileup_alignments): CIGAR walk, a base counts when Phred >= minqual, it is A/C/G/T and the record's TRUE
     tags pass AS >= minscore, XM <= max_xM (cmseq's BAM_tagFilter looks tags up by name, unlike :110).
 
+A BGZF BAM and SAM text with @SQ lines are typed on the device instead (BamSample / SamSample below: Engine.submit_bam_file,
+Engine.submit_sam_file); AlignmentSample is their fallback ("host path needed") and the yardstick of their tests.
+
 pysam's per-column depth cap (max_depth = 8000) is not applied, as everywhere in this package.
 """
 from __future__ import annotations
@@ -375,6 +378,36 @@ def read_bam_header(path: str, verify_crc: bool = False):
         return names, state["coff"], 0       # the header ends with its block
 
 
+def is_sam_text(path: str) -> bool:
+    """True for what read_alignments reads as SAM text: a file that is not gzip, or gzip that does not inflate to a BAM."""
+    with open(path, "rb") as raw:
+        if raw.read(2) != b"\x1f\x8b":
+            return True
+    with gzip.open(path, "rb") as z:
+        return z.read(4) != b"BAM\1"
+
+
+def read_sam_header(path: str) -> list:
+    """The SN: names of the @SQ lines in front of the first record of SAM text (plain or gzip, told by the file's first bytes), in
+    file order: the names table of the device path (mlst_sam_open).  Other '@' lines (@HD, @CO, @PG ...) between them and @SQ
+    lines without SN: are passed over; a file without a header gives [].  Names are the line's bytes (undecodable ones kept
+    with surrogateescape, so that encoding a name gives its bytes back)."""
+    with open(path, "rb") as raw:
+        zipped = raw.read(2) == b"\x1f\x8b"
+    names = []
+    with (gzip.open(path, "rb") if zipped else open(path, "rb")) as fh:
+        for line in fh:
+            if line[:1] != b"@":
+                break
+            if line[:4] != b"@SQ\t":
+                continue
+            for f in line.rstrip(b"\r\n").split(b"\t")[1:]:
+                if f[:3] == b"SN:":
+                    names.append(f[3:].decode("utf-8", "surrogateescape"))
+                    break
+    return names
+
+
 def bam_ref_table(index: AlleleIndex, names, species_filter: str | None = None):
     """Per reference sequence of a BAM header: (allele index or -1, locus index or -1, flags) with the name rules of
     AlignmentSample.add / .stats(): flags bit 0 = the species passes --filter (metamlst.py:114), bit 1 = the name does not split
@@ -417,3 +450,23 @@ class BamSample:
 
     def pileup(self, engine, chosen, chunk_bytes: int = 64 << 20) -> dict:
         return engine.pileup_bam_file(self.path, chosen, chunk_bytes)
+
+
+class SamSample:
+    """BamSample's counterpart for SAM text (plain or .gz) parsed on the device: .stats() and .pileup(engine, chosen).  The engine's
+    parameters (minscore, max_xm, min_read_len, minqual) are the sample's.  HostPathNeeded from either: use AlignmentSample."""
+
+    def __init__(self, index: AlleleIndex, args: TypingArgs | None, engine):
+        self.index, self.args, self.engine = index, args or TypingArgs(), engine
+        self.path, self.n_records = None, 0
+
+    def add_file(self, path: str, chunk_bytes: int = 64 << 20):
+        self.path = path
+        self.n_records = self.engine.submit_sam_file(path, self.args.filter or None, chunk_bytes)
+        return self
+
+    def stats(self) -> SampleStats:
+        return self.engine.stats()
+
+    def pileup(self, engine, chosen, chunk_bytes: int = 64 << 20) -> dict:
+        return engine.pileup_sam_file(self.path, chosen, chunk_bytes)
