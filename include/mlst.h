@@ -529,6 +529,38 @@ int mlst_hamming_le(mlst_handle* h, uint32_t locus, const uint8_t* query, uint32
 int mlst_hamming_all(mlst_handle* h, uint32_t locus, const uint8_t* query, uint32_t len,
                      uint32_t* dist);
 
+/* ---- centre-star alignment of the alleles of one locus (merge --outseqformat A / A+) ---------------------------------------------------
+ * Replaces the MUSCLE run of metamlst-merge.py:402-405 [MUSCLE NOT IN TREE], which the reference needs when the sequences of a locus
+ * differ in length.  The output is NOT MUSCLE's: the rule below is this engine's own (MLST_MSA_* of mlst_policy.h), stated in Python by
+ * metamlst_amd/msa.py (center_star), and the device reproduces that statement byte for byte (csrc/msa_dev.h).
+ * mlst_msa_align: seqs / off[n + 1] are the n sequences back to back (sequence r = bytes off[r] .. off[r + 1]).
+ *   - the centre is the first sequence, in input order, of the most frequent length (the greatest such length on a tie).
+ *   - every other sequence b (rows i = 1..len(b)) is aligned to the centre a (columns j = 1..m): global, affine, unbanded, int32.
+ *     s(x, y) = MLST_MSA_MATCH when x & 0xDF == y & 0xDF and that letter is one of A C G T, MLST_MSA_MISMATCH otherwise (an N matches
+ *     nothing, itself included; lower case matches its upper case).  A gap of g bases costs GO + g * GE (10 + g), end gaps included.
+ *     States M (b_i on a_j), I (b_i opposite a gap), D (a_j opposite a gap):
+ *       M[0][0] = 0, I[i][0] = -(GO + GE i), D[0][j] = -(GO + GE j), everything else on the border NEG
+ *       M[i][j] = s + max(M, I, D)[i-1][j-1]
+ *       I[i][j] = max(M[i-1][j] - GO - GE, I[i-1][j] - GE, D[i-1][j] - GO - GE)
+ *       D[i][j] = max(M[i][j-1] - GO - GE, D[i][j-1] - GE, I[i][j-1] - GO - GE)
+ *     in every max the first listed candidate wins ties; the end state is the first of M, I, D at the maximum of [len(b)][m]; the
+ *     traceback follows the recorded choices.
+ *   - slot k (k = 0..m) lies between centre columns k and k + 1 and is as wide as the longest insertion any row makes there.  A row
+ *     is, for k = 0..m: its insertion in slot k, left-justified and padded with '-', then (k < m) its base on column k + 1, or '-'.
+ *     The centre's slots are all '-'; letters keep their case; every row is width = m + sum of the slot widths bytes long; a row
+ *     without its '-' is its sequence.  Insertions of different rows that share a slot are stacked, not aligned to each other.
+ *   center_out / width_out (optional): index of the centre, bytes per row.  No reference needs to be loaded; nothing of the sample's
+ *   state is read or changed, and mlst_reset_sample leaves a finished alignment alone.  The pairs are aligned in batches whose
+ *   traceback store (about len x m bytes a pair) fits MLST_MSA_BATCH_BYTES (environment, read by mlst_create; default 1 GiB, floor
+ *   one pair); one host synchronisation per call (the width sizes the rows).
+ *   Refused: n = 0, an empty sequence, a byte that is not an ASCII letter ('-', white space and digits included): MLST_E_INVALID;
+ *   a sequence longer than MLST_MAX_ALLELE_LEN (4095) bases, n x width >= 2^32: MLST_E_LIMIT; a call while a FASTQ, BAM or SAM
+ *   stream is open on the handle: MLST_E_INVALID.  A refused call leaves no finished alignment; the handle stays usable.
+ * mlst_msa_fetch: the n x width bytes of the alignment just finished, row after row (rows: host memory).  Without a finished
+ *   mlst_msa_align: MLST_E_INVALID. */
+int mlst_msa_align(mlst_handle* h, const uint8_t* seqs, const uint64_t* off /* n + 1 */, uint32_t n, uint32_t* center_out, uint32_t* width_out);
+int mlst_msa_fetch(mlst_handle* h, uint8_t* rows /* n * width */);
+
 /* Multi-GPU: index of this rank's first read in the whole sample, so that locus_first_read (the
  * first-seen order of metamlst.py's dicts, Q6) is global.  Call after mlst_reset_sample / before submitting. */
 int mlst_set_read_index_base(mlst_handle* h, uint64_t base);

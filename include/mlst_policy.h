@@ -67,6 +67,14 @@
                                        per allele.  The reference states nothing for reads its aligner handles and the packed score
                                        fields (MLST_MAX_READ_LEN) cannot hold: the policy is this engine's own, like --contigs */
 
+/* ---- centre-star alignment of a locus' alleles (mlst_msa_align; merge --outseqformat A) ----
+ * The policy is this engine's own: the reference pipes the sequences through MUSCLE (metamlst-merge.py:402-405) [NOT IN TREE], whose
+ * gap placement differs between its own versions.  The rule is stated in metamlst_amd/msa.py and in include/mlst.h. */
+#define MLST_MSA_MATCH          5   /* same letter (case folded), one of A C G T */
+#define MLST_MSA_MISMATCH     (-4)  /* everything else: N matches nothing, itself included */
+#define MLST_MSA_GAP_OPEN      10   /* a gap of g bases costs GAP_OPEN + g * GAP_EXT, end gaps included */
+#define MLST_MSA_GAP_EXT        1
+
 /* ---- hard limits of the packed formats ---- */
 #define MLST_MAX_READ_LEN     320   /* 20 packed words; xm field of the packed score is 8 bits */
 #define MLST_MAX_ALLELE_LEN  4095   /* 12-bit position in a seed posting */

@@ -4,7 +4,7 @@
     python -m metamlst_amd.cli type  READS.bam -d DB [-o out]            (the reads of a BAM, as `samtools fastq` takes them)
     python -m metamlst_amd.cli type  LONG.fastq --long-reads [--tile LEN,STEP] -d DB   (reads longer than 320 bases, cut into windows)
     python -m metamlst_amd.cli type  HIFI.bam --long-bam-reads [--tile LEN,STEP] -d DB  (the same for the reads of an unaligned BAM)
-    python -m metamlst_amd.cli merge FOLDER -d DB [-z 5] [--filter ...] [--meta ...] [--idField ...]       (metamlst-merge.py:35-49)
+    python -m metamlst_amd.cli merge FOLDER -d DB [-z 5] [--filter ...] [--meta ...] [--idField ...] [--aligner auto|gpu|muscle]   (metamlst-merge.py:35-49)
     python -m metamlst_amd.cli index -d DB [-s seqs.fasta,...] [-t typings.txt,...] [-q dump.fa] [--list]   (metamlst-index.py:24-33)
 
 `type` takes reads instead of a bowtie2 BAM: the alignment happens on the GPU.  Everything it
@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import argparse
 import os
+import shutil
 import sys
 import time
 
@@ -22,7 +23,7 @@ from . import db as mdb
 from .engine import CorruptInput, Engine, crc_checked, default_params
 from .fastq import is_bgzf, mates_share_names, pair_chunks, prefetch, text_chunks, tile_fasta
 from .index import load_index
-from .merge import EngineMatcher, merge_folder
+from .merge import EngineAligner, EngineMatcher, _muscle, merge_folder
 from .typing import TypingArgs, log_table, sample_name, type_sample
 
 
@@ -98,6 +99,10 @@ def _merge_parser(sub):
     p.add_argument("--outseqformat", choices=["A", "A+", "B", "B+", "C", "C+"])
     p.add_argument("-j", metavar="subjectID,diet,age...")
     p.add_argument("--jgroup", action="store_true")
+    p.add_argument("--aligner", choices=["auto", "gpu", "muscle"], default="auto",
+                   help="what aligns the sequences of a locus that differ in length (--outseqformat A / A+): muscle = the MUSCLE binary, as "
+                        "the reference; gpu = the engine's centre-star alignment (no MUSCLE needed; not MUSCLE's gap placement); auto = "
+                        "muscle where one is installed, gpu otherwise")
     p.add_argument("--device", default=0, type=int)
     return p
 
@@ -506,8 +511,15 @@ def run_merge(a) -> int:
     idx = load_index(a.database)
     eng = Engine(a.device)
     eng.load_reference(idx)
+    use_muscle = a.aligner == "muscle" or (a.aligner == "auto" and shutil.which("muscle") is not None)
+    align, name = (_muscle, "MUSCLE") if use_muscle else (EngineAligner(eng), "the GPU engine (centre-star)")
+
+    def aligner(seqs):
+        sys.stderr.write("aligner: %s on %d sequences\n" % (name, len(seqs)))
+        return align(seqs)
+
     tables = merge_folder(a.folder, database, EngineMatcher(eng, idx), z=a.z, filter=a.filter, meta=a.meta, idField=a.idField,
-                          cache=mdb.DbCache(database.conn, idx), outseqformat=a.outseqformat, j=a.j, jgroup=a.jgroup)
+                          cache=mdb.DbCache(database.conn, idx), outseqformat=a.outseqformat, j=a.j, jgroup=a.jgroup, aligner=aligner)
     for sp, t in tables.items():
         print("%s: %d sample(s) typed, %d new profile(s)" % (sp, len(t["isolates"]), sum(1 for v in t["encounteredProfiles"].values() if v[2] in (1, 2))))
     return 0

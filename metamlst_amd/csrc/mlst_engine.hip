@@ -3684,6 +3684,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "fasta_dev.h"
 #include "fastq_tile.h"
 #include "bam_tile.h"
+#include "msa_dev.h"
 
 // ================================================================== host side
 struct EvPair { hipEvent_t a, b; int which; };
@@ -3806,6 +3807,13 @@ struct mlst_handle {
     struct { u32 read_len = 0, stride = 0; u64 round = 16ull << 20; u64 info[4] = {0, 0, 0, 0};
              FqtDev* d_desc = nullptr; FqtMeta* d_meta = nullptr; u8* h_fqt = nullptr; u64* d_rlen = nullptr; u64* d_wex = nullptr; u64 cap_recs = 0;
              u64* d_gsum = nullptr; u64 cap_groups = 0; u64* d_soff = nullptr; u64* d_qoff = nullptr; u64 cap_win = 0; } tile;
+    // centre-star alignment (mlst_msa_align / mlst_msa_fetch; csrc/msa_dev.h): no part of a sample's state.  batch_bytes: the traceback
+    // store of one batch of pairs (MLST_MSA_BATCH_BYTES, read by mlst_create); the buffers grow and stay; done: rows of n x width
+    // bytes wait in d_rows for mlst_msa_fetch
+    struct { u64 batch_bytes = 1ull << 30; bool done = false; u32 n = 0, width = 0;
+             u8* d_seq = nullptr; u64 cap_seq = 0; u64* d_off = nullptr; u64 cap_off = 0; u16* d_tab = nullptr; u64 cap_tab = 0;
+             u32* d_slot = nullptr; u8* d_end = nullptr; u64 cap_end = 0; u32* d_tb = nullptr; u64 cap_tb = 0; u8* d_rows = nullptr; u64 cap_rows = 0;
+             u32* h_width = nullptr; } msa;
 };
 
 static std::string g_create_err;
@@ -3921,6 +3929,7 @@ extern "C" int mlst_create(int device, const mlst_params* p, mlst_handle** out) 
     h->own_stream = h->stream;
     { const char* g = getenv("MLST_GRAPHS"); if (g && g[0] == '0') h->use_graphs = false; }
     { const char* g = getenv("MLST_BGZF_CRC"); h->bgzf_verify = g && g[0] == '1'; }      // initial value of mlst_set_bgzf_verify
+    { const char* g = getenv("MLST_MSA_BATCH_BYTES"); if (g && atoll(g) > 0) h->msa.batch_bytes = (u64)atoll(g); }      // traceback store of one batch of mlst_msa_align (floor: one pair)
     { const char* g = getenv("MLST_TILE_ROUND"); if (g && atoll(g) > 0) h->tile.round = (u64)atoll(g); }      // windows per round of a tiled FASTQ chunk: a memory bound
     { int khz = 0; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) h->wall_khz = (double)khz; }
     KParams& k = h->kp;
@@ -3993,6 +4002,8 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     if (h->fa.h_fa) hipHostFree(h->fa.h_fa);
     hipFree(h->tile.d_desc); hipFree(h->tile.d_meta); hipFree(h->tile.d_rlen); hipFree(h->tile.d_wex); hipFree(h->tile.d_gsum); hipFree(h->tile.d_soff); hipFree(h->tile.d_qoff);
     if (h->tile.h_fqt) hipHostFree(h->tile.h_fqt);
+    hipFree(h->msa.d_seq); hipFree(h->msa.d_off); hipFree(h->msa.d_tab); hipFree(h->msa.d_slot); hipFree(h->msa.d_end); hipFree(h->msa.d_tb); hipFree(h->msa.d_rows);
+    if (h->msa.h_width) hipHostFree(h->msa.h_width);
     hipFree(h->d_bgzf); hipFree(h->d_bgzf_blk); hipFree(h->d_fq_carry); h->d_bgzf = nullptr; h->d_bgzf_blk = nullptr; h->d_fq_carry = nullptr; h->cap_bgzf = h->cap_bgzf_blk = h->cap_fq_carry = h->fq_carry_len = 0;
     hipFree(h->d_packed); hipFree(h->d_qrows); hipFree(h->d_lens); hipFree(h->d_counts); hipFree(h->d_dist); hipFree(h->d_query);
     for (auto* g : {&h->g_submit, &h->g_typing}) if (g->exec) hipGraphExecDestroy(g->exec);
@@ -7222,4 +7233,92 @@ extern "C" int mlst_debug_route_realloc(mlst_handle* h, uint64_t pad_bytes) {
     if (pad_bytes && pad_bytes != ~0ull) { void* q = nullptr; HIPCHK(h, hipMalloc(&q, pad_bytes)); h->dbg_pads.push_back(q); }
     return MLST_OK;
 }
+// ---- centre-star alignment of a locus' alleles (kernels: csrc/msa_dev.h; the rule: include/mlst.h, metamlst_amd/msa.py).  Input checks
+// and the choice of the centre are host work (one pass over the bytes); the pairs are aligned in batches whose traceback store fits
+// MLST_MSA_BATCH_BYTES, DP and traceback of a batch behind each other on the engine's stream, the slot widths adding up across the
+// batches; then the scan, and the one host synchronisation of the call: the width sizes the rows, which k_msa_rows writes for
+// mlst_msa_fetch.  Nothing of a sample's state is read or written.
+template <typename T> static int msa_grow(mlst_handle* h, T** p, u64* cap, u64 need) {
+    if (*cap >= need && *p) return MLST_OK;
+    hipFree(*p); *p = nullptr; *cap = 0;
+    HIPCHK(h, dmalloc(p, need)); *cap = need;
+    return MLST_OK;
+}
+extern "C" int mlst_msa_align(mlst_handle* h, const uint8_t* seqs, const uint64_t* off, uint32_t n, uint32_t* center_out, uint32_t* width_out) {
+    if (!h) return MLST_E_INVALID;
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
+    auto& S = h->msa;
+    S.done = false;
+    if (n == 0) return fail(h, MLST_E_INVALID, "no sequence to align");
+    if (!seqs || !off) return fail(h, MLST_E_INVALID, "NULL argument");
+    std::vector<u32> by_len(MLST_MAX_ALLELE_LEN + 1, 0);
+    u32 nmax = 0;
+    for (u32 r = 0; r < n; r++) {
+        if (off[r + 1] < off[r]) return fail(h, MLST_E_INVALID, "offsets must not decrease");
+        const u64 len = off[r + 1] - off[r];
+        if (len == 0) return fail(h, MLST_E_INVALID, "sequence %u is empty", r);
+        if (len > (u64)MLST_MAX_ALLELE_LEN) return fail(h, MLST_E_LIMIT, "sequence %u is longer than %d bases", r, MLST_MAX_ALLELE_LEN);
+        for (u64 x = off[r]; x < off[r + 1]; x++) { const u8 c = seqs[x] | 0x20; if (c < 'a' || c > 'z') return fail(h, MLST_E_INVALID, "sequence %u holds a byte that is not an ASCII letter", r); }
+        by_len[len]++; nmax = std::max(nmax, (u32)len);
+    }
+    u32 m = 1;      // the most frequent length, the greatest on a tie
+    for (u32 len = 1; len <= (u32)MLST_MAX_ALLELE_LEN; len++) if (by_len[len] && by_len[len] >= by_len[m]) m = len;
+    u32 center = 0;
+    while (off[center + 1] - off[center] != m) center++;      // its first sequence
+    hipSetDevice(h->device);
+    const u64 n_bytes = off[n] - off[0], cells = (u64)n * (m + 1);
+    { int rc = msa_grow(h, &S.d_seq, &S.cap_seq, n_bytes); if (rc) return rc; }
+    { int rc = msa_grow(h, &S.d_off, &S.cap_off, (u64)n + 1); if (rc) return rc; }
+    { int rc = msa_grow(h, &S.d_tab, &S.cap_tab, cells * 3); if (rc) return rc; }
+    { int rc = msa_grow(h, &S.d_end, &S.cap_end, (u64)n); if (rc) return rc; }
+    if (!S.d_slot) HIPCHK(h, dmalloc(&S.d_slot, (u64)2 * (MLST_MAX_ALLELE_LEN + 1) + 1));
+    if (!S.h_width) { void* p = nullptr; HIPCHK(h, hipHostMalloc(&p, 4, hipHostMallocDefault)); S.h_width = (u32*)p; }
+    MsaDev A;
+    A.seq = S.d_seq - off[0]; A.off = S.d_off; A.n = n; A.center = center; A.m = m; A.nmax = nmax;
+    A.col = S.d_tab; A.ins_start = S.d_tab + cells; A.ins_len = S.d_tab + 2 * cells;
+    A.slot_w = S.d_slot; A.slot_at = S.d_slot + (MLST_MAX_ALLELE_LEN + 1); A.width = S.d_slot + 2 * (MLST_MAX_ALLELE_LEN + 1);
+    A.end_state = S.d_end;
+    A.T4 = (nmax + 63) / 4 + 1; A.tb_words = (u64)((m + 63) / 64) * A.T4 * 64;
+    const u64 per_batch = std::min<u64>(n, std::max<u64>(1, S.batch_bytes / (A.tb_words * 4)));
+    { int rc = msa_grow(h, &S.d_tb, &S.cap_tb, per_batch * A.tb_words); if (rc) return rc; }
+    A.tb = S.d_tb;
+    HIPCHK(h, hipMemcpyAsync(S.d_seq, seqs + off[0], n_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(S.d_off, off, ((u64)n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.ins_len, 0, cells * 2, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.slot_w, 0, (u64)(m + 1) * 4, h->stream));
+    u32 wpb = MSA_WPB;      // pairs per workgroup: their row buffers (8 bytes per row of the longest sequence) within 48 KiB of LDS
+    while (wpb > 1 && (u64)wpb * (nmax + 1) * sizeof(int2) > 49152) wpb >>= 1;
+    const size_t lds = (size_t)wpb * (nmax + 1) * sizeof(int2);
+    for (u64 r0 = 0; r0 < n; r0 += per_batch) {
+        const u32 r1 = (u32)std::min<u64>(n, r0 + per_batch), cnt = r1 - (u32)r0;
+        hipLaunchKernelGGL(k_msa_dp, dim3((cnt + wpb - 1) / wpb), dim3(64 * wpb), lds, h->stream, A, (u32)r0, r1);
+        hipLaunchKernelGGL(k_msa_trace, dim3((cnt + 63) / 64), dim3(64), 0, h->stream, A, (u32)r0, r1);
+    }
+    hipLaunchKernelGGL(k_msa_scan, dim3(1), dim3(1024), 0, h->stream, A);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(S.h_width, A.width, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u32 width = *S.h_width;
+    if ((u64)n * width >= (1ull << 32)) return fail(h, MLST_E_LIMIT, "%u rows of %u columns: the alignment does not fit 2^32 bytes", n, width);
+    { int rc = msa_grow(h, &S.d_rows, &S.cap_rows, (u64)n * width); if (rc) return rc; }
+    hipLaunchKernelGGL(k_msa_rows, dim3(grid_for((u64)n * width, 256, 65536)), dim3(256), 0, h->stream, A, width, S.d_rows);
+    HIPCHK(h, hipGetLastError());
+    S.n = n; S.width = width; S.done = true;
+    if (center_out) *center_out = center;
+    if (width_out) *width_out = width;
+    return MLST_OK;
+}
+extern "C" int mlst_msa_fetch(mlst_handle* h, uint8_t* rows) {
+    if (!h) return MLST_E_INVALID;
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
+    if (!h->msa.done) return fail(h, MLST_E_INVALID, "no finished alignment (mlst_msa_align comes first)");
+    if (!rows) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    HIPCHK(h, hipMemcpyAsync(rows, h->msa.d_rows, (u64)h->msa.n * h->msa.width, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLST_OK;
+}
+
 extern "C" int mlst_synchronize(mlst_handle* h) { if (!h) return MLST_E_INVALID; hipSetDevice(h->device); { int rc_ = bz_flush(h); if (rc_) return rc_; } HIPCHK(h, hipStreamSynchronize(h->stream)); return MLST_OK; }

@@ -176,6 +176,8 @@ def load_library(path: str | None = None):
         "mlst_round_tenths": (C.c_longlong, [C.c_longlong, C.c_uint32]),
         "mlst_hamming_le": (C.c_int, [H, C.c_uint32, u8p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
         "mlst_hamming_all": (C.c_int, [H, C.c_uint32, u8p, C.c_uint32, u32p]),
+        "mlst_msa_align": (C.c_int, [H, u8p, u64p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "mlst_msa_fetch": (C.c_int, [H, u8p]),
         "mlst_reset_sample": (C.c_int, [H]),
         "mlst_set_read_index_base": (C.c_int, [H, C.c_uint64]),
         "mlst_get_items": (C.c_int, [H, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -1003,6 +1005,19 @@ class Engine:
         return d
 
     # ---- misc ----
+    def align_center_star(self, seqs) -> tuple[int, list[bytes]]:
+        """Centre-star alignment of `seqs` (bytes each) on the GPU: (index of the centre, the rows), byte for byte what
+        metamlst_amd.msa.center_star returns (mlst_msa_align / mlst_msa_fetch).  Raises MlstError for what that statement refuses."""
+        seqs = [bytes(q) for q in seqs]
+        off = np.zeros(len(seqs) + 1, np.uint64)
+        off[1:] = np.cumsum([len(q) for q in seqs], dtype=np.uint64)
+        flat = np.frombuffer(b"".join(seqs) or b"\0", np.uint8)
+        center, width = C.c_uint32(), C.c_uint32()
+        self._check(self.lib.mlst_msa_align(self._h, _ptr(flat), _ptr(off), len(seqs), C.byref(center), C.byref(width)), "mlst_msa_align")
+        rows = np.empty((len(seqs), width.value), np.uint8)
+        self._check(self.lib.mlst_msa_fetch(self._h, _ptr(rows)), "mlst_msa_fetch")
+        return int(center.value), [r.tobytes() for r in rows]
+
     def reset_sample(self):
         self._check(self.lib.mlst_reset_sample(self._h), "mlst_reset_sample")
 

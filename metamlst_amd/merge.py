@@ -9,7 +9,8 @@ The only heavy step -- the stringDiff scan over every allele of a locus
 (metamlst-merge.py:177-181) -- is delegated to `matcher`, which in the product is the GPU
 Hamming kernel (Engine.hamming_le).  Sequence outputs (--outseqformat A / A+ / B / B+ / C / C+, -j, --jgroup;
 metamlst-merge.py:345-494) are written by write_sequences; format A needs MUSCLE only when the sequences of a locus
-differ in length, exactly as in the reference.
+differ in length, exactly as in the reference -- or, with `aligner=EngineAligner(engine)`, the engine's own centre-star
+alignment (metamlst_amd/msa.py states its rule), which needs no MUSCLE.
 """
 from __future__ import annotations
 
@@ -250,9 +251,23 @@ def _muscle(seqs):
     return res
 
 
+class EngineAligner:
+    """`aligner` backed by the GPU engine, with `_muscle`'s contract: [(id, sequence), ...] -> {id: aligned sequence}.  The rows are
+    the centre-star alignment of metamlst_amd.msa.center_star (Engine.align_center_star), not MUSCLE's."""
+
+    def __init__(self, engine):
+        self.engine = engine
+
+    def __call__(self, seqs) -> dict:
+        _, rows = self.engine.align_center_star([str(q).encode() for _, q in seqs])
+        return dict((i, row.decode()) for (i, _), row in zip(seqs, rows))
+
+
 def write_sequences(folder: str, bacterium: str, tables: dict, database: mdb.metaMLST_db, outseqformat: str,
-                    STmapper: dict, metadataJoinField: str = "sampleID", j: str | None = None, jgroup: bool = False) -> None:
-    """metamlst-merge.py:345-494: merged/<sp>_sequences.fna (A, A+, B, B+) or merged/<sp>_sequences.txt (C)."""
+                    STmapper: dict, metadataJoinField: str = "sampleID", j: str | None = None, jgroup: bool = False,
+                    aligner=None) -> None:
+    """metamlst-merge.py:345-494: merged/<sp>_sequences.fna (A, A+, B, B+) or merged/<sp>_sequences.txt (C).
+    aligner: what aligns the sequences of a locus that differ in length (format A / A+); None = MUSCLE, as in the reference."""
     oldProfiles, encounteredProfiles = tables["oldProfiles"], tables["encounteredProfiles"]
     lastGenes, newSequences = tables["lastGenes"], tables["newSequences"]          # newSequences[gene] = [(label, seq), ...]
     base = folder + "/merged/" + bacterium + "_sequences"
@@ -287,7 +302,7 @@ def write_sequences(folder: str, bacterium: str, tables: dict, database: mdb.met
                 if len(q) not in tld:
                     tld.append(len(q))
             if len(tld) > 1:
-                seqTable.update(_muscle(seqs))
+                seqTable.update((aligner or _muscle)(seqs))
             else:
                 for i, q in seqs:
                     seqTable[i] = str(q)
@@ -345,7 +360,7 @@ def write_sequences(folder: str, bacterium: str, tables: dict, database: mdb.met
 
 def merge_folder(folder: str, database: mdb.metaMLST_db, matcher, z: int | None = 5, filter: str | None = None,
                  meta: str | None = None, idField: int = 0, cache: mdb.DbCache | None = None,
-                 outseqformat: str | None = None, j: str | None = None, jgroup: bool = False) -> dict:
+                 outseqformat: str | None = None, j: str | None = None, jgroup: bool = False, aligner=None) -> dict:
     """The whole metamlst-merge.py run for one folder of .nfo files.  Returns {species: tables}."""
     if not os.path.isdir(folder + "/merged"):
         os.makedirs(folder + "/merged")
@@ -355,6 +370,6 @@ def merge_folder(folder: str, database: mdb.metaMLST_db, matcher, z: int | None 
         tables = call_species(database, bacterium, bactRecord, z, matcher, cache)
         STmapper, joinField = write_species(folder, bacterium, tables, meta, idField)
         if outseqformat:
-            write_sequences(folder, bacterium, tables, database, outseqformat, STmapper, joinField, j, jgroup)
+            write_sequences(folder, bacterium, tables, database, outseqformat, STmapper, joinField, j, jgroup, aligner)
         out[bacterium] = tables
     return out
