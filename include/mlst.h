@@ -332,6 +332,38 @@ int mlst_pileup_alignments(mlst_handle* h, const uint32_t* chosen_allele_idx, ui
                            const uint8_t* seq, const uint8_t* qual, int32_t minscore, int32_t max_xm, int32_t minqual,
                            uint32_t* counts);
 
+/* ---- the engine's own alignments to the chosen alleles, as records (what the reference leaves behind as a BAM) --------------------
+ * mlst_alignments_export walks every work item (mlst_get_items) whose locus has a chosen allele and decides it exactly as the
+ * pile-up decides that (item, chosen allele): the ungapped alignment, or the banded one when the gap trigger fires (the policy of
+ * pass 1: MLST_DEF_GAP_TRIGGER_MM / _CLIP).  A record exists iff score >= the floor of the read's length && score > 0.  Records
+ * that fail the AS / XM tag filter are exported too: they sit in a bowtie2 BAM and count towards depth.  mlst_set_depth_cap is
+ * ignored: every record is exported.  The totals (records, CIGAR operations, bases) size the arrays of mlst_alignments_fetch:
+ *   read_index  : index of the read in submission order (mlst_item.read_index)
+ *   rec_allele  : index of the chosen allele among the loaded alleles     rec_diag : the item's diagonal
+ *   rec_flags   : bit 0 the item's strand (1 = the read is reverse-complemented), bit 1 the banded alignment was taken (used_dp)
+ *   rec_as / rec_xm : the true AS and XM, the values the pile-up's tag filter sees
+ *   rec_pos0    : the leftmost aligned allele column, 0-based
+ *   cigar       : len << 4 | op, BAM operation codes, in reference orientation; cigar_off[n_rec + 1] delimits records.
+ *                 Ungapped: [bs S] (be - bs) M [(n - be) S] with the aligned span [bs, be) in oriented read coordinates, so
+ *                 rec_pos0 = bs + diag.  Banded: the traceback from its end back to its start, written forwards as M / I / D runs,
+ *                 S for the oriented bases in front of and behind the walk.  No operation has length 0.
+ *   seq / qual  : ASCII on the reference strand (reverse-complemented for strand 1; 'N' where the read has no A/C/G/T) and the raw
+ *                 Phred (not +33) in the same orientation; seq_off[n_rec + 1] delimits records.
+ * The arrays from rec_allele on, rec_diag and rec_flags left out, have the layout mlst_pileup_alignments takes: piled up with the
+ * engine's minscore / max_xm / minqual they give mlst_pileup's counts.  The order of the records is unspecified (it follows the item
+ * list).  The sample's state is read and none of it is changed: the statistics, a later mlst_pileup* / mlst_typing_* and
+ * mlst_reset_sample behave as before; an open BGZF piece is finished first.  Two host synchronisations per export (the item count
+ * sizes the tables, the totals size the arrays).  A sample without reads gives 0 records.  The records stay on the device until
+ * the next export.
+ *   Refused: a call while a BAM, SAM or paired stream is open on the handle, two chosen alleles of one locus, an allele out of
+ *   range: MLST_E_INVALID.  mlst_alignments_fetch without a finished export (a refused one leaves none): MLST_E_INVALID. */
+int mlst_alignments_export(mlst_handle* h, const uint32_t* chosen_allele_idx, uint32_t n,
+                           uint64_t* n_rec_out, uint64_t* n_cigar_out, uint64_t* n_bases_out);
+int mlst_alignments_fetch(mlst_handle* h, uint64_t* read_index, uint32_t* rec_allele, int32_t* rec_pos0, int32_t* rec_as,
+                          int32_t* rec_xm, int32_t* rec_diag, uint8_t* rec_flags /* bit 0 strand, bit 1 used_dp */,
+                          uint64_t* cigar_off /* n_rec+1 */, uint32_t* cigar, uint64_t* seq_off /* n_rec+1 */,
+                          uint8_t* seq, uint8_t* qual);
+
 /* ---- ready-made alignments straight from a BGZF BAM (the reference's one input, metamlst.py:34) ------------------------------
  * The file is streamed twice, as the reference reads it twice (samtools view, then pysam): pass 1 is the hit accumulation of
  * metamlst.py:101-130 (what mlst_submit_* do for reads), pass 2 the pile-up of the chosen contigs (mlst_pileup_alignments).  The

@@ -4,6 +4,7 @@
     python -m metamlst_amd.cli type  READS.bam -d DB [-o out]            (the reads of a BAM, as `samtools fastq` takes them)
     python -m metamlst_amd.cli type  LONG.fastq --long-reads [--tile LEN,STEP] -d DB   (reads longer than 320 bases, cut into windows)
     python -m metamlst_amd.cli type  HIFI.bam --long-bam-reads [--tile LEN,STEP] -d DB  (the same for the reads of an unaligned BAM)
+    python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam -d DB      (also <out>/<sample>.sam: the alignments to the chosen alleles)
     python -m metamlst_amd.cli merge FOLDER -d DB [-z 5] [--filter ...] [--meta ...] [--idField ...] [--aligner auto|gpu|muscle]   (metamlst-merge.py:35-49)
     python -m metamlst_amd.cli index -d DB [-s seqs.fasta,...] [-t typings.txt,...] [-q dump.fa] [--list]   (metamlst-index.py:24-33)
 
@@ -78,6 +79,11 @@ def _type_parser(sub):
                    help="bgzip'd input: do not check the CRC-32 of the BGZF blocks.  By default every block's text is checked against "
                         "the CRC in its trailer before its reads are typed (on the GPU; the boundary blocks of a --gpus N shard on the "
                         "host), as zlib, htslib and `bgzip -d` do; a mismatch ends the sample with an error and no .nfo")
+    p.add_argument("--write-sam", dest="write_sam", action="store_true",
+                   help="after the .nfo, write <out>/<sample>.sam: the engine's alignments of the sample's reads to the alleles the "
+                        "typing tail chose, as SAM text (metamlst_amd/samout.py: QNAME r<read index>, secondary records flagged 256, the "
+                        "optional fields of bowtie2 with XS a placeholder).  One sample of reads on one GPU: it goes with none of "
+                        "--alignments (the file is the input there), several samples or a folder, and --gpus N")
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -202,6 +208,16 @@ def run_type(a, argv=None) -> int:
         print("no %s file found in " % ("FASTA" if a.contigs else "FASTQ") + ", ".join(a.READS))
         return 1
     many = len(samples) > 1
+    if a.write_sam:      # (refused before any GPU use)
+        if a.alignments:
+            print("--write-sam writes the engine's own alignments: with --alignments the file is the input")
+            return 1
+        if many:
+            print("--write-sam takes one sample: several samples or a folder are typed without it")
+            return 1
+        if a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            print("--write-sam takes one GPU: a rank of --gpus N holds its own reads' alignments only")
+            return 1
     if many and (a.alignments or a.mates):
         print("several samples at once: FASTQ input only (use `r1.fq,r2.fq` for a sample made of two files)")
         return 1
@@ -317,7 +333,7 @@ def run_type(a, argv=None) -> int:
         return _finish_type(a, idx, database, targs, smp.stats(), lambda chosen: smp.pileup(eng, chosen))
     if a.contigs:      # the file's bytes go to the GPU and are cut into windows there (mlst_submit_fasta)
         submit_contigs(eng, a.READS, tile)
-        return _finish_type_device(a, eng, idx, database, targs)
+        return _finish_type_device(a, eng, idx, database, targs, paired=False)
     # Mates are unpaired reads for the aligner (bowtie2 -U r1,r2).  What a shared read name changes is sequenceBank
     # (metamlst.py:127: one entry per QNAME and locus): pairs whose files name both mates alike are submitted as pairs.
     paired = bool(a.mates) and mates_share_names(a.READS, a.mates)
@@ -347,15 +363,24 @@ def run_type(a, argv=None) -> int:
         print(e, file=sys.stderr)
         database.closeConnection()
         return 1
-    return _finish_type_device(a, eng, idx, database, targs)
+    if a.write_sam and not paired and not (long_reads or long_bam) and all(_is_reads_bam(f) for f in paths):      # (as submit_bam_reads decides it)
+        from .samin import bam_first_read_flags
+        paired = any((bam_first_read_flags(f) or 0) & 1 for f in paths)
+    return _finish_type_device(a, eng, idx, database, targs, paired=paired)
 
 
-def _finish_type_device(a, eng, idx, database, targs) -> int:
+def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> int:
     """Allele choice (metamlst.py:133-151, 244), pile-up and majority consensus on the device, queued behind pass 1
-    (mlst_typing_enqueue): one host synchronisation per sample instead of three (statistics, host choice, pile-up)."""
+    (mlst_typing_enqueue): one host synchronisation per sample instead of three (statistics, host choice, pile-up).
+    --write-sam: then the alignments to the alleles chosen there, as <out>/<sample>.sam (paired: the reads were submitted as pairs)."""
     eng.typing_enqueue(penalty=targs.penalty)
     st, chosen, letters = eng.typing_fetch()
-    return _finish_type(a, idx, database, targs, st, None, typed=(chosen, letters))
+    rc = _finish_type(a, idx, database, targs, st, None, typed=(chosen, letters))
+    if rc == 0 and a.write_sam:
+        from .samout import write_sam
+        alleles = [chosen[l] for l in sorted(chosen)]
+        write_sam(a.o + "/" + sample_name(a.READS) + ".sam", idx, alleles, eng.export_alignments(alleles), paired)
+    return rc
 
 
 class _FileReader:

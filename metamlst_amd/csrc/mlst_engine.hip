@@ -3685,6 +3685,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "fastq_tile.h"
 #include "bam_tile.h"
 #include "msa_dev.h"
+#include "aln_export.h"
 
 // ================================================================== host side
 struct EvPair { hipEvent_t a, b; int which; };
@@ -3814,6 +3815,13 @@ struct mlst_handle {
              u8* d_seq = nullptr; u64 cap_seq = 0; u64* d_off = nullptr; u64 cap_off = 0; u16* d_tab = nullptr; u64 cap_tab = 0;
              u32* d_slot = nullptr; u8* d_end = nullptr; u64 cap_end = 0; u32* d_tb = nullptr; u64 cap_tb = 0; u8* d_rows = nullptr; u64 cap_rows = 0;
              u32* h_width = nullptr; } msa;
+    // the alignments to the chosen alleles as records (mlst_alignments_export / mlst_alignments_fetch; csrc/aln_export.h): no part of a
+    // sample's state.  Per item: its AxItem, the list of items for the banded SW, three offset tables (records, CIGAR operations,
+    // bases); per workgroup of FQT_GROUP items their sums; desc: three FqtDev then three FqtMeta (k_fqt_scan / k_fqt_add), h_tot the
+    // pinned mirror of the FqtMeta; d_out: the record arrays of the last export (out points into it); the buffers grow and stay
+    struct { bool done = false; u64 n_rec = 0, n_cig = 0, n_seq = 0; int* d_lc = nullptr; u64 cap_lc = 0; AxItem* d_meta = nullptr; u64* d_dp = nullptr;
+             u64* d_off = nullptr; u64 cap_items = 0; u64* d_gs = nullptr; u64 cap_groups = 0; u8* d_desc = nullptr; u8* h_tot = nullptr;
+             u8* d_out = nullptr; u64 cap_out = 0; AxOut out; } ax;
 };
 
 static std::string g_create_err;
@@ -4004,6 +4012,8 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     if (h->tile.h_fqt) hipHostFree(h->tile.h_fqt);
     hipFree(h->msa.d_seq); hipFree(h->msa.d_off); hipFree(h->msa.d_tab); hipFree(h->msa.d_slot); hipFree(h->msa.d_end); hipFree(h->msa.d_tb); hipFree(h->msa.d_rows);
     if (h->msa.h_width) hipHostFree(h->msa.h_width);
+    hipFree(h->ax.d_lc); hipFree(h->ax.d_meta); hipFree(h->ax.d_dp); hipFree(h->ax.d_off); hipFree(h->ax.d_gs); hipFree(h->ax.d_desc); hipFree(h->ax.d_out);
+    if (h->ax.h_tot) hipHostFree(h->ax.h_tot);
     hipFree(h->d_bgzf); hipFree(h->d_bgzf_blk); hipFree(h->d_fq_carry); h->d_bgzf = nullptr; h->d_bgzf_blk = nullptr; h->d_fq_carry = nullptr; h->cap_bgzf = h->cap_bgzf_blk = h->cap_fq_carry = h->fq_carry_len = 0;
     hipFree(h->d_packed); hipFree(h->d_qrows); hipFree(h->d_lens); hipFree(h->d_counts); hipFree(h->d_dist); hipFree(h->d_query);
     for (auto* g : {&h->g_submit, &h->g_typing}) if (g->exec) hipGraphExecDestroy(g->exec);
@@ -6883,6 +6893,112 @@ extern "C" int mlst_pileup_alignments(mlst_handle* h, const uint32_t* chosen, ui
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     cleanup();
     if (e != hipSuccess) return fail(h, MLST_E_HIP, "mlst_pileup_alignments: %s", hipGetErrorString(e));
+    return MLST_OK;
+}
+
+// ---- the alignments to the chosen alleles as records (include/mlst.h; kernels: csrc/aln_export.h) ----
+// a handle has no stream of ready-made alignments, of mate files or of BAM reads open (what every entry that must see a whole sample asks)
+static int ax_refuse_open(mlst_handle* h) {
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
+    if (h->pair_open || h->bzp.on) return fail(h, MLST_E_INVALID, "a paired BGZF stream is open (its last chunk was not marked final)");
+    return MLST_OK;
+}
+extern "C" int mlst_alignments_export(mlst_handle* h, const uint32_t* chosen, uint32_t n, uint64_t* n_rec_out, uint64_t* n_cigar_out, uint64_t* n_bases_out) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    auto& X = h->ax;
+    X.done = false;
+    { int rc_ = ax_refuse_open(h); if (rc_) return rc_; }
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    if (n && !chosen) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    const u64 nl = h->n_loci;
+    std::vector<int> lc(nl ? nl : 1, -1);
+    for (u32 k = 0; k < n; k++) {
+        const u32 a = chosen[k]; if (a >= h->n_alleles) return fail(h, MLST_E_INVALID, "chosen allele %u out of range", a);
+        const u32 L = h->allele_locus[a]; if (lc[L] >= 0) return fail(h, MLST_E_INVALID, "two chosen alleles for locus %u", L);
+        lc[L] = (int)a;
+    }
+    // the item count sizes the per-item tables (a first, small wait; the one behind the scans sizes the output)
+    Counters c;
+    HIPCHK(h, hipMemcpyAsync(&c, h->E.ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 ni = std::min<u64>(c.n_items, h->E.cap_items);
+    X.n_rec = X.n_cig = X.n_seq = 0;
+    if (ni && h->max_wpr) {
+        const u64 ng = (ni + FQT_GROUP - 1) / FQT_GROUP;
+        if (X.cap_lc < nl) { hipFree(X.d_lc); X.d_lc = nullptr; X.cap_lc = 0; HIPCHK(h, dmalloc(&X.d_lc, nl)); X.cap_lc = nl; }
+        if (X.cap_items < ni) {
+            hipFree(X.d_meta); hipFree(X.d_dp); hipFree(X.d_off); X.d_meta = nullptr; X.d_dp = nullptr; X.d_off = nullptr; X.cap_items = 0;
+            HIPCHK(h, dmalloc(&X.d_meta, ni)); HIPCHK(h, dmalloc(&X.d_dp, ni + 1)); HIPCHK(h, dmalloc(&X.d_off, 3 * ni));
+            X.cap_items = ni;
+        }
+        if (X.cap_groups < ng) { hipFree(X.d_gs); X.d_gs = nullptr; X.cap_groups = 0; HIPCHK(h, dmalloc(&X.d_gs, 3 * ng)); X.cap_groups = ng; }
+        if (!X.d_desc) HIPCHK(h, dmalloc(&X.d_desc, 3 * (sizeof(FqtDev) + sizeof(FqtMeta))));
+        if (!X.h_tot) { void* p = nullptr; HIPCHK(h, hipHostMalloc(&p, 3 * sizeof(FqtMeta), hipHostMallocDefault)); X.h_tot = (u8*)p; }
+        u64* dp_n = X.d_dp + ni;                     // the list's length sits behind its ni entries
+        u64* off[3] = {X.d_off, X.d_off + X.cap_items, X.d_off + 2 * X.cap_items};
+        u64* gs[3] = {X.d_gs, X.d_gs + X.cap_groups, X.d_gs + 2 * X.cap_groups};
+        FqtDev* d_dev = (FqtDev*)X.d_desc; FqtMeta* d_met = (FqtMeta*)(X.d_desc + 3 * sizeof(FqtDev));
+        FqtDev D[3];
+        memset((void*)D, 0, sizeof D);
+        for (int q = 0; q < 3; q++) { D[q].wex = off[q]; D[q].gsum = gs[q]; D[q].meta = d_met + q; D[q].n_recs = ni; }
+        HIPCHK(h, hipMemcpyAsync(X.d_lc, lc.data(), nl * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(d_dev, D, sizeof D, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemsetAsync(d_met, 0, 3 * sizeof(FqtMeta), h->stream));
+        HIPCHK(h, hipMemsetAsync(dp_n, 0, 8, h->stream));
+        const unsigned gw = (unsigned)grid_for(ni, 1, 8192);      // one-wave workgroups, as k_pileup
+        if (h->max_wpr <= 10) hipLaunchKernelGGL(k_ax_ungapped_160, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, (const int*)X.d_lc, ni, X.d_meta, X.d_dp, dp_n);
+        else hipLaunchKernelGGL(k_ax_ungapped_320, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, (const int*)X.d_lc, ni, X.d_meta, X.d_dp, dp_n);
+        hipLaunchKernelGGL(k_ax_dp<false>, dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, (const int*)X.d_lc, (const u64*)X.d_dp, (const u64*)dp_n, h->d_tb,
+                           X.d_meta, (const u64*)nullptr, (u32*)nullptr);
+        hipLaunchKernelGGL(k_ax_local, dim3((unsigned)ng), dim3(1024), 0, h->stream, (const AxItem*)X.d_meta, ni, off[0], off[1], off[2], gs[0], gs[1], gs[2]);
+        for (int q = 0; q < 3; q++) {
+            hipLaunchKernelGGL(k_fqt_scan, dim3(1), dim3(1024), 0, h->stream, (const FqtDev*)(d_dev + q), ng);
+            hipLaunchKernelGGL(k_fqt_add, dim3((unsigned)ng), dim3(1024), 0, h->stream, (const FqtDev*)(d_dev + q));
+        }
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(X.h_tot, d_met, 3 * sizeof(FqtMeta), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));      // the totals size the record arrays
+        const FqtMeta* T = (const FqtMeta*)X.h_tot;
+        const u64 nr = T[0].n_windows, nc = T[1].n_windows, ns = T[2].n_windows;
+        // one block: the 8-byte arrays first, then the 4-byte ones, then the bytes
+        const u64 need = (nr + 2 * (nr + 1)) * 8 + (5 * nr + nc) * 4 + nr + 2 * ns + 64;
+        if (X.cap_out < need) { hipFree(X.d_out); X.d_out = nullptr; X.cap_out = 0; HIPCHK(h, dmalloc(&X.d_out, need)); X.cap_out = need; }
+        AxOut& O = X.out; u8* p = X.d_out;
+        O.read_index = (u64*)p; p += nr * 8; O.cigar_off = (u64*)p; p += (nr + 1) * 8; O.seq_off = (u64*)p; p += (nr + 1) * 8;
+        O.allele = (u32*)p; p += nr * 4; O.pos0 = (int*)p; p += nr * 4; O.as = (int*)p; p += nr * 4; O.xm = (int*)p; p += nr * 4; O.diag = (int*)p; p += nr * 4;
+        O.cigar = (u32*)p; p += nc * 4; O.flags = p; p += nr; O.seq = p; p += ns; O.qual = p;
+        hipLaunchKernelGGL(k_ax_emit, dim3(gw), dim3(64), 0, h->stream, h->d_E, (const int*)X.d_lc, (const AxItem*)X.d_meta, ni, (const u64*)off[0],
+                           (const u64*)off[1], (const u64*)off[2], O, nr, nc, ns);
+        hipLaunchKernelGGL(k_ax_dp<true>, dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, (const int*)X.d_lc, (const u64*)X.d_dp, (const u64*)dp_n, h->d_tb,
+                           X.d_meta, (const u64*)off[1], O.cigar);
+        HIPCHK(h, hipGetLastError());
+        X.n_rec = nr; X.n_cig = nc; X.n_seq = ns;
+    }
+    X.done = true;
+    if (n_rec_out) *n_rec_out = X.n_rec;
+    if (n_cigar_out) *n_cigar_out = X.n_cig;
+    if (n_bases_out) *n_bases_out = X.n_seq;
+    return MLST_OK;
+}
+extern "C" int mlst_alignments_fetch(mlst_handle* h, uint64_t* read_index, uint32_t* rec_allele, int32_t* rec_pos0, int32_t* rec_as, int32_t* rec_xm,
+                                     int32_t* rec_diag, uint8_t* rec_flags, uint64_t* cigar_off, uint32_t* cigar, uint64_t* seq_off, uint8_t* seq, uint8_t* qual) {
+    if (!h) return MLST_E_INVALID;
+    auto& X = h->ax;
+    if (!X.done) return fail(h, MLST_E_INVALID, "no finished export (mlst_alignments_export comes first)");
+    if (!cigar_off || !seq_off) return fail(h, MLST_E_INVALID, "NULL argument");
+    const u64 nr = X.n_rec, nc = X.n_cig, ns = X.n_seq;
+    if (nr == 0) { cigar_off[0] = 0; seq_off[0] = 0; return MLST_OK; }
+    if (!read_index || !rec_allele || !rec_pos0 || !rec_as || !rec_xm || !rec_diag || !rec_flags || !cigar || !seq || !qual) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    const AxOut& O = X.out;
+#define DOWN(dst, src, cnt, T) HIPCHK(h, hipMemcpyAsync(dst, src, (u64)(cnt) * sizeof(T), hipMemcpyDeviceToHost, h->stream))
+    DOWN(read_index, O.read_index, nr, u64); DOWN(rec_allele, O.allele, nr, u32); DOWN(rec_pos0, O.pos0, nr, int); DOWN(rec_as, O.as, nr, int);
+    DOWN(rec_xm, O.xm, nr, int); DOWN(rec_diag, O.diag, nr, int); DOWN(rec_flags, O.flags, nr, u8);
+    DOWN(cigar_off, O.cigar_off, nr + 1, u64); DOWN(cigar, O.cigar, nc, u32); DOWN(seq_off, O.seq_off, nr + 1, u64);
+    DOWN(seq, O.seq, ns, u8); DOWN(qual, O.qual, ns, u8);
+#undef DOWN
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return MLST_OK;
 }
 

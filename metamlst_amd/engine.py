@@ -7,6 +7,7 @@ imported from here.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
@@ -55,6 +56,32 @@ def default_params() -> MlstParams:
 
 class MlstError(RuntimeError):
     pass
+
+
+@dataclasses.dataclass
+class Alignments:
+    """The records of Engine.export_alignments (mlst_alignments_fetch, include/mlst.h): one entry per record in read_index ..
+    flags (bit 0 strand, bit 1 used_dp); cigar (len << 4 | op) and seq / qual (ASCII on the reference strand, raw Phred) delimited
+    by cigar_off / seq_off[n_rec + 1]."""
+    read_index: np.ndarray
+    allele: np.ndarray
+    pos0: np.ndarray
+    as_: np.ndarray
+    xm: np.ndarray
+    diag: np.ndarray
+    flags: np.ndarray
+    cigar_off: np.ndarray
+    cigar: np.ndarray
+    seq_off: np.ndarray
+    seq: np.ndarray
+    qual: np.ndarray
+
+    def __len__(self) -> int:
+        return len(self.read_index)
+
+    def pileup_arrays(self) -> tuple:
+        """the arrays Engine.pileup_alignments takes behind `chosen`, in its order"""
+        return (self.allele, self.pos0, self.as_, self.xm, self.cigar_off, self.cigar, self.seq_off, self.seq, self.qual)
 
 
 class BgzfCrcMismatch(MlstError):
@@ -157,6 +184,8 @@ def load_library(path: str | None = None):
         "mlst_consensus_from_counts_device": (C.c_int, [H, u32p, C.c_uint64, C.c_uint32, C.c_char, u8p]),
         "mlst_pileup_alignments": (C.c_int, [H, u32p, C.c_uint32, C.c_uint64, u32p, i32p, i32p, i32p, u64p, u32p, u64p, u8p, u8p,
                                              C.c_int32, C.c_int32, C.c_int32, u32p]),
+        "mlst_alignments_export": (C.c_int, [H, u32p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "mlst_alignments_fetch": (C.c_int, [H, u64p, u32p, i32p, i32p, i32p, i32p, u8p, u64p, u32p, u64p, u8p, u8p]),
         "mlst_typing_layout": (C.c_int, [H, u64p, C.POINTER(C.c_uint64)]),
         "mlst_typing_enqueue": (C.c_int, [H, C.c_int32, C.c_uint32, C.c_char]),
         "mlst_typing_choose_pileup": (C.c_int, [H, C.c_int32, u32p]),
@@ -842,6 +871,21 @@ class Engine:
             out[int(a)] = counts[at:at + L]
             at += L
         return out
+
+    def export_alignments(self, chosen) -> Alignments:
+        """The engine's alignments of the sample's work items to the chosen alleles (allele indices, one per locus at the most), as
+        records: what the pile-up of `chosen` piles up, the records that fail its AS / XM filter included (mlst_alignments_export /
+        mlst_alignments_fetch).  Reads the sample's state and changes none of it."""
+        ch = np.ascontiguousarray(chosen, np.uint32)
+        nr, nc, ns = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mlst_alignments_export(self._h, _ptr(ch) if len(ch) else None, len(ch), C.byref(nr), C.byref(nc), C.byref(ns)),
+                    "mlst_alignments_export")
+        nr, nc, ns = int(nr.value), int(nc.value), int(ns.value)
+        a = Alignments(np.zeros(nr, np.uint64), np.zeros(nr, np.uint32), np.zeros(nr, np.int32), np.zeros(nr, np.int32), np.zeros(nr, np.int32),
+                       np.zeros(nr, np.int32), np.zeros(nr, np.uint8), np.zeros(nr + 1, np.uint64), np.zeros(nc, np.uint32),
+                       np.zeros(nr + 1, np.uint64), np.zeros(ns, np.uint8), np.zeros(ns, np.uint8))
+        self._check(self.lib.mlst_alignments_fetch(self._h, *[_ptr(getattr(a, f.name)) for f in dataclasses.fields(a)]), "mlst_alignments_fetch")
+        return a
 
     # ---- typing tail on the device ----
     def typing_enqueue(self, penalty: int = 100, mincov: int = 1, none_char: str = "N"):
