@@ -364,6 +364,37 @@ int mlst_alignments_fetch(mlst_handle* h, uint64_t* read_index, uint32_t* rec_al
                           uint64_t* cigar_off /* n_rec+1 */, uint32_t* cigar, uint64_t* seq_off /* n_rec+1 */,
                           uint8_t* seq, uint8_t* qual);
 
+/* ---- EVERY alignment of the sample as SAM text, formatted on the device (what `bowtie2 -a` leaves in front of metamlst.py) ---------
+ * Records: one for every (work item, allele of the item's locus) whose alignment, decided exactly as pass 1 decides that pair
+ *   (oracle/mlst_oracle.c: align_pair -- the ungapped alignment, or the banded one where the gap trigger fires), has
+ *   score >= the floor of the read's length && score > 0: the records pass 1 counts in MLST_CNT_TOTAL_RECORDS.  Records that fail the
+ *   AS / XM tag filter are written too; mlst_set_depth_cap is ignored.
+ * Header: the caller's (metamlst_amd/samout.py: @HD VN:1.6 SO:unsorted GO:query, one @SQ per loaded allele in index order, @PG).
+ * Order: work items by (read index, locus index, strand, diag), inside an item the alleles ascending: all records of a read are
+ *   consecutive.  The bytes depend neither on the order of the item list nor on round_bytes.
+ * Columns: QNAME r<k>, k = the read index (read index >> 1 with paired != 0); FLAG 16 * strand, plus 256 on every record of a read
+ *   index except its best one (the highest AS, ties to the first in file order); RNAME the allele's label; POS = the leftmost aligned
+ *   column + 1; MAPQ 255; CIGAR as mlst_alignments_fetch describes it; * 0 0; SEQ on the reference strand; QUAL chr(min(q, 93) + 33);
+ *   AS:i [XS:i] XN:i:0 XM:i XO:i XG:i NM:i YT:Z:UU.  XS:i is present iff the read index has two records or more, and is the
+ *   highest AS among the read's other records (a read with one record has XO in the 15th column: quirk Q1 by construction).  AS and XM
+ *   are the true values; XO = the I and D runs, XG = their columns, NM = XG + the M columns whose SEQ letter is not the allele's (an N
+ *   on either side included).
+ * mlst_alignments_text_open sorts the item list (on the host, per item), bounds every item's text from above -- (alleles of its locus)
+ *   x (10 n + the longest label + 192 bytes for a read of n bases) -- and cuts the list into rounds of at most round_bytes (0: 256 MiB)
+ *   of bounded text at read boundaries.  A read whose own bound exceeds round_bytes: MLST_E_LIMIT, the message names the bytes
+ *   needed.  names / name_off[n_alleles + 1]: the RNAME labels, uploaded once per open.
+ * mlst_alignments_text_next formats one round: whole lines only, n_bytes of them into text (host memory of cap bytes), n_records
+ *   lines; done = 1 with the last round (and with n_bytes = 0 when there is none left).  text = NULL with cap = 0 asks for the size of
+ *   the round that comes next (n_bytes, n_records; done = 1 iff none is left) and consumes nothing.
+ * The sample's state is read and none of it is changed: the statistics, a later mlst_pileup* / mlst_typing_* / mlst_alignments_export
+ *   and mlst_reset_sample behave as before (a reset closes the export); an open BGZF piece is finished first.
+ *   Refused with MLST_E_INVALID: a call while a BAM, SAM or paired stream is open on the handle, mlst_alignments_text_next without an
+ *   open export, cap smaller than the round. */
+int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, const uint64_t* name_off /* n_alleles+1 */, int paired,
+                              uint64_t round_bytes /* 0: 256 MiB */);
+int mlst_alignments_text_next(mlst_handle* h, uint8_t* text, uint64_t cap, uint64_t* n_bytes, uint64_t* n_records, int* done);
+int mlst_alignments_text_close(mlst_handle* h);
+
 /* ---- ready-made alignments straight from a BGZF BAM (the reference's one input, metamlst.py:34) ------------------------------
  * The file is streamed twice, as the reference reads it twice (samtools view, then pysam): pass 1 is the hit accumulation of
  * metamlst.py:101-130 (what mlst_submit_* do for reads), pass 2 the pile-up of the chosen contigs (mlst_pileup_alignments).  The

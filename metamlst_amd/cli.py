@@ -5,6 +5,7 @@
     python -m metamlst_amd.cli type  LONG.fastq --long-reads [--tile LEN,STEP] -d DB   (reads longer than 320 bases, cut into windows)
     python -m metamlst_amd.cli type  HIFI.bam --long-bam-reads [--tile LEN,STEP] -d DB  (the same for the reads of an unaligned BAM)
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam -d DB      (also <out>/<sample>.sam: the alignments to the chosen alleles)
+    python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam-all -d DB  (also <out>/<sample>.all.sam: every alignment, as bowtie2 -a would leave it)
     python -m metamlst_amd.cli merge FOLDER -d DB [-z 5] [--filter ...] [--meta ...] [--idField ...] [--aligner auto|gpu|muscle]   (metamlst-merge.py:35-49)
     python -m metamlst_amd.cli index -d DB [-s seqs.fasta,...] [-t typings.txt,...] [-q dump.fa] [--list]   (metamlst-index.py:24-33)
 
@@ -84,6 +85,11 @@ def _type_parser(sub):
                         "typing tail chose, as SAM text (metamlst_amd/samout.py: QNAME r<read index>, secondary records flagged 256, the "
                         "optional fields of bowtie2 with XS a placeholder).  One sample of reads on one GPU: it goes with none of "
                         "--alignments (the file is the input there), several samples or a folder, and --gpus N")
+    p.add_argument("--write-sam-all", dest="write_sam_all", action="store_true",
+                   help="after the .nfo, write <out>/<sample>.all.sam: EVERY alignment the engine decides -- each work item against every "
+                        "allele of its locus, what `bowtie2 -a` leaves in front of metamlst.py -- as SAM text formatted on the GPU "
+                        "(metamlst_amd/samout.py: one @SQ per loaded allele, XS:i only where the read has a second record).  Accepted and "
+                        "refused where --write-sam is; both may be given")
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -208,15 +214,15 @@ def run_type(a, argv=None) -> int:
         print("no %s file found in " % ("FASTA" if a.contigs else "FASTQ") + ", ".join(a.READS))
         return 1
     many = len(samples) > 1
-    if a.write_sam:      # (refused before any GPU use)
+    for flag in [f for f, on in (("--write-sam", a.write_sam), ("--write-sam-all", a.write_sam_all)) if on]:      # (refused before any GPU use)
         if a.alignments:
-            print("--write-sam writes the engine's own alignments: with --alignments the file is the input")
+            print(flag + " writes the engine's own alignments: with --alignments the file is the input")
             return 1
         if many:
-            print("--write-sam takes one sample: several samples or a folder are typed without it")
+            print(flag + " takes one sample: several samples or a folder are typed without it")
             return 1
         if a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            print("--write-sam takes one GPU: a rank of --gpus N holds its own reads' alignments only")
+            print(flag + " takes one GPU: a rank of --gpus N holds its own reads' alignments only")
             return 1
     if many and (a.alignments or a.mates):
         print("several samples at once: FASTQ input only (use `r1.fq,r2.fq` for a sample made of two files)")
@@ -363,7 +369,7 @@ def run_type(a, argv=None) -> int:
         print(e, file=sys.stderr)
         database.closeConnection()
         return 1
-    if a.write_sam and not paired and not (long_reads or long_bam) and all(_is_reads_bam(f) for f in paths):      # (as submit_bam_reads decides it)
+    if (a.write_sam or a.write_sam_all) and not paired and not (long_reads or long_bam) and all(_is_reads_bam(f) for f in paths):      # (as submit_bam_reads decides it)
         from .samin import bam_first_read_flags
         paired = any((bam_first_read_flags(f) or 0) & 1 for f in paths)
     return _finish_type_device(a, eng, idx, database, targs, paired=paired)
@@ -372,7 +378,8 @@ def run_type(a, argv=None) -> int:
 def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> int:
     """Allele choice (metamlst.py:133-151, 244), pile-up and majority consensus on the device, queued behind pass 1
     (mlst_typing_enqueue): one host synchronisation per sample instead of three (statistics, host choice, pile-up).
-    --write-sam: then the alignments to the alleles chosen there, as <out>/<sample>.sam (paired: the reads were submitted as pairs)."""
+    --write-sam: then the alignments to the alleles chosen there, as <out>/<sample>.sam (paired: the reads were submitted as pairs);
+    --write-sam-all: then every alignment, as <out>/<sample>.all.sam."""
     eng.typing_enqueue(penalty=targs.penalty)
     st, chosen, letters = eng.typing_fetch()
     rc = _finish_type(a, idx, database, targs, st, None, typed=(chosen, letters))
@@ -380,6 +387,9 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
         from .samout import write_sam
         alleles = [chosen[l] for l in sorted(chosen)]
         write_sam(a.o + "/" + sample_name(a.READS) + ".sam", idx, alleles, eng.export_alignments(alleles), paired)
+    if rc == 0 and a.write_sam_all:
+        from .samout import write_sam_all
+        write_sam_all(a.o + "/" + sample_name(a.READS) + ".all.sam", idx, eng, paired)
     return rc
 
 

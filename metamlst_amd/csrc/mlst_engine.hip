@@ -3686,6 +3686,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "bam_tile.h"
 #include "msa_dev.h"
 #include "aln_export.h"
+#include "aln_text.h"
 
 // ================================================================== host side
 struct EvPair { hipEvent_t a, b; int which; };
@@ -3822,6 +3823,13 @@ struct mlst_handle {
     struct { bool done = false; u64 n_rec = 0, n_cig = 0, n_seq = 0; int* d_lc = nullptr; u64 cap_lc = 0; AxItem* d_meta = nullptr; u64* d_dp = nullptr;
              u64* d_off = nullptr; u64 cap_items = 0; u64* d_gs = nullptr; u64 cap_groups = 0; u8* d_desc = nullptr; u8* h_tot = nullptr;
              u8* d_out = nullptr; u64 cap_out = 0; AxOut out; } ax;
+    // every alignment as SAM text (mlst_alignments_text_open / _next / _close; csrc/aln_text.h): no part of a sample's state.  Per export:
+    // the sorted item list (perm, pair_off, item_read, read_first), the RNAME labels and the rounds; per round (sized by the largest
+    // one): AtPair and line offset per pair, the list of the banded SW, AtRead per read, the workgroups' sums; d_text = the round's text.
+    struct AtState { bool open = false, ready = false; size_t next = 0; std::vector<AtRound> rounds; u64 round_bytes = 0, round_recs = 0, max_pairs = 0;
+             u32* d_perm = nullptr; u64* d_pair_off = nullptr; u32* d_item_read = nullptr; u64* d_read_first = nullptr; u8* d_names = nullptr; u64* d_name_off = nullptr;
+             AtPair* d_meta = nullptr; AtRead* d_reads = nullptr; u64* d_wex = nullptr; u64* d_gsum = nullptr; u64* d_dp = nullptr; u8* d_desc = nullptr;
+             u8* d_text = nullptr; u64 cap_text = 0; u8* h_tot = nullptr; } at;
 };
 
 static std::string g_create_err;
@@ -3839,6 +3847,7 @@ static void bz_free(mlst_handle* h);
 static int bam_flush(mlst_handle* h);     // BAM input: the piece in flight is finished (its errors are this call's)
 static void bam_drop(mlst_handle* h, bool release);      // the BAM stream is closed and forgotten (release: its buffers too)
 static bool bam_is_open(const mlst_handle* h);
+static void at_free(mlst_handle* h);      // the per-export tables of mlst_alignments_text_*
 static const char* bam_kind(const mlst_handle* h);      // "BAM" or "SAM": what the open stream of ready-made alignments takes
 template <typename T> static hipError_t dmalloc(T** p, u64 n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
 template <typename T> static hipError_t dmalloc(GP<T>* p, u64 n) { return hipMalloc((void**)&p->p, (n ? n : 1) * sizeof(T)); }
@@ -4014,6 +4023,7 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     if (h->msa.h_width) hipHostFree(h->msa.h_width);
     hipFree(h->ax.d_lc); hipFree(h->ax.d_meta); hipFree(h->ax.d_dp); hipFree(h->ax.d_off); hipFree(h->ax.d_gs); hipFree(h->ax.d_desc); hipFree(h->ax.d_out);
     if (h->ax.h_tot) hipHostFree(h->ax.h_tot);
+    at_free(h); hipFree(h->at.d_text); hipFree(h->at.d_desc); if (h->at.h_tot) hipHostFree(h->at.h_tot);
     hipFree(h->d_bgzf); hipFree(h->d_bgzf_blk); hipFree(h->d_fq_carry); h->d_bgzf = nullptr; h->d_bgzf_blk = nullptr; h->d_fq_carry = nullptr; h->cap_bgzf = h->cap_bgzf_blk = h->cap_fq_carry = h->fq_carry_len = 0;
     hipFree(h->d_packed); hipFree(h->d_qrows); hipFree(h->d_lens); hipFree(h->d_counts); hipFree(h->d_dist); hipFree(h->d_query);
     for (auto* g : {&h->g_submit, &h->g_typing}) if (g->exec) hipGraphExecDestroy(g->exec);
@@ -4034,6 +4044,7 @@ static int reset_sample_state(mlst_handle* h) {
     for (u64& x : h->tile.info) x = 0;
     h->pc_len[0] = h->pc_len[1] = 0; h->pair_open = false;      // (mlst_submit_fastq_bgzf_pair: both files' carries)
     bam_drop(h, false);
+    h->at.open = false;      // (an export of the sample that is dropped)
     return MLST_OK;
 }
 
@@ -6999,6 +7010,174 @@ extern "C" int mlst_alignments_fetch(mlst_handle* h, uint64_t* read_index, uint3
     DOWN(seq, O.seq, ns, u8); DOWN(qual, O.qual, ns, u8);
 #undef DOWN
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLST_OK;
+}
+
+// ---- every alignment as SAM text, written on the device (include/mlst.h; kernels: csrc/aln_text.h) ----
+static void at_free(mlst_handle* h) {
+    auto& T = h->at;
+    hipFree(T.d_perm); hipFree(T.d_pair_off); hipFree(T.d_item_read); hipFree(T.d_read_first); hipFree(T.d_names); hipFree(T.d_name_off);
+    hipFree(T.d_meta); hipFree(T.d_reads); hipFree(T.d_wex); hipFree(T.d_gsum); hipFree(T.d_dp);
+    T.d_perm = nullptr; T.d_pair_off = nullptr; T.d_item_read = nullptr; T.d_read_first = nullptr; T.d_names = nullptr; T.d_name_off = nullptr;
+    T.d_meta = nullptr; T.d_reads = nullptr; T.d_wex = nullptr; T.d_gsum = nullptr; T.d_dp = nullptr;
+    T.rounds.clear(); T.next = 0; T.open = false; T.ready = false;
+}
+extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, const uint64_t* name_off, int paired, uint64_t round_bytes) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    auto& T = h->at;
+    hipSetDevice(h->device);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    at_free(h);      // (an export left open, or one whose sample was reset)
+    { int rc_ = ax_refuse_open(h); if (rc_) return rc_; }
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    if (!names || !name_off) return fail(h, MLST_E_INVALID, "NULL argument");
+    const u64 na = h->n_alleles, nl = h->n_loci;
+    u64 max_name = 0;
+    for (u64 a = 0; a < na; a++) {
+        if (name_off[a + 1] < name_off[a]) return fail(h, MLST_E_INVALID, "name_off descends at allele %llu", (unsigned long long)a);
+        max_name = std::max<u64>(max_name, name_off[a + 1] - name_off[a]);
+    }
+    if (!round_bytes) round_bytes = 256ull << 20;
+    std::vector<u32> nall(nl ? nl : 1, 0);
+    for (u64 a = 0; a < na; a++) nall[h->allele_locus[a]]++;
+    for (u64 l = 0; l < nl; l++) if (nall[l] >= (1u << 20)) return fail(h, MLST_E_LIMIT, "locus %llu has %u alleles: the export takes fewer than 2^20", (unsigned long long)l, nall[l]);
+    // the item list, the reads' indices and lengths (one wait; everything below is per item, nothing per record)
+    Counters c;
+    HIPCHK(h, hipMemcpyAsync(&c, h->E.ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const u64 ni = h->max_wpr ? std::min<u64>(c.n_items, h->E.cap_items) : 0, nret = std::min<u64>(c.n_ret, h->E.cap_ret);
+    std::vector<ItemDev> items(ni ? ni : 1); std::vector<u64> ridx(nret ? nret : 1); std::vector<u16> rlen(nret ? nret : 1);
+    if (ni) {
+        HIPCHK(h, hipMemcpyAsync(items.data(), h->E.items, ni * sizeof(ItemDev), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(ridx.data(), h->E.ret_ridx, nret * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(rlen.data(), h->E.ret_len, nret * 2, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    for (u64 i = 0; i < ni; i++) if (items[i].ret >= nret || items[i].locus >= nl) return fail(h, MLST_E_HIP, "work item %llu is inconsistent", (unsigned long long)i);
+    std::vector<u32> perm(ni ? ni : 1);
+    for (u64 i = 0; i < ni; i++) perm[i] = (u32)i;
+    std::sort(perm.begin(), perm.begin() + ni, [&](u32 x, u32 y) {
+        const ItemDev& a = items[x]; const ItemDev& b = items[y];
+        const u64 ra = ridx[a.ret], rb = ridx[b.ret];
+        if (ra != rb) return ra < rb;
+        if (a.locus != b.locus) return a.locus < b.locus;
+        if (a.strand != b.strand) return a.strand < b.strand;
+        if (a.diag != b.diag) return a.diag < b.diag;
+        return x < y;
+    });
+    // reads, pairs in front of every item, a bound on every read's text; rounds cut at read boundaries
+    std::vector<u64> pair_off(ni + 1, 0), read_first; std::vector<u32> item_read(ni ? ni : 1); std::vector<u64> read_bound;
+    for (u64 k = 0; k < ni; k++) {
+        const ItemDev& it = items[perm[k]];
+        if (k == 0 || ridx[it.ret] != ridx[items[perm[k - 1]].ret]) { read_first.push_back(k); read_bound.push_back(0); }
+        item_read[k] = (u32)(read_first.size() - 1);
+        pair_off[k + 1] = pair_off[k] + nall[it.locus];
+        read_bound.back() += (u64)nall[it.locus] * at_line_bound((u32)(rlen[it.ret] & 0x7FFFu), max_name);
+    }
+    const u64 nr = read_first.size();
+    read_first.push_back(ni);
+    u64 worst = 0;
+    for (u64 r = 0; r < nr; r++) worst = std::max(worst, read_bound[r]);
+    if (worst > round_bytes) return fail(h, MLST_E_LIMIT, "round_bytes %llu is too small: the records of one read may need %llu bytes", (unsigned long long)round_bytes, (unsigned long long)worst);
+    std::vector<AtRound> rounds;
+    u64 max_pairs = 0, max_reads = 0;
+    for (u64 r = 0; r < nr;) {
+        u64 r1 = r, sum = 0;
+        while (r1 < nr && sum + read_bound[r1] <= round_bytes) sum += read_bound[r1++];
+        AtRound R; R.r0 = r; R.r1 = r1; R.k0 = read_first[r]; R.k1 = read_first[r1]; R.pb = pair_off[R.k0]; R.n_pairs = pair_off[R.k1] - R.pb;
+        rounds.push_back(R); max_pairs = std::max(max_pairs, R.n_pairs); max_reads = std::max(max_reads, r1 - r);
+        r = r1;
+    }
+    const u64 nbytes = name_off[na] - name_off[0], max_groups = (max_pairs + FQT_GROUP - 1) / FQT_GROUP;
+    auto bad = [&](hipError_t e) { at_free(h); return fail(h, MLST_E_HIP, "mlst_alignments_text_open: %s", hipGetErrorString(e)); };
+#define ATCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bad(e_); } while (0)
+    ATCHK(dmalloc(&T.d_perm, ni)); ATCHK(dmalloc(&T.d_pair_off, ni + 1)); ATCHK(dmalloc(&T.d_item_read, ni)); ATCHK(dmalloc(&T.d_read_first, nr + 1));
+    ATCHK(dmalloc(&T.d_names, nbytes)); ATCHK(dmalloc(&T.d_name_off, na + 1));
+    ATCHK(dmalloc(&T.d_meta, max_pairs)); ATCHK(dmalloc(&T.d_reads, max_reads)); ATCHK(dmalloc(&T.d_wex, max_pairs)); ATCHK(dmalloc(&T.d_gsum, max_groups));
+    ATCHK(dmalloc(&T.d_dp, max_pairs + 2));      // the list, its length and the round's records behind it
+    if (!T.d_desc) ATCHK(dmalloc(&T.d_desc, sizeof(AtDev) + sizeof(FqtDev) + sizeof(FqtMeta)));
+    if (!T.h_tot) { void* p = nullptr; ATCHK(hipHostMalloc(&p, sizeof(FqtMeta) + 8, hipHostMallocDefault)); T.h_tot = (u8*)p; }
+    std::vector<u64> noff(na + 1);
+    for (u64 a = 0; a <= na; a++) noff[a] = name_off[a] - name_off[0];
+    if (ni) { ATCHK(hipMemcpyAsync(T.d_perm, perm.data(), ni * 4, hipMemcpyHostToDevice, h->stream)); ATCHK(hipMemcpyAsync(T.d_item_read, item_read.data(), ni * 4, hipMemcpyHostToDevice, h->stream)); }
+    ATCHK(hipMemcpyAsync(T.d_pair_off, pair_off.data(), (ni + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    ATCHK(hipMemcpyAsync(T.d_read_first, read_first.data(), (nr + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    if (nbytes) ATCHK(hipMemcpyAsync(T.d_names, names + name_off[0], nbytes, hipMemcpyHostToDevice, h->stream));
+    ATCHK(hipMemcpyAsync(T.d_name_off, noff.data(), (na + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    AtDev D; memset((void*)&D, 0, sizeof D);
+    D.perm = T.d_perm; D.pair_off = T.d_pair_off; D.item_read = T.d_item_read; D.read_first = T.d_read_first; D.names = T.d_names; D.name_off = T.d_name_off;
+    D.ascii = h->d_ascii; D.aoff = h->d_aoff; D.meta = T.d_meta; D.reads = T.d_reads; D.wex = T.d_wex; D.gsum = T.d_gsum;
+    D.dp_list = T.d_dp; D.dp_n = T.d_dp + max_pairs; D.n_rec = T.d_dp + max_pairs + 1; D.paired = paired ? 1 : 0;
+    FqtDev F; memset((void*)&F, 0, sizeof F);
+    F.wex = T.d_wex; F.gsum = T.d_gsum; F.meta = (FqtMeta*)(T.d_desc + sizeof(AtDev) + sizeof(FqtDev));
+    ATCHK(hipMemcpyAsync(T.d_desc, &D, sizeof D, hipMemcpyHostToDevice, h->stream));
+    ATCHK(hipMemcpyAsync(T.d_desc + sizeof(AtDev), &F, sizeof F, hipMemcpyHostToDevice, h->stream));
+    ATCHK(hipStreamSynchronize(h->stream));      // (the host vectors go out of scope)
+#undef ATCHK
+    T.rounds.swap(rounds); T.max_pairs = max_pairs; T.next = 0; T.ready = false; T.open = true;
+    return MLST_OK;
+}
+// the kernels of round T.next up to the lines' offsets; leaves the round's bytes and records in T.round_bytes / T.round_recs
+static int at_prepare(mlst_handle* h) {
+    auto& T = h->at;
+    const AtRound R = T.rounds[T.next];
+    const AtDev* d_D = (const AtDev*)T.d_desc; FqtDev* d_F = (FqtDev*)(T.d_desc + sizeof(AtDev)); FqtMeta* d_M = (FqtMeta*)(T.d_desc + sizeof(AtDev) + sizeof(FqtDev));
+    u64* dp_n = T.d_dp + T.max_pairs;      // the list's length and the round's records sit behind the largest round's list
+    const u64 ng = (R.n_pairs + FQT_GROUP - 1) / FQT_GROUP;
+    HIPCHK(h, hipMemsetAsync(dp_n, 0, 16, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_M, 0, sizeof(FqtMeta), h->stream));
+    HIPCHK(h, hipMemcpyAsync(&d_F->n_recs, &R.n_pairs, 8, hipMemcpyHostToDevice, h->stream));
+    const unsigned gw = (unsigned)grid_for(R.k1 - R.k0, 1, 8192);      // one-wave workgroups, as k_pileup
+    if (h->max_wpr <= 10) hipLaunchKernelGGL(k_at_decide_160, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
+    else hipLaunchKernelGGL(k_at_decide_320, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
+    hipLaunchKernelGGL(k_at_dp<false>, dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, (u8*)nullptr);
+    hipLaunchKernelGGL(k_at_reads, dim3((unsigned)grid_for(R.r1 - R.r0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R);
+    if (ng) {
+        hipLaunchKernelGGL(k_at_local, dim3((unsigned)ng), dim3(1024), 0, h->stream, T.d_wex, R.n_pairs, T.d_gsum);
+        hipLaunchKernelGGL(k_fqt_scan, dim3(1), dim3(1024), 0, h->stream, (const FqtDev*)d_F, ng);
+        hipLaunchKernelGGL(k_fqt_add, dim3((unsigned)ng), dim3(1024), 0, h->stream, (const FqtDev*)d_F);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(T.h_tot, d_M, sizeof(FqtMeta), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.h_tot + sizeof(FqtMeta), dp_n + 1, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // the total sizes the text
+    T.round_bytes = ((const FqtMeta*)T.h_tot)->n_windows; memcpy(&T.round_recs, T.h_tot + sizeof(FqtMeta), 8);
+    T.ready = true;
+    return MLST_OK;
+}
+extern "C" int mlst_alignments_text_next(mlst_handle* h, uint8_t* text, uint64_t cap, uint64_t* n_bytes, uint64_t* n_records, int* done) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    auto& T = h->at;
+    if (!T.open) return fail(h, MLST_E_INVALID, "no export is open (mlst_alignments_text_open comes first)");
+    { int rc_ = ax_refuse_open(h); if (rc_) return rc_; }
+    if (!n_bytes || !n_records || !done) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    *n_bytes = 0; *n_records = 0;
+    if (T.next >= T.rounds.size()) { *done = 1; return MLST_OK; }
+    if (!T.ready) { int rc_ = at_prepare(h); if (rc_) return rc_; }
+    *n_bytes = T.round_bytes; *n_records = T.round_recs; *done = 0;
+    if (!text && !cap) return MLST_OK;      // the size of the round that comes next: nothing is consumed
+    if (!text) return fail(h, MLST_E_INVALID, "NULL argument");
+    if (cap < T.round_bytes) return fail(h, MLST_E_INVALID, "cap %llu is smaller than the round: %llu bytes", (unsigned long long)cap, (unsigned long long)T.round_bytes);
+    if (T.round_bytes) {
+        const AtRound R = T.rounds[T.next];
+        if (T.cap_text < T.round_bytes) { hipFree(T.d_text); T.d_text = nullptr; T.cap_text = 0; HIPCHK(h, dmalloc(&T.d_text, T.round_bytes)); T.cap_text = T.round_bytes; }
+        const AtDev* d_D = (const AtDev*)T.d_desc;
+        hipLaunchKernelGGL(k_at_write, dim3((unsigned)grid_for(R.k1 - R.k0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R, T.d_text);
+        hipLaunchKernelGGL(k_at_dp<true>, dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, T.d_text);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(text, T.d_text, T.round_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    T.next++; T.ready = false;
+    *done = T.next >= T.rounds.size() ? 1 : 0;
+    return MLST_OK;
+}
+extern "C" int mlst_alignments_text_close(mlst_handle* h) {
+    if (!h) return MLST_E_INVALID;
+    hipSetDevice(h->device);
+    if (h->at.open) hipStreamSynchronize(h->stream);
+    at_free(h);
     return MLST_OK;
 }
 

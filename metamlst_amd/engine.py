@@ -186,6 +186,9 @@ def load_library(path: str | None = None):
                                              C.c_int32, C.c_int32, C.c_int32, u32p]),
         "mlst_alignments_export": (C.c_int, [H, u32p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mlst_alignments_fetch": (C.c_int, [H, u64p, u32p, i32p, i32p, i32p, i32p, u8p, u64p, u32p, u64p, u8p, u8p]),
+        "mlst_alignments_text_open": (C.c_int, [H, u8p, u64p, C.c_int, C.c_uint64]),
+        "mlst_alignments_text_next": (C.c_int, [H, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+        "mlst_alignments_text_close": (C.c_int, [H]),
         "mlst_typing_layout": (C.c_int, [H, u64p, C.POINTER(C.c_uint64)]),
         "mlst_typing_enqueue": (C.c_int, [H, C.c_int32, C.c_uint32, C.c_char]),
         "mlst_typing_choose_pileup": (C.c_int, [H, C.c_int32, u32p]),
@@ -886,6 +889,36 @@ class Engine:
                        np.zeros(nr + 1, np.uint64), np.zeros(ns, np.uint8), np.zeros(ns, np.uint8))
         self._check(self.lib.mlst_alignments_fetch(self._h, *[_ptr(getattr(a, f.name)) for f in dataclasses.fields(a)]), "mlst_alignments_fetch")
         return a
+
+    def export_sam_text(self, idx, paired: bool = False, round_bytes: int = 0):
+        """Every alignment of the sample as SAM records, formatted on the device (mlst_alignments_text_open / _next / _close; the
+        rule: samout's docstring): a generator of `bytes`, whole lines, one per round of at most round_bytes of bounded text
+        (0: 256 MiB).  idx: the loaded AlleleIndex (its labels are the RNAMEs); paired: the sample was submitted as pairs.  The
+        rounds leave the device through one page-locked buffer; the export is closed on exhaustion and on error.  Reads the
+        sample's state and changes none of it."""
+        labels = [idx.label(a).encode() for a in range(idx.n_alleles)]
+        name_off = np.zeros(len(labels) + 1, np.uint64)
+        name_off[1:] = np.cumsum([len(x) for x in labels], dtype=np.uint64)
+        names = np.frombuffer(b"".join(labels) or b"\0", np.uint8)
+        self._check(self.lib.mlst_alignments_text_open(self._h, _ptr(names), _ptr(name_off), int(bool(paired)), int(round_bytes)), "mlst_alignments_text_open")
+        try:
+            buf = None
+            nb, nr, done = C.c_uint64(), C.c_uint64(), C.c_int()
+            while True:
+                # the size of the round that comes next, then the round itself
+                self._check(self.lib.mlst_alignments_text_next(self._h, None, 0, C.byref(nb), C.byref(nr), C.byref(done)), "mlst_alignments_text_next")
+                if done.value:
+                    break
+                need = int(nb.value)
+                if buf is None or len(buf) < need:
+                    buf = pinned_array(max(need, 1 << 16))
+                self._check(self.lib.mlst_alignments_text_next(self._h, _ptr(buf), len(buf), C.byref(nb), C.byref(nr), C.byref(done)), "mlst_alignments_text_next")
+                if nb.value:      # (a round whose reads have no record gives no text)
+                    yield buf[:int(nb.value)].tobytes()
+                if done.value:
+                    break
+        finally:
+            self.lib.mlst_alignments_text_close(self._h)
 
     # ---- typing tail on the device ----
     def typing_enqueue(self, penalty: int = 100, mincov: int = 1, none_char: str = "N"):

@@ -1,4 +1,4 @@
-"""The engine's alignments to the chosen alleles as SAM text (`cli type --write-sam`).
+"""The engine's alignments as SAM text (`cli type --write-sam` / `--write-sam-all`).
 
 The reference leaves a BAM of each sample's reads on the MLST loci behind (the bowtie2 run in front of metamlst.py); here the
 alignments are the engine's own, exported as records by Engine.export_alignments (mlst_alignments_export, include/mlst.h) and
@@ -21,7 +21,27 @@ formatted on the host by `write_sam(path, idx, chosen, aln, paired)`:
     columns whose SEQ letter is not the allele's, an N on either side included) are computed here from the CIGAR and the
     allele text.
 
-Not written: BAM / BGZF, real read names, alignments to alleles that were not chosen, MD:Z."""
+EVERY alignment of the sample (`cli type --write-sam-all`, `write_sam_all(path, idx, eng, paired)`): what `bowtie2 -a` leaves in
+front of metamlst.py, with the records formatted on the device (Engine.export_sam_text: mlst_alignments_text_open / _next / _close,
+csrc/aln_text.h) and only the header written here.  The rule, which `format_record` and `all_records_rule` below state in plain
+Python (they are the specification and the tests' yardstick; the command never calls them):
+
+  * records: one for every (work item, allele of the item's locus) whose alignment, decided exactly as pass 1 decides that pair
+    (the ungapped one, or the banded one where the gap trigger fires: align_pair of the oracle), has score >= the floor of the
+    read's length and score > 0 -- the records pass 1 counts in MLST_CNT_TOTAL_RECORDS.  Records that fail the AS / XM tag filter
+    are written too; mlst_set_depth_cap is ignored;
+  * header: `@HD VN:1.6 SO:unsorted GO:query`, one `@SQ SN:<label> LN:<len>` for EVERY loaded allele in index order (what bowtie2
+    writes and mlst_sam_open needs), the `@PG` line;
+  * order: work items by (read index, locus index, strand, diag), inside an item the alleles ascending.  All records of a read are
+    consecutive, two loci first seen in the same read keep locus order, and the bytes depend neither on the order of the item list
+    nor on the size of the rounds the text leaves the device in;
+  * columns 1-11 as above (QNAME r<k>, MAPQ 255, * 0 0, SEQ on the reference strand, QUAL chr(min(q, 93) + 33)); FLAG 16 * strand,
+    plus 256 on every record of a read index except its best one: the highest AS, ties to the first in file order;
+  * optional fields `AS:i [XS:i] XN:i:0 XM:i XO:i XG:i NM:i YT:Z:UU`.  XS:i is there iff the read index has two records or more in
+    the file, and is the highest AS among the read's OTHER records.  A read with one record has no XS field, so XO stands in the
+    15th column: Q1 by construction, as with bowtie2.  AS and XM are the true values; XO, XG and NM are `gap_figures` of the record.
+
+Not written: BAM / BGZF, real read names, MD:Z."""
 from __future__ import annotations
 
 import numpy as np
@@ -91,4 +111,57 @@ def write_sam(path: str, idx: AlleleIndex, chosen, aln, paired: bool) -> int:
                 ridx >> 1 if paired else ridx, 16 * strand + (0 if best[k] else 256), idx.label(a), int(aln.pos0[k]) + 1,
                 "".join("%d%s" % (int(o) >> 4, CIGAR_OPS[int(o) & 15]) for o in ops), seq.decode("ascii"), qual_all[s0:s1].decode("ascii"),
                 int(aln.as_[k]), int(aln.as_[k]), int(aln.xm[k]), xo, xg, nm))
+    return n
+
+
+# ------------------------------------------------------------------ every alignment (--write-sam-all)
+def sam_all_header(idx: AlleleIndex) -> str:
+    """the header of the full export: every loaded allele, in index order"""
+    sq = "".join("@SQ\tSN:%s\tLN:%d\n" % (idx.label(a), int(idx.off[a + 1] - idx.off[a])) for a in range(idx.n_alleles))
+    return "@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + sq + PG_LINE + "\n"
+
+
+def format_record(idx: AlleleIndex, rec, paired: bool, secondary: bool, xs) -> bytes:
+    """One line of the full export.  rec = (read index, strand, diag, locus, allele, pos0, AS, XM, CIGAR ops (len << 4 | op), SEQ
+    (ASCII, reference strand), QUAL (raw Phred)); secondary: not the best record of its read index; xs: the highest AS among the
+    read's other records, None when it has no other record (no XS:i field then)."""
+    ridx, strand, _diag, _locus, a, pos0, as_, xm, ops, seq, qual = rec
+    xo, xg, nm = gap_figures(ops, bytes(seq), idx.sequence(int(a)), int(pos0))
+    cols = ["r%d" % (int(ridx) >> 1 if paired else int(ridx)), "%d" % (16 * int(strand) + (256 if secondary else 0)), idx.label(int(a)), "%d" % (int(pos0) + 1), "255",
+            "".join("%d%s" % (int(o) >> 4, CIGAR_OPS[int(o) & 15]) for o in ops), "*", "0", "0", bytes(seq).decode("ascii"),
+            "".join(chr(min(int(q), 93) + 33) for q in bytes(qual)), "AS:i:%d" % int(as_)]
+    if xs is not None:
+        cols.append("XS:i:%d" % int(xs))
+    cols += ["XN:i:0", "XM:i:%d" % int(xm), "XO:i:%d" % xo, "XG:i:%d" % xg, "NM:i:%d" % nm, "YT:Z:UU"]
+    return ("\t".join(cols) + "\n").encode("ascii")
+
+
+def all_records_rule(idx: AlleleIndex, recs, paired: bool) -> list:
+    """The lines of the full export for a sample's records (tuples as format_record takes them, in any order): sorted by (read
+    index, locus, strand, diag, allele); per read index the best record (highest AS, ties to the first in that order) is the one
+    without 256, and XS is the highest AS among the others."""
+    order = sorted(recs, key=lambda r: (int(r[0]), int(r[3]), int(r[1]), int(r[2]), int(r[4])))
+    out, k = [], 0
+    while k < len(order):
+        e = k
+        while e < len(order) and int(order[e][0]) == int(order[k][0]):
+            e += 1
+        scores = [int(r[6]) for r in order[k:e]]
+        best = scores.index(max(scores))
+        for t, r in enumerate(order[k:e]):
+            others = scores[:t] + scores[t + 1:]
+            out.append(format_record(idx, r, paired, t != best, max(others) if others else None))
+        k = e
+    return out
+
+
+def write_sam_all(path: str, idx: AlleleIndex, eng, paired: bool, round_bytes: int = 0) -> int:
+    """Write every alignment of the sample on `eng` to `path`: the header here, the records as the device formats them, round by
+    round.  Returns the number of records written."""
+    n = 0
+    with open(path, "wb") as f:
+        f.write(sam_all_header(idx).encode("ascii"))
+        for chunk in eng.export_sam_text(idx, paired=paired, round_bytes=round_bytes):
+            f.write(chunk)
+            n += chunk.count(b"\n")
     return n
