@@ -372,7 +372,8 @@ int mlst_alignments_fetch(mlst_handle* h, uint64_t* read_index, uint32_t* rec_al
  * Header: the caller's (metamlst_amd/samout.py: @HD VN:1.6 SO:unsorted GO:query, one @SQ per loaded allele in index order, @PG).
  * Order: work items by (read index, locus index, strand, diag), inside an item the alleles ascending: all records of a read are
  *   consecutive.  The bytes depend neither on the order of the item list nor on round_bytes.
- * Columns: QNAME r<k>, k = the read index (read index >> 1 with paired != 0); FLAG 16 * strand, plus 256 on every record of a read
+ * Columns: QNAME r<k>, k = the read index (read index >> 1 with paired != 0), or the read's own name with mlst_set_read_names
+ *   (below); FLAG 16 * strand, plus 256 on every record of a read
  *   index except its best one (the highest AS, ties to the first in file order); RNAME the allele's label; POS = the leftmost aligned
  *   column + 1; MAPQ 255; CIGAR as mlst_alignments_fetch describes it; * 0 0; SEQ on the reference strand; QUAL chr(min(q, 93) + 33);
  *   AS:i [XS:i] XN:i:0 XM:i XO:i XG:i NM:i YT:Z:UU.  XS:i is present iff the read index has two records or more, and is the
@@ -394,6 +395,34 @@ int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, const uint64
                               uint64_t round_bytes /* 0: 256 MiB */);
 int mlst_alignments_text_next(mlst_handle* h, uint8_t* text, uint64_t cap, uint64_t* n_bytes, uint64_t* n_records, int* done);
 int mlst_alignments_text_close(mlst_handle* h);
+
+/* ---- the reads' own names as QNAME (off by default; csrc/read_names.h; `cli type --read-names`) ---------------------------------------
+ * mlst_set_read_names(h, 1): the name of every read pass 1 retains is copied out of the FASTQ text on the device, before the text
+ *   slot of its chunk is reused; mlst_alignments_text_* then writes that name as QNAME and mlst_read_names_fetch hands the names to the
+ *   host (metamlst_amd.samout.write_sam).  With the switch off nothing is queued and nothing is allocated.
+ * The rule (metamlst_amd.samout.read_qname states it in Python): the name is the header line's bytes behind the '@' up to, not
+ *   including, the first space, TAB, CR or LF (bowtie2's rule).  A name that is no legal SAM QNAME ([!-?A-~]{1,254}: empty, longer than
+ *   254 bytes, a '@' or a byte outside '!'..'~' in it) is not kept: the read's QNAME stays r<k> as without the switch, and the read is
+ *   counted as a fallback.  Every read carries its own name, mates included (paired != 0 changes the k of a fallback only).
+ * Entries that carry names: mlst_submit_fastq, mlst_submit_fastq_stream, mlst_submit_fastq_pair, mlst_submit_fastq_bgzf and
+ *   mlst_submit_fastq_bgzf_pair.  With the switch on every other way of adding reads (mlst_submit_reads, mlst_submit_reads_device,
+ *   mlst_submit_packed_device, mlst_submit_packed_host, mlst_submit_fasta, mlst_bam_reads_open) and mlst_set_read_tiling with a tile
+ *   are refused with MLST_E_INVALID ("read names are on ..."), as is mlst_set_read_names(h, 1) behind mlst_set_read_tiling.
+ * The switch may change only while the sample holds no reads (before the first submission or behind mlst_reset_sample; a non-zero
+ *   mlst_set_read_index_base counts as reads: set the switch first) and no stream is open: MLST_E_INVALID otherwise.
+ *   mlst_reset_sample empties the arena and keeps the switch.
+ * Memory: the bytes of the kept names in an arena of MLST_NAMES_BYTES bytes (environment, read by mlst_create; default 256 MiB),
+ *   offset and length per retained slot; allocated by the first submission under the switch.  An arena that is too small loses no
+ *   statistics: the next entry that fetches statistics, names or the text export fails with MLST_E_LIMIT and names the bytes needed.
+ * mlst_read_names_info: out[0] = retained reads with a kept name, out[1] = bytes of the kept names, out[2] = fallbacks (retained
+ *   reads whose name was not kept), out[3] = the longest kept name in bytes.  All zero with the switch off.
+ * mlst_read_names_fetch: read_index[n], off[n + 1], bytes[out[1]] with n = out[0] of mlst_read_names_info: the name of read
+ *   read_index[i] is bytes[off[i] .. off[i + 1]).  The order is unspecified.  An open BGZF piece is finished first by both.
+ * The text export bounds a line with the longest kept name in place of the 21 bytes of r<k> where that is longer. */
+int mlst_set_read_names(mlst_handle* h, int on);
+int mlst_get_read_names(mlst_handle* h, int* on);
+int mlst_read_names_info(mlst_handle* h, uint64_t out[4]);
+int mlst_read_names_fetch(mlst_handle* h, uint64_t* read_index /* n */, uint64_t* off /* n+1 */, uint8_t* bytes);
 
 /* ---- ready-made alignments straight from a BGZF BAM (the reference's one input, metamlst.py:34) ------------------------------
  * The file is streamed twice, as the reference reads it twice (samtools view, then pysam): pass 1 is the hit accumulation of

@@ -6,6 +6,7 @@
     python -m metamlst_amd.cli type  HIFI.bam --long-bam-reads [--tile LEN,STEP] -d DB  (the same for the reads of an unaligned BAM)
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam -d DB      (also <out>/<sample>.sam: the alignments to the chosen alleles)
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam-all -d DB  (also <out>/<sample>.all.sam: every alignment, as bowtie2 -a would leave it)
+    python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam-all --read-names -d DB  (QNAME = the reads' own names, kept on the GPU)
     python -m metamlst_amd.cli merge FOLDER -d DB [-z 5] [--filter ...] [--meta ...] [--idField ...] [--aligner auto|gpu|muscle]   (metamlst-merge.py:35-49)
     python -m metamlst_amd.cli index -d DB [-s seqs.fasta,...] [-t typings.txt,...] [-q dump.fa] [--list]   (metamlst-index.py:24-33)
 
@@ -90,6 +91,13 @@ def _type_parser(sub):
                         "allele of its locus, what `bowtie2 -a` leaves in front of metamlst.py -- as SAM text formatted on the GPU "
                         "(metamlst_amd/samout.py: one @SQ per loaded allele, XS:i only where the read has a second record).  Accepted and "
                         "refused where --write-sam is; both may be given")
+    p.add_argument("--read-names", dest="read_names", action="store_true",
+                   help="with --write-sam / --write-sam-all: QNAME is the read's own name (the FASTQ header behind the @ up to the first "
+                        "white space, bowtie2's rule) instead of r<read index>; the names of the reads on the loci are copied out of the "
+                        "FASTQ text on the GPU.  A name that is no legal SAM QNAME keeps r<k>, and such reads are counted.  FASTQ input of "
+                        "one sample on one GPU (plain, .gz, bgzip, `a.fq,b.fq`, -2): it goes with none of a reads BAM, --contigs, "
+                        "--long-reads, --long-bam-reads, --alignments, a folder or several samples, and --gpus N.  The .nfo and the --log "
+                        "file do not change")
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -214,6 +222,18 @@ def run_type(a, argv=None) -> int:
         print("no %s file found in " % ("FASTA" if a.contigs else "FASTQ") + ", ".join(a.READS))
         return 1
     many = len(samples) > 1
+    if a.read_names:      # (refused before any GPU use, each with its reason)
+        for on, why in ((a.alignments, "with --alignments the file is the input, and its records carry their names already"),
+                        (many, "it names the reads of one sample's export: several samples or a folder are typed without exports"),
+                        (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "the exports take one GPU, so do the names (not --gpus N)"),
+                        (a.contigs, "--contigs cuts assemblies into windows, and a window has no name"),
+                        (a.long_reads, "--long-reads cuts reads into windows, and a window has no name"),
+                        (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and a window has no name"),
+                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the names of a reads BAM are not carried to the exports: FASTQ input only"),
+                        (not (a.write_sam or a.write_sam_all), "it names the reads of an export: give --write-sam or --write-sam-all")):
+            if on:
+                print("--read-names: " + why)
+                return 1
     for flag in [f for f, on in (("--write-sam", a.write_sam), ("--write-sam-all", a.write_sam_all)) if on]:      # (refused before any GPU use)
         if a.alignments:
             print(flag + " writes the engine's own alignments: with --alignments the file is the input")
@@ -273,6 +293,8 @@ def run_type(a, argv=None) -> int:
     eng.set_bgzf_verify(a.verify_crc)
     if long_reads or long_bam:
         eng.set_read_tiling(*(long_reads or long_bam))
+    if a.read_names:      # (FASTQ input only: text, host-inflated .gz and BGZF all reach the device as text, where the names are kept)
+        eng.set_read_names(True)
     # the built host index is kept next to the database (as the reference keeps <idx>.1.bt2: metamlst-index.py:224-225) unless a
     # species filter made this index a one-off or MLST_INDEX_CACHE=0
     ref_cache = (a.database + ".mlstref") if (not a.filter and os.environ.get("MLST_INDEX_CACHE", "1") != "0") else ""
@@ -383,10 +405,16 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
     eng.typing_enqueue(penalty=targs.penalty)
     st, chosen, letters = eng.typing_fetch()
     rc = _finish_type(a, idx, database, targs, st, None, typed=(chosen, letters))
+    names = None
+    if rc == 0 and getattr(a, "read_names", False):      # the engine knows its switch: the text export needs no more than that
+        names = eng.read_names()
+        info = eng.read_names_info()
+        if not a.quiet:
+            print("--read-names: %d reads on the loci keep their names, %d have a name that is no legal QNAME and keep r<k>" % (info["named"], info["fallbacks"]))
     if rc == 0 and a.write_sam:
         from .samout import write_sam
         alleles = [chosen[l] for l in sorted(chosen)]
-        write_sam(a.o + "/" + sample_name(a.READS) + ".sam", idx, alleles, eng.export_alignments(alleles), paired)
+        write_sam(a.o + "/" + sample_name(a.READS) + ".sam", idx, alleles, eng.export_alignments(alleles), paired, names=names)
     if rc == 0 and a.write_sam_all:
         from .samout import write_sam_all
         write_sam_all(a.o + "/" + sample_name(a.READS) + ".all.sam", idx, eng, paired)

@@ -17,6 +17,7 @@
 //                 that k_at_local / k_fqt_scan / k_fqt_add turn into the lines' offsets in the text.
 //   k_at_write    one wave per item: SEQ and QUAL rendered once into LDS; per pass of 64 alleles every lane formats the other columns
 //                 of its record (at_line<true>), then the wave copies SEQ and QUAL into each record, four bytes per lane and store.
+// QNAME: r<k>, or with mlst_set_read_names the read's own name out of the name arena (at_qname; csrc/read_names.h).
 //   k_at_dp<true> the banded alignment and the walk again for the listed pairs that have a record: the CIGAR text, written from its
 //                 last character down (the walk meets the runs last to first).
 // Plain vector stores only.
@@ -38,6 +39,7 @@ struct AtDev {          // device-resident descriptor of an export (uploaded by 
     GP<const u8> ascii; GP<const u64> aoff;          // the alleles' text
     GP<AtPair> meta; GP<AtRead> reads; GP<u64> wex; GP<u64> gsum; GP<u64> dp_list; GP<u64> dp_n; GP<u64> n_rec;
     int paired;
+    GP<const u8> rn_bytes; GP<const u64> rn_off; GP<const u16> rn_len;      // the retained reads' names (csrc/read_names.h); NULL: mlst_set_read_names is off
 };
 struct AtRound { u64 k0, k1, r0, r1, pb, n_pairs; };      // sorted positions, reads and first pair of a round
 
@@ -51,11 +53,11 @@ __host__ __device__ inline u32 at_digits64(u64 v) {
     return d;
 }
 // A bound from above on the bytes of one record's line for a read of n bases and RNAMEs of at most max_name bytes (the round planner).
-// Columns 1-5 and 7-9: r + 20 digits, FLAG 3, RNAME, POS 10, 255, *, 0, 0 and their TABs; CIGAR: a run holds a column at the least
+// Columns 1-5 and 7-9: QNAME max_qname (r + 20 digits, or the longest kept name where that is longer), FLAG 3, RNAME, POS 10, 255, *, 0, 0 and their TABs; CIGAR: a run holds a column at the least
 // and its text (digits + letter) is no longer than twice its columns, S / M / I runs hold n read bases together (2 n), and at most
 // n + 1 D runs of at most five digits stand between them (6 (n + 1)); SEQ and QUAL with their TABs 2 n + 2; six integer tags of at
 // most 17 bytes with their TABs, XN:i:0, YT:Z:UU and the LF.
-__host__ __device__ inline u64 at_line_bound(u32 n, u64 max_name) { return 10ull * n + max_name + 192ull; }
+__host__ __device__ inline u64 at_line_bound(u32 n, u64 max_name, u64 max_qname = 21) { return 10ull * n + max_name + 171ull + (max_qname > 21 ? max_qname : 21ull); }
 
 // The columns of a line, either counted (WRITE = false) or written.  SEQ, QUAL and a banded record's CIGAR are left out: their bytes are
 // counted and, when writing, skipped -- the wave and k_at_dp<true> write them.
@@ -76,20 +78,33 @@ template <bool WRITE> struct AtOut {
     __device__ inline void tag(char a, char b, u32 v) { ch('\t'); ch(a); ch(b); ch(':'); ch('i'); ch(':'); dec32(v); }
     __device__ inline void skip(u64 k) { n += k; }
 };
+// the QNAME of a retained read: its kept name (len bytes at p), or len = 0: r<k> (the switch is off, or the name is no legal QNAME)
+// NAMES = false is the export without the switch: no load, and at_head's branch folds away -- the kernels are the ones they were
+struct AtQn { GP<const u8>::G* p; u32 len; };
+template <bool NAMES>
+__device__ inline AtQn at_qname(const AtDev& D, u32 ret) {
+    AtQn q; q.p = nullptr; q.len = 0;
+    if (NAMES) { q.len = D.rn_len[ret]; q.p = D.rn_bytes.g() + D.rn_off[ret]; }
+    return q;
+}
 // bytes in front of the CIGAR column: QNAME, FLAG, RNAME, POS, MAPQ and their TABs
 template <bool WRITE>
-__device__ inline void at_head(AtOut<WRITE>& o, u64 qname, u32 flag, GP<const u8>::G* name, u32 name_len, int pos0) {
-    o.ch('r'); o.dec64(qname); o.ch('\t'); o.dec32(flag); o.ch('\t');
+__device__ inline void at_head(AtOut<WRITE>& o, u64 qname, AtQn qn, u32 flag, GP<const u8>::G* name, u32 name_len, int pos0) {
+    if (qn.len) {
+        if (WRITE) for (u32 i = 0; i < qn.len; i++) o.p[o.n + i] = qn.p[i];
+        o.n += qn.len;
+    } else { o.ch('r'); o.dec64(qname); }
+    o.ch('\t'); o.dec32(flag); o.ch('\t');
     if (WRITE) for (u32 i = 0; i < name_len; i++) o.p[o.n + i] = name[i];
     o.n += name_len;
     o.ch('\t'); o.dec32((u32)(pos0 + 1)); o.ch('\t'); o.ch('2'); o.ch('5'); o.ch('5'); o.ch('\t');
 }
 // the whole line; returns its bytes.  seq_at = where SEQ starts (QUAL starts n + 1 bytes behind it)
 template <bool WRITE>
-__device__ inline u64 at_line(u8* p, const AtPair& m, u64 qname, u32 flag, GP<const u8>::G* name, u32 name_len, int n, int bs,
+__device__ inline u64 at_line(u8* p, const AtPair& m, u64 qname, AtQn qn, u32 flag, GP<const u8>::G* name, u32 name_len, int n, int bs,
                               bool has_xs, int xs, u64& seq_at) {
     AtOut<WRITE> o; o.p = p; o.n = 0;
-    at_head<WRITE>(o, qname, flag, name, name_len, m.pos0);
+    at_head<WRITE>(o, qname, qn, flag, name, name_len, m.pos0);
     if (m.flags & AT_DP) o.skip(m.cigw);
     else {
         const int be = (int)m.be;
@@ -230,9 +245,10 @@ __device__ inline void at_walk(const u8* __restrict__ TB, int bi, int bb, int di
     if (!text) { cigw = w; nm = xg + mism; }
 }
 
+// NAMES: the reads carry their own names (at_qname); only the EMIT pass looks at them.
 // EMIT = false: the listed pairs' AtPair;  EMIT = true: the CIGAR text of those that have a record (text = the round's text, the
 // lines' offsets in D.wex).  64 workgroups of 64 lanes at the most: lane k of workgroup g owns slice 64 g + k of the traceback store.
-template <bool EMIT>
+template <bool EMIT, bool NAMES>
 __global__ __launch_bounds__(64) void k_at_dp(const EngineDev* __restrict__ Ep, KParams P, const AtDev* __restrict__ Dp, AtRound R,
                                               u8* __restrict__ tb_scratch, u8* __restrict__ text) {
     const EngineDev& E = *Ep;     // device-resident descriptor: fields are scalar-loaded on demand
@@ -264,7 +280,7 @@ __global__ __launch_bounds__(64) void k_at_dp(const EngineDev* __restrict__ Ep, 
             const u32 flag = (it.strand ? 16u : 0u) + (rd.best_pair == pi ? 0u : 256u);
             const u64 g = L.a_begin + a;
             AtOut<false> h; h.p = nullptr; h.n = 0;
-            at_head<false>(h, D.paired ? ridx >> 1 : ridx, flag, nullptr, (u32)(D.name_off[g + 1] - D.name_off[g]), o.pos0);
+            at_head<false>(h, D.paired ? ridx >> 1 : ridx, at_qname<NAMES>(D, it.ret), flag, nullptr, (u32)(D.name_off[g + 1] - D.name_off[g]), o.pos0);
             at_walk(TB, bi, bb, it.diag, P.band_w, n, rb, rq, it.strand, ref, text + D.wex[pi] + h.n, cigw, xo, xg, nm, pos0);
             continue;
         }
@@ -287,6 +303,7 @@ __device__ inline void at_xs_flag(const AtRead& rd, u64 pi, int strand, bool& ha
 }
 
 // One wave per read of the round: its pairs are consecutive (the items are sorted by read first).
+template <bool NAMES>
 __global__ __launch_bounds__(64) void k_at_reads(const EngineDev* __restrict__ Ep, const AtDev* __restrict__ Dp, AtRound R) {
     const EngineDev& E = *Ep;     // device-resident descriptor: fields are scalar-loaded on demand
     const AtDev& D = *Dp;
@@ -320,6 +337,7 @@ __global__ __launch_bounds__(64) void k_at_reads(const EngineDev* __restrict__ E
             const LocusDev L = E.loci[it.locus];
             const int n = (int)(E.ret_len[it.ret] & 0x7FFFu);
             const u64 ridx = E.ret_ridx[it.ret];
+            const AtQn qn = at_qname<NAMES>(D, it.ret);
             const u64 p0 = D.pair_off[k] - R.pb;
             for (u32 a = (u32)lane; a < L.n_alleles; a += 64) {
                 const AtPair m = D.meta[p0 + a];
@@ -328,7 +346,7 @@ __global__ __launch_bounds__(64) void k_at_reads(const EngineDev* __restrict__ E
                     bool has_xs; int xs; u32 flag; u64 seq_at;
                     at_xs_flag(rd, p0 + a, it.strand, has_xs, xs, flag);
                     const u64 g = L.a_begin + a;
-                    len = at_line<false>(nullptr, m, D.paired ? ridx >> 1 : ridx, flag, nullptr, (u32)(D.name_off[g + 1] - D.name_off[g]), n, m.pos0 - it.diag, has_xs, xs, seq_at);
+                    len = at_line<false>(nullptr, m, D.paired ? ridx >> 1 : ridx, qn, flag, nullptr, (u32)(D.name_off[g + 1] - D.name_off[g]), n, m.pos0 - it.diag, has_xs, xs, seq_at);
                 }
                 D.wex[p0 + a] = len;
             }
@@ -366,6 +384,7 @@ __device__ __forceinline__ void at_copy(u8* __restrict__ dst, const u8* s_src, i
     if (lane < n - t0) dst[t0 + lane] = s_src[t0 + lane];
 }
 
+template <bool NAMES>
 __global__ __launch_bounds__(64) void k_at_write(const EngineDev* __restrict__ Ep, const AtDev* __restrict__ Dp, AtRound R, u8* __restrict__ text) {
     const EngineDev& E = *Ep;     // device-resident descriptor: fields are scalar-loaded on demand
     const AtDev& D = *Dp;
@@ -376,6 +395,7 @@ __global__ __launch_bounds__(64) void k_at_write(const EngineDev* __restrict__ E
         const LocusDev L = E.loci[it.locus];
         const int n = (int)(E.ret_len[it.ret] & 0x7FFFu);
         const u64 ridx = E.ret_ridx[it.ret];
+        const AtQn qn = at_qname<NAMES>(D, it.ret);
         const AtRead rd = D.reads[D.item_read[k] - R.r0];
         const u64 p0 = D.pair_off[k] - R.pb;
         __syncthreads();      // the rows of the item before are no longer read
@@ -394,7 +414,7 @@ __global__ __launch_bounds__(64) void k_at_write(const EngineDev* __restrict__ E
                     bool has_xs; int xs; u32 flag;
                     at_xs_flag(rd, p0 + a, it.strand, has_xs, xs, flag);
                     const u64 g = L.a_begin + a; const u64 n0 = D.name_off[g];
-                    at_line<true>(text + at, m, D.paired ? ridx >> 1 : ridx, flag, D.names.g() + n0, (u32)(D.name_off[g + 1] - n0), n, m.pos0 - it.diag, has_xs, xs, seq_at);
+                    at_line<true>(text + at, m, D.paired ? ridx >> 1 : ridx, qn, flag, D.names.g() + n0, (u32)(D.name_off[g + 1] - n0), n, m.pos0 - it.diag, has_xs, xs, seq_at);
                 }
             }
             u64 rm = __ballot(rec);

@@ -3686,6 +3686,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "bam_tile.h"
 #include "msa_dev.h"
 #include "aln_export.h"
+#include "read_names.h"
 #include "aln_text.h"
 
 // ================================================================== host side
@@ -3826,10 +3827,15 @@ struct mlst_handle {
     // every alignment as SAM text (mlst_alignments_text_open / _next / _close; csrc/aln_text.h): no part of a sample's state.  Per export:
     // the sorted item list (perm, pair_off, item_read, read_first), the RNAME labels and the rounds; per round (sized by the largest
     // one): AtPair and line offset per pair, the list of the banded SW, AtRead per read, the workgroups' sums; d_text = the round's text.
-    struct AtState { bool open = false, ready = false; size_t next = 0; std::vector<AtRound> rounds; u64 round_bytes = 0, round_recs = 0, max_pairs = 0;
+    struct AtState { bool open = false, ready = false, with_names = false; size_t next = 0; std::vector<AtRound> rounds; u64 round_bytes = 0, round_recs = 0, max_pairs = 0;
              u32* d_perm = nullptr; u64* d_pair_off = nullptr; u32* d_item_read = nullptr; u64* d_read_first = nullptr; u8* d_names = nullptr; u64* d_name_off = nullptr;
              AtPair* d_meta = nullptr; AtRead* d_reads = nullptr; u64* d_wex = nullptr; u64* d_gsum = nullptr; u64* d_dp = nullptr; u8* d_desc = nullptr;
              u8* d_text = nullptr; u64 cap_text = 0; u8* h_tot = nullptr; } at;
+    // the retained reads' names (mlst_set_read_names; csrc/read_names.h), next to the retained-read store: the switch, the counters on the
+    // device, the byte arena (MLST_NAMES_BYTES, read by mlst_create) and offset / length per retained slot -- allocated by the first
+    // submission under the switch; src: where the header lines of the chunk being submitted start (set by the FASTQ parsers)
+    struct { bool on = false; u64 want_bytes = 256ull << 20; RnCtr* d_ctr = nullptr; u8* d_bytes = nullptr; u64 cap_bytes = 0; u64* d_off = nullptr; u16* d_len = nullptr;
+             RnSrc src = {nullptr, nullptr, 0}; } rn;
 };
 
 static std::string g_create_err;
@@ -3847,6 +3853,7 @@ static void bz_free(mlst_handle* h);
 static int bam_flush(mlst_handle* h);     // BAM input: the piece in flight is finished (its errors are this call's)
 static void bam_drop(mlst_handle* h, bool release);      // the BAM stream is closed and forgotten (release: its buffers too)
 static bool bam_is_open(const mlst_handle* h);
+static int rn_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_names is on: an entry that carries no names is refused
 static void at_free(mlst_handle* h);      // the per-export tables of mlst_alignments_text_*
 static const char* bam_kind(const mlst_handle* h);      // "BAM" or "SAM": what the open stream of ready-made alignments takes
 template <typename T> static hipError_t dmalloc(T** p, u64 n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
@@ -3948,6 +3955,7 @@ extern "C" int mlst_create(int device, const mlst_params* p, mlst_handle** out) 
     { const char* g = getenv("MLST_BGZF_CRC"); h->bgzf_verify = g && g[0] == '1'; }      // initial value of mlst_set_bgzf_verify
     { const char* g = getenv("MLST_MSA_BATCH_BYTES"); if (g && atoll(g) > 0) h->msa.batch_bytes = (u64)atoll(g); }      // traceback store of one batch of mlst_msa_align (floor: one pair)
     { const char* g = getenv("MLST_TILE_ROUND"); if (g && atoll(g) > 0) h->tile.round = (u64)atoll(g); }      // windows per round of a tiled FASTQ chunk: a memory bound
+    { const char* g = getenv("MLST_NAMES_BYTES"); if (g && atoll(g) > 0) h->rn.want_bytes = (u64)atoll(g); }      // the byte arena of mlst_set_read_names
     { int khz = 0; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) h->wall_khz = (double)khz; }
     KParams& k = h->kp;
     k.minscore = prm.minscore; k.max_xm = prm.max_xm; k.min_read_len = prm.min_read_len; k.minqual = prm.minqual;
@@ -3989,6 +3997,8 @@ static void free_state(mlst_handle* h) {
     hipFree(E.items); hipFree(E.item_state); hipFree(E.res); hipFree(E.dp_list);
     for (int k = 0; k < 2; k++) { hipFree(h->d_xrec[k]); h->d_xrec[k] = nullptr; h->cap_xrec[k] = 0; }
     hipFree(h->d_acc64); h->d_acc64 = nullptr;
+    hipFree(h->rn.d_ctr); hipFree(h->rn.d_bytes); hipFree(h->rn.d_off); hipFree(h->rn.d_len);      // (sized by cap_ret: the next first use allocates them again)
+    h->rn.d_ctr = nullptr; h->rn.d_bytes = nullptr; h->rn.d_off = nullptr; h->rn.d_len = nullptr; h->rn.cap_bytes = 0;
     hipFree(h->d_qc); h->d_qc = nullptr; h->cap_qc = 0; if (h->h_qc) { hipHostFree(h->h_qc); h->h_qc = nullptr; h->cap_hostq = 0; }
     hipFree(h->d_locus_chosen); hipFree(h->d_locus_colbase); hipFree(h->d_pl_list); hipFree(h->d_tb);
     hipFree(h->d_capbuf); h->d_capbuf = nullptr; h->cap_capcols = 0;
@@ -4039,6 +4049,7 @@ static int reset_sample_state(mlst_handle* h) {
     HIPCHK(h, hipMemsetAsync(h->d_stats, 0, h->stats_zero_bytes, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_stats + h->off_first, 0xFF, h->stats_bytes - h->off_first, h->stream));
     if (h->d_acc64 && h->n_alleles) HIPCHK(h, hipMemsetAsync(h->d_acc64, 0, (u64)h->n_alleles * 8, h->stream));      // (zero after every complete submission already: k_accumulate; this is for one that was cut short)
+    if (h->rn.d_ctr) HIPCHK(h, hipMemsetAsync(h->rn.d_ctr, 0, sizeof(RnCtr), h->stream));      // the name arena is empty; the switch stays
     h->reads_seen = 0; h->fq_carry_len = 0; h->max_wpr = 0;
     h->last_pack.n_reads = 0; h->last_pack.wpr = h->last_pack.qstride = 0;
     for (u64& x : h->tile.info) x = 0;
@@ -4651,6 +4662,7 @@ static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* 
                        uint64_t n_reads, uint32_t wpr, uint32_t qstride, int paired, int phase);
 extern "C" int mlst_submit_packed_device(mlst_handle* h, const uint32_t* d_packed, const uint8_t* d_qrows, const uint16_t* d_lens,
                                          uint64_t n_reads, uint32_t wpr, uint32_t qstride, int paired) {
+    { int rc_ = rn_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     return submit_impl(h, d_packed, d_qrows, d_lens, n_reads, wpr, qstride, paired, 0);
 }
 static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* d_qrows, const uint16_t* d_lens,
@@ -4797,6 +4809,7 @@ static int h2d_overlapped(mlst_handle* h, void* d_dst, const void* src, u64 n, h
 extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, const uint8_t* d_quals, const uint64_t* d_off,
                                         uint64_t n_reads, uint32_t max_len, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    { int rc_ = rn_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     hipSetDevice(h->device);
@@ -4812,6 +4825,7 @@ extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, 
 extern "C" int mlst_submit_reads(mlst_handle* h, const uint8_t* bases, const uint8_t* quals, const uint64_t* off,
                                  uint64_t n_reads, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    { int rc_ = rn_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (n_reads == 0) return MLST_OK;
@@ -4849,6 +4863,29 @@ static int next_text_slot(mlst_handle* h, u64 bytes) {
 }
 
 static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, int paired, uint64_t* n_reads_out);
+// mlst_set_read_names: the name arena, allocated by the first submission under the switch (csrc/read_names.h)
+static int rn_ensure(mlst_handle* h) {
+    auto& N = h->rn;
+    if (N.d_ctr) return MLST_OK;
+    HIPCHK(h, dmalloc(&N.d_ctr, (u64)1)); HIPCHK(h, dmalloc(&N.d_bytes, N.want_bytes)); N.cap_bytes = N.want_bytes;
+    HIPCHK(h, dmalloc(&N.d_off, h->E.cap_ret)); HIPCHK(h, dmalloc(&N.d_len, h->E.cap_ret));
+    HIPCHK(h, hipMemsetAsync(N.d_ctr, 0, sizeof(RnCtr), h->stream));
+    return MLST_OK;
+}
+// with the switch on, reads come from FASTQ text only: every other way of adding reads is refused
+static int rn_refuse(mlst_handle* h, const char* entry) {
+    if (h && h->rn.on) return fail(h, MLST_E_INVALID, "%s: read names are on (mlst_set_read_names) and only the FASTQ text and BGZF entries carry names", entry);
+    return MLST_OK;
+}
+// the counters of the name arena; an arena that was too small is reported here (the next entry that looks)
+static int rn_fetch(mlst_handle* h, RnCtr* c) {
+    memset(c, 0, sizeof *c);
+    if (!h->rn.d_ctr) return MLST_OK;
+    HIPCHK(h, hipMemcpyAsync(c, h->rn.d_ctr, sizeof *c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (c->err) return fail(h, MLST_E_LIMIT, "the read names need %llu bytes and the arena holds %llu: raise MLST_NAMES_BYTES", (unsigned long long)c->bytes, (unsigned long long)h->rn.cap_bytes);
+    return MLST_OK;
+}
 static int fq_tile_submit(mlst_handle* h, u64 n_bytes, u64 n_lines, u64 n_recs, int tslot, uint64_t* n_reads_out);
 // FASTQ text in h->d_fq_text[0 .. n_bytes) -> packed reads -> pass 1.  whole: the text consists of whole records; else
 // the partial record at its end is kept (h->d_fq_carry) for the next chunk.
@@ -4921,6 +4958,7 @@ static int fastq_pipeline(mlst_handle* h, u64 n_bytes, int paired, bool whole, u
     }
     if (flags[1] & 2) return fail(h, MLST_E_LIMIT, "a FASTQ read is longer than %d bases", MLST_MAX_READ_LEN);
     if (flags[1] & 1) return fail(h, MLST_E_INVALID, "malformed FASTQ: a record does not start with '@' or its sequence and quality lengths differ");
+    h->rn.src.lines1 = h->d_fq_lines; h->rn.src.lines2 = nullptr; h->rn.src.pair_k = pair_k;
     return fq_pack_submit(h, n_reads, flags[0], tslot, paired, n_reads_out);
 }
 // the tail of a FASTQ parse: k_fq_records (or k_fq_pair_records) wrote n_reads lengths into d_lens, the longest is max_len;
@@ -4942,10 +4980,24 @@ static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, i
     hipLaunchKernelGGL(k_pack_text, dim3(grid_for((n_reads + 63) / 64, 1, 8192)), dim3(256), 0, h->stream, h->d_fq_text, h->d_fq_soff, h->d_fq_qoff,
                        h->d_lens, n_reads, h->d_packed, h->d_qrows, wpr, qstride);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
+    if (!h->rn.on) HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
     if (n_reads_out) *n_reads_out = n_reads;
     h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
-    return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired);
+    if (!h->rn.on) return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired);
+    // mlst_set_read_names: the text outlives pass 1 of its chunk -- the names of the reads it retained are copied out of the header
+    // lines (csrc/read_names.h), behind the submission and outside its captured graph, and only then is the slot released
+    const u64 read_base = h->reads_seen;
+    rc = rn_ensure(h);
+    if (!rc) rc = submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);
+    if (!rc) {
+        hipLaunchKernelGGL(k_rn_gather, dim3(64), dim3(256), 0, h->stream, (const EngineDev*)h->d_E, (const u8*)h->d_fq_text, h->rn.src, read_base, n_reads,
+                           h->rn.d_ctr, h->rn.d_bytes, h->rn.cap_bytes, h->rn.d_off, h->rn.d_len);
+        hipLaunchKernelGGL(k_rn_advance, dim3(1), dim3(1), 0, h->stream, (const EngineDev*)h->d_E, h->rn.d_ctr);
+    }
+    const hipError_t le = hipGetLastError(), re = hipEventRecord(h->ev_packed[tslot], h->stream);      // (released on every way out)
+    if (rc) return rc;
+    HIPCHK(h, le); HIPCHK(h, re);
+    return MLST_OK;
 }
 
 // the tail of a FASTQ parse whose chunk holds a record longer than the tile (mlst_set_read_tiling; kernels: csrc/fastq_tile.h): windows
@@ -5085,6 +5137,7 @@ extern "C" int mlst_pack_fastq_host(const uint8_t* text, uint64_t n_bytes, uint3
 extern "C" int mlst_submit_packed_host(mlst_handle* h, const uint32_t* packed, const uint8_t* qrows, const uint16_t* lens, uint64_t n_reads,
                                        uint32_t wpr, uint32_t qstride, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    { int rc_ = rn_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (!packed || !qrows || !lens) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -5606,6 +5659,7 @@ static int bzp_finish_impl(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
         h->pc_len[r] = c;
     }
     if (!k) { HIPCHK(h, hipEventRecord(h->ev_packed[P.tslot], h->stream)); return MLST_OK; }
+    h->rn.src.lines1 = lines1; h->rn.src.lines2 = lines2; h->rn.src.pair_k = 0;
     return fq_pack_submit(h, 2 * k, flags[0], P.tslot, 1, n_reads_out);
 }
 static int bzp_finish(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
@@ -6410,6 +6464,7 @@ static int bamr_tile_submit(mlst_handle* h, BamSlot& S, const u32* rd_rec, const
 
 extern "C" int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip_bytes, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    { int rc_ = rn_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6453,6 +6508,7 @@ extern "C" int mlst_bam_reads_info(mlst_handle* h, uint64_t out[4]) {
 extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n_bytes, uint32_t read_len, uint32_t stride, uint32_t min_len,
                                  uint64_t* n_contigs_out, uint64_t* n_reads_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    { int rc_ = rn_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6622,6 +6678,7 @@ extern "C" int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t 
     if (!h) return MLST_E_INVALID;
     if ((read_len == 0) != (stride == 0)) return fail(h, MLST_E_INVALID, "read_len and stride must both be positive (or both 0: no tiling)");
     if (read_len > (u32)MLST_MAX_READ_LEN) return fail(h, MLST_E_LIMIT, "read_len %u exceeds %d bases", read_len, MLST_MAX_READ_LEN);
+    if (read_len) { int rc_ = rn_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window has no name)
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
     // (a reads stream took its tile when it was opened: include/mlst.h gives one message for every stream of reads)
     if (bam_is_open(h) && h->bam->reads) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (the reads stream of a BAM: its last chunk was not marked final)");
@@ -6638,6 +6695,52 @@ extern "C" int mlst_get_read_tiling_info(mlst_handle* h, uint64_t out[4]) {
     if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
     { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
     for (int k = 0; k < 4; k++) out[k] = h->tile.info[k];
+    return MLST_OK;
+}
+
+// the retained reads' names (include/mlst.h; csrc/read_names.h): the switch may change only while the sample holds no reads and no stream
+// is open -- a read submitted without the switch has no name to give
+extern "C" int mlst_set_read_names(mlst_handle* h, int on) {
+    if (!h) return MLST_E_INVALID;
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
+    if ((on != 0) != h->rn.on && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_names changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
+    if (on && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_tiling is on: a window has no name");
+    h->rn.on = on != 0;
+    return MLST_OK;
+}
+extern "C" int mlst_get_read_names(mlst_handle* h, int* on) {
+    if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
+    *on = h->rn.on ? 1 : 0;
+    return MLST_OK;
+}
+extern "C" int mlst_read_names_info(mlst_handle* h, uint64_t out[4]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
+    RnCtr c; { int rc_ = rn_fetch(h, &c); if (rc_) return rc_; }
+    out[0] = c.done - c.fallbacks; out[1] = c.bytes; out[2] = c.fallbacks; out[3] = c.longest;
+    return MLST_OK;
+}
+extern "C" int mlst_read_names_fetch(mlst_handle* h, uint64_t* read_index, uint64_t* off, uint8_t* bytes) {
+    if (!h || !read_index || !off || !bytes) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    RnCtr c; { int rc_ = rn_fetch(h, &c); if (rc_) return rc_; }
+    off[0] = 0;
+    if (!c.done) return MLST_OK;
+    std::vector<u64> ridx(c.done), noff(c.done); std::vector<u16> nlen(c.done); std::vector<u8> arena(c.bytes ? c.bytes : 1);
+    HIPCHK(h, hipMemcpyAsync(ridx.data(), h->E.ret_ridx, c.done * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(noff.data(), h->rn.d_off, c.done * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(nlen.data(), h->rn.d_len, c.done * 2, hipMemcpyDeviceToHost, h->stream));
+    if (c.bytes) HIPCHK(h, hipMemcpyAsync(arena.data(), h->rn.d_bytes, c.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    u64 n = 0, at = 0;
+    for (u64 s = 0; s < c.done; s++) {      // the slots with a name, in slot order
+        if (!nlen[s]) continue;
+        if (noff[s] + nlen[s] > c.bytes) return fail(h, MLST_E_HIP, "name arena inconsistent at slot %llu", (unsigned long long)s);
+        read_index[n] = ridx[s]; memcpy(bytes + at, arena.data() + noff[s], nlen[s]); at += nlen[s]; off[++n] = at;
+    }
     return MLST_OK;
 }
 
@@ -6666,6 +6769,7 @@ static int fetch_stats(mlst_handle* h, Counters** c_out) {
     if (c->err) return fail(h, MLST_E_CAPACITY, "capacity exceeded (flags 0x%llx: 1=retained reads %llu/%llu, 2=items %llu/%llu, 4=pair results %llu/%llu, 8=banded-SW list); raise mlst_params.max_*",
                             (unsigned long long)c->err, (unsigned long long)c->n_ret, (unsigned long long)h->E.cap_ret, (unsigned long long)c->n_items, (unsigned long long)h->E.cap_items,
                             (unsigned long long)c->n_res, (unsigned long long)h->E.cap_res);
+    if (h->rn.on) { RnCtr rnc; int rc_ = rn_fetch(h, &rnc); if (rc_) return rc_; }      // (a name arena that was too small)
     return MLST_OK;
 }
 static int check_overflow(mlst_handle* h) { return fetch_stats(h, nullptr); }
@@ -7038,6 +7142,9 @@ extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, c
         max_name = std::max<u64>(max_name, name_off[a + 1] - name_off[a]);
     }
     if (!round_bytes) round_bytes = 256ull << 20;
+    RnCtr rnc; { int rc_ = rn_fetch(h, &rnc); if (rc_) return rc_; }      // mlst_set_read_names: the longest kept name bounds the QNAME column
+    const bool with_names = h->rn.on && h->rn.d_ctr;
+    const u64 max_qname = with_names ? rnc.longest : 0;
     std::vector<u32> nall(nl ? nl : 1, 0);
     for (u64 a = 0; a < na; a++) nall[h->allele_locus[a]]++;
     for (u64 l = 0; l < nl; l++) if (nall[l] >= (1u << 20)) return fail(h, MLST_E_LIMIT, "locus %llu has %u alleles: the export takes fewer than 2^20", (unsigned long long)l, nall[l]);
@@ -7072,7 +7179,7 @@ extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, c
         if (k == 0 || ridx[it.ret] != ridx[items[perm[k - 1]].ret]) { read_first.push_back(k); read_bound.push_back(0); }
         item_read[k] = (u32)(read_first.size() - 1);
         pair_off[k + 1] = pair_off[k] + nall[it.locus];
-        read_bound.back() += (u64)nall[it.locus] * at_line_bound((u32)(rlen[it.ret] & 0x7FFFu), max_name);
+        read_bound.back() += (u64)nall[it.locus] * at_line_bound((u32)(rlen[it.ret] & 0x7FFFu), max_name, max_qname);
     }
     const u64 nr = read_first.size();
     read_first.push_back(ni);
@@ -7108,13 +7215,14 @@ extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, c
     D.perm = T.d_perm; D.pair_off = T.d_pair_off; D.item_read = T.d_item_read; D.read_first = T.d_read_first; D.names = T.d_names; D.name_off = T.d_name_off;
     D.ascii = h->d_ascii; D.aoff = h->d_aoff; D.meta = T.d_meta; D.reads = T.d_reads; D.wex = T.d_wex; D.gsum = T.d_gsum;
     D.dp_list = T.d_dp; D.dp_n = T.d_dp + max_pairs; D.n_rec = T.d_dp + max_pairs + 1; D.paired = paired ? 1 : 0;
+    if (with_names) { D.rn_bytes = h->rn.d_bytes; D.rn_off = h->rn.d_off; D.rn_len = h->rn.d_len; }
     FqtDev F; memset((void*)&F, 0, sizeof F);
     F.wex = T.d_wex; F.gsum = T.d_gsum; F.meta = (FqtMeta*)(T.d_desc + sizeof(AtDev) + sizeof(FqtDev));
     ATCHK(hipMemcpyAsync(T.d_desc, &D, sizeof D, hipMemcpyHostToDevice, h->stream));
     ATCHK(hipMemcpyAsync(T.d_desc + sizeof(AtDev), &F, sizeof F, hipMemcpyHostToDevice, h->stream));
     ATCHK(hipStreamSynchronize(h->stream));      // (the host vectors go out of scope)
 #undef ATCHK
-    T.rounds.swap(rounds); T.max_pairs = max_pairs; T.next = 0; T.ready = false; T.open = true;
+    T.rounds.swap(rounds); T.max_pairs = max_pairs; T.next = 0; T.ready = false; T.open = true; T.with_names = with_names;
     return MLST_OK;
 }
 // the kernels of round T.next up to the lines' offsets; leaves the round's bytes and records in T.round_bytes / T.round_recs
@@ -7130,8 +7238,9 @@ static int at_prepare(mlst_handle* h) {
     const unsigned gw = (unsigned)grid_for(R.k1 - R.k0, 1, 8192);      // one-wave workgroups, as k_pileup
     if (h->max_wpr <= 10) hipLaunchKernelGGL(k_at_decide_160, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
     else hipLaunchKernelGGL(k_at_decide_320, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
-    hipLaunchKernelGGL(k_at_dp<false>, dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, (u8*)nullptr);
-    hipLaunchKernelGGL(k_at_reads, dim3((unsigned)grid_for(R.r1 - R.r0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R);
+    hipLaunchKernelGGL((k_at_dp<false, false>), dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, (u8*)nullptr);
+    if (T.with_names) hipLaunchKernelGGL(k_at_reads<true>, dim3((unsigned)grid_for(R.r1 - R.r0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R);
+    else hipLaunchKernelGGL(k_at_reads<false>, dim3((unsigned)grid_for(R.r1 - R.r0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R);
     if (ng) {
         hipLaunchKernelGGL(k_at_local, dim3((unsigned)ng), dim3(1024), 0, h->stream, T.d_wex, R.n_pairs, T.d_gsum);
         hipLaunchKernelGGL(k_fqt_scan, dim3(1), dim3(1024), 0, h->stream, (const FqtDev*)d_F, ng);
@@ -7163,8 +7272,13 @@ extern "C" int mlst_alignments_text_next(mlst_handle* h, uint8_t* text, uint64_t
         const AtRound R = T.rounds[T.next];
         if (T.cap_text < T.round_bytes) { hipFree(T.d_text); T.d_text = nullptr; T.cap_text = 0; HIPCHK(h, dmalloc(&T.d_text, T.round_bytes)); T.cap_text = T.round_bytes; }
         const AtDev* d_D = (const AtDev*)T.d_desc;
-        hipLaunchKernelGGL(k_at_write, dim3((unsigned)grid_for(R.k1 - R.k0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R, T.d_text);
-        hipLaunchKernelGGL(k_at_dp<true>, dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, T.d_text);
+        if (T.with_names) {      // (the export without the switch runs the kernels it ran before the switch existed)
+            hipLaunchKernelGGL(k_at_write<true>, dim3((unsigned)grid_for(R.k1 - R.k0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R, T.d_text);
+            hipLaunchKernelGGL((k_at_dp<true, true>), dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, T.d_text);
+        } else {
+            hipLaunchKernelGGL(k_at_write<false>, dim3((unsigned)grid_for(R.k1 - R.k0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R, T.d_text);
+            hipLaunchKernelGGL((k_at_dp<true, false>), dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, T.d_text);
+        }
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemcpyAsync(text, T.d_text, T.round_bytes, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -166,6 +166,10 @@ def load_library(path: str | None = None):
         "mlst_set_read_tiling": (C.c_int, [H, C.c_uint32, C.c_uint32]),
         "mlst_get_read_tiling": (C.c_int, [H, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "mlst_get_read_tiling_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "mlst_set_read_names": (C.c_int, [H, C.c_int]),
+        "mlst_get_read_names": (C.c_int, [H, C.POINTER(C.c_int)]),
+        "mlst_read_names_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "mlst_read_names_fetch": (C.c_int, [H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)]),
         "mlst_submit_reads_device": (C.c_int, [H, u8p, u8p, u64p, C.c_uint64, C.c_uint32, C.c_int]),
         "mlst_pack_reads_device": (C.c_int, [H, u8p, u8p, u64p, C.c_uint64, u32p, u8p, u16p, C.c_uint32, C.c_uint32]),
         "mlst_submit_packed_device": (C.c_int, [H, u32p, u8p, u16p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int]),
@@ -783,6 +787,35 @@ class Engine:
         out = (C.c_uint64 * 4)()
         self._check(self.lib.mlst_get_read_tiling_info(self._h, out), "mlst_get_read_tiling_info")
         return {"records": int(out[0]), "cut": int(out[1]), "windows": int(out[2]), "longest": int(out[3])}
+
+    def set_read_names(self, on: bool = True) -> None:
+        """Keep the name of every retained read, copied out of the FASTQ text on the GPU (mlst_set_read_names; off by default; the
+        rule: samout.read_qname).  export_sam_text / write_sam_all then write it as QNAME, read_names() gives samout.write_sam its
+        map.  FASTQ text and BGZF entries only -- every other way of adding reads is refused while it is on; may change only while
+        the sample holds no reads and no stream is open.  reset_sample empties the names and keeps the switch."""
+        self._check(self.lib.mlst_set_read_names(self._h, int(bool(on))), "mlst_set_read_names")
+
+    def get_read_names(self) -> bool:
+        on = C.c_int()
+        self._check(self.lib.mlst_get_read_names(self._h, C.byref(on)), "mlst_get_read_names")
+        return bool(on.value)
+
+    def read_names_info(self) -> dict:
+        """Since the last reset_sample: retained reads with a kept name, the bytes of those names, retained reads whose name is no
+        legal QNAME (they keep r<k>), the longest kept name.  All zero with the switch off."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.mlst_read_names_info(self._h, out), "mlst_read_names_info")
+        return {"named": int(out[0]), "bytes": int(out[1]), "fallbacks": int(out[2]), "longest": int(out[3])}
+
+    def read_names(self) -> dict:
+        """{read index: name (bytes)} of the retained reads with a kept name (mlst_read_names_fetch)"""
+        info = self.read_names_info()
+        n = info["named"]
+        ridx = np.zeros(max(n, 1), np.uint64); off = np.zeros(n + 1, np.uint64); data = np.zeros(max(info["bytes"], 1), np.uint8)
+        self._check(self.lib.mlst_read_names_fetch(self._h, ridx.ctypes.data_as(C.POINTER(C.c_uint64)), off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                   data.ctypes.data_as(C.POINTER(C.c_uint8))), "mlst_read_names_fetch")
+        raw = data.tobytes()
+        return {int(ridx[i]): raw[int(off[i]):int(off[i + 1])] for i in range(n)}
 
     @property
     def bgzf_verify(self) -> bool:

@@ -8,9 +8,13 @@ formatted on the host by `write_sam(path, idx, chosen, aln, paired)`:
     (the names samin resolves: AlleleIndex.label), one `@PG` line;
   * records sorted by (position of the allele in `chosen`, pos0, read_index, strand, diag): the file's bytes do not depend on
     the order the device exported them in;
-  * QNAME `r<k>`: the FASTQ path never carries read names to the device, so k is the read index, or read_index >> 1 when the
-    sample was submitted as pairs -- the mates then share a name, as sequenceBank wants (metamlst.py:127).  No pairing flags, as
-    with bowtie2 -U.  Under --long-reads / --long-bam-reads / --contigs the reads are windows and k is the window's index;
+  * QNAME `r<k>`: k is the read index, or read_index >> 1 when the sample was submitted as pairs -- the mates then share a name,
+    as sequenceBank wants (metamlst.py:127).  No pairing flags, as with bowtie2 -U.  Under --long-reads / --long-bam-reads /
+    --contigs the reads are windows and k is the window's index.  With `--read-names` (Engine.set_read_names; FASTQ input only) the
+    QNAME of both exports is the read's own name, `read_qname` below: the engine copies the names of the reads it retains out of the
+    FASTQ text on the device (csrc/read_names.h) and hands `write_sam` the map {read index: name}; a name that is no legal QNAME
+    keeps `r<k>`.  Every read carries its own name, mates included: the product submits mates as pairs only when their names are
+    equal (fastq.mates_share_names), so "one entry per QNAME per locus" holds as it does with `r<k>`;
   * FLAG 16 * strand, plus 256 on every record of a read (a read index, not a QNAME) except its best one: the highest AS, ties
     to the first in the sort order above;
   * MAPQ 255, RNEXT *, PNEXT 0, TLEN 0; POS = pos0 + 1; SEQ as exported (reference strand); QUAL chr(min(q, 93) + 33);
@@ -41,7 +45,7 @@ Python (they are the specification and the tests' yardstick; the command never c
     the file, and is the highest AS among the read's OTHER records.  A read with one record has no XS field, so XO stands in the
     15th column: Q1 by construction, as with bowtie2.  AS and XM are the true values; XO, XG and NM are `gap_figures` of the record.
 
-Not written: BAM / BGZF, real read names, MD:Z."""
+Not written: BAM / BGZF, MD:Z, the names of a reads BAM or of windows, pairing flags."""
 from __future__ import annotations
 
 import numpy as np
@@ -50,6 +54,28 @@ from .index import AlleleIndex
 from .samin import CIGAR_OPS
 
 PG_LINE = "@PG\tID:metamlst_amd\tPN:metamlst_amd"
+
+
+def read_qname(header_line: bytes, k: int) -> bytes:
+    """The QNAME of a read under --read-names, from its FASTQ header line (with or without its line end): the bytes behind the `@`
+    up to, not including, the first space, TAB, CR or LF (bowtie2's rule, and fastq.mates_share_names').  A name that is no legal SAM
+    QNAME -- `[!-?A-~]{1,254}`: empty, longer than 254 bytes, an `@` or a byte outside `!`..`~` in it -- gives `r<k>`, as without the
+    switch; k = the read index, or read index >> 1 when the sample was submitted as pairs.  The specification of csrc/read_names.h
+    and the tests' yardstick; the command never calls it."""
+    name = bytes(header_line)[1:]
+    for i, c in enumerate(name):
+        if c in b" \t\r\n":
+            name = name[:i]
+            break
+    if 1 <= len(name) <= 254 and all(0x21 <= c <= 0x7E and c != 0x40 for c in name):
+        return name
+    return b"r%d" % int(k)
+
+
+def _qname(ridx: int, paired: bool, names) -> str:
+    """QNAME of read index ridx: its name in `names` (a mapping read index -> bytes, or None), else r<k>"""
+    nm = names.get(int(ridx)) if names is not None else None
+    return nm.decode("ascii") if nm else "r%d" % (int(ridx) >> 1 if paired else int(ridx))
 
 
 def gap_figures(ops, seq: bytes, allele: str, pos0: int) -> tuple[int, int, int]:
@@ -79,9 +105,10 @@ def sam_order(chosen, aln) -> np.ndarray:
     return np.lexsort((aln.diag, aln.flags & 1, aln.read_index, aln.pos0, ref))
 
 
-def write_sam(path: str, idx: AlleleIndex, chosen, aln, paired: bool) -> int:
+def write_sam(path: str, idx: AlleleIndex, chosen, aln, paired: bool, names=None) -> int:
     """Write the records `aln` (engine.Alignments) of the chosen alleles (allele indices, in @SQ order) to `path`; paired: the
-    sample was submitted as pairs.  Returns the number of records written.  The rules: the module's docstring."""
+    sample was submitted as pairs; names: {read index: name (bytes)} of Engine.read_names() -- a read in it gets its name as QNAME,
+    None gives r<k> throughout.  Returns the number of records written.  The rules: the module's docstring."""
     chosen = [int(a) for a in chosen]
     order = sam_order(chosen, aln)
     n = len(aln)
@@ -107,8 +134,8 @@ def write_sam(path: str, idx: AlleleIndex, chosen, aln, paired: bool) -> int:
             ridx = int(aln.read_index[k])
             strand = int(aln.flags[k]) & 1
             xo, xg, nm = gap_figures(ops, seq, idx.sequence(a), int(aln.pos0[k]))
-            f.write("r%d\t%d\t%s\t%d\t255\t%s\t*\t0\t0\t%s\t%s\tAS:i:%d\tXS:i:%d\tXN:i:0\tXM:i:%d\tXO:i:%d\tXG:i:%d\tNM:i:%d\tYT:Z:UU\n" % (
-                ridx >> 1 if paired else ridx, 16 * strand + (0 if best[k] else 256), idx.label(a), int(aln.pos0[k]) + 1,
+            f.write("%s\t%d\t%s\t%d\t255\t%s\t*\t0\t0\t%s\t%s\tAS:i:%d\tXS:i:%d\tXN:i:0\tXM:i:%d\tXO:i:%d\tXG:i:%d\tNM:i:%d\tYT:Z:UU\n" % (
+                _qname(ridx, paired, names), 16 * strand + (0 if best[k] else 256), idx.label(a), int(aln.pos0[k]) + 1,
                 "".join("%d%s" % (int(o) >> 4, CIGAR_OPS[int(o) & 15]) for o in ops), seq.decode("ascii"), qual_all[s0:s1].decode("ascii"),
                 int(aln.as_[k]), int(aln.as_[k]), int(aln.xm[k]), xo, xg, nm))
     return n
@@ -121,13 +148,13 @@ def sam_all_header(idx: AlleleIndex) -> str:
     return "@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + sq + PG_LINE + "\n"
 
 
-def format_record(idx: AlleleIndex, rec, paired: bool, secondary: bool, xs) -> bytes:
+def format_record(idx: AlleleIndex, rec, paired: bool, secondary: bool, xs, names=None) -> bytes:
     """One line of the full export.  rec = (read index, strand, diag, locus, allele, pos0, AS, XM, CIGAR ops (len << 4 | op), SEQ
     (ASCII, reference strand), QUAL (raw Phred)); secondary: not the best record of its read index; xs: the highest AS among the
-    read's other records, None when it has no other record (no XS:i field then)."""
+    read's other records, None when it has no other record (no XS:i field then); names: {read index: name (bytes)} or None (r<k>)."""
     ridx, strand, _diag, _locus, a, pos0, as_, xm, ops, seq, qual = rec
     xo, xg, nm = gap_figures(ops, bytes(seq), idx.sequence(int(a)), int(pos0))
-    cols = ["r%d" % (int(ridx) >> 1 if paired else int(ridx)), "%d" % (16 * int(strand) + (256 if secondary else 0)), idx.label(int(a)), "%d" % (int(pos0) + 1), "255",
+    cols = [_qname(ridx, paired, names), "%d" % (16 * int(strand) + (256 if secondary else 0)), idx.label(int(a)), "%d" % (int(pos0) + 1), "255",
             "".join("%d%s" % (int(o) >> 4, CIGAR_OPS[int(o) & 15]) for o in ops), "*", "0", "0", bytes(seq).decode("ascii"),
             "".join(chr(min(int(q), 93) + 33) for q in bytes(qual)), "AS:i:%d" % int(as_)]
     if xs is not None:
@@ -136,10 +163,10 @@ def format_record(idx: AlleleIndex, rec, paired: bool, secondary: bool, xs) -> b
     return ("\t".join(cols) + "\n").encode("ascii")
 
 
-def all_records_rule(idx: AlleleIndex, recs, paired: bool) -> list:
+def all_records_rule(idx: AlleleIndex, recs, paired: bool, names=None) -> list:
     """The lines of the full export for a sample's records (tuples as format_record takes them, in any order): sorted by (read
     index, locus, strand, diag, allele); per read index the best record (highest AS, ties to the first in that order) is the one
-    without 256, and XS is the highest AS among the others."""
+    without 256, and XS is the highest AS among the others.  names: {read index: name (bytes)} under --read-names, None: r<k>."""
     order = sorted(recs, key=lambda r: (int(r[0]), int(r[3]), int(r[1]), int(r[2]), int(r[4])))
     out, k = [], 0
     while k < len(order):
@@ -150,7 +177,7 @@ def all_records_rule(idx: AlleleIndex, recs, paired: bool) -> list:
         best = scores.index(max(scores))
         for t, r in enumerate(order[k:e]):
             others = scores[:t] + scores[t + 1:]
-            out.append(format_record(idx, r, paired, t != best, max(others) if others else None))
+            out.append(format_record(idx, r, paired, t != best, max(others) if others else None, names))
         k = e
     return out
 
