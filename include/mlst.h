@@ -424,6 +424,26 @@ int mlst_get_read_names(mlst_handle* h, int* on);
 int mlst_read_names_info(mlst_handle* h, uint64_t out[4]);
 int mlst_read_names_fetch(mlst_handle* h, uint64_t* read_index /* n */, uint64_t* off /* n+1 */, uint8_t* bytes);
 
+/* ---- bowtie2's MD:Z field in the text export (off by default; csrc/aln_text.h; `cli type --md`) --------------------------------------
+ * mlst_set_export_md(h, 1): every record of mlst_alignments_text_* carries MD:Z:<text> between NM:i and YT:Z:UU, bowtie2's place;
+ *   columns 1-11 and every other field are the bytes they are without it.  With the switch off the export writes what it wrote
+ *   before the switch existed, with the kernels it ran then, and allocates nothing more.
+ * The rule (metamlst_amd.samout.md_text states it in Python): the CIGAR is walked in reference orientation with a match run u = 0.
+ *   An M column matches iff the SEQ letter is the upper-cased allele's and is not N -- the predicate of NM; a match: u += 1; otherwise
+ *   u in decimal, the allele's letter, u = 0.  A D run: u (also 0), '^', the run's allele letters, u = 0.  I and S runs do not break
+ *   the run.  At the end: u (also 0).  The text matches [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*.  An allele byte outside A-Z after
+ *   upper-casing is written as N.  SEQ + CIGAR + MD give the allele's bases under the record back.
+ * The switch is read by mlst_alignments_text_open and holds for that export; changing it while an export is open: MLST_E_INVALID.  It
+ *   is no part of the sample's state (statistics, pile-up, typing and mlst_reset_sample neither see nor change it) and may change at
+ *   any other time.  Memory: two bytes per (item, allele) pair of the largest round while an export with it is open.
+ * The line bound with the switch on: 3 n + 2 x 15 + 11 bytes more for a read of n bases -- 6 for TAB MD:Z:, 5 for the last run's
+ *   digits, 2 per M column (a mismatch's letter and the digits of the run in front of it, which are no more than 1 + the run), 2 per D
+ *   run and 1 per D column, with M + I <= n, fewer than 0.4 M gap runs (mlst_create admits 5 match_bonus <= 2 (gap_open + gap_ext)
+ *   only, and a record's score is positive) and D <= I + 2 x 15 (the band: band_w <= 15): (alleles of the locus) x (13 n + the longest
+ *   label + 233) per item.  MLST_E_LIMIT of mlst_alignments_text_open names the bytes needed under this bound. */
+int mlst_set_export_md(mlst_handle* h, int on);
+int mlst_get_export_md(mlst_handle* h, int* on);
+
 /* ---- ready-made alignments straight from a BGZF BAM (the reference's one input, metamlst.py:34) ------------------------------
  * The file is streamed twice, as the reference reads it twice (samtools view, then pysam): pass 1 is the hit accumulation of
  * metamlst.py:101-130 (what mlst_submit_* do for reads), pass 2 the pile-up of the chosen contigs (mlst_pileup_alignments).  The

@@ -7,6 +7,7 @@
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam -d DB      (also <out>/<sample>.sam: the alignments to the chosen alleles)
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam-all -d DB  (also <out>/<sample>.all.sam: every alignment, as bowtie2 -a would leave it)
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam-all --read-names -d DB  (QNAME = the reads' own names, kept on the GPU)
+    python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam --write-sam-all --md -d DB  (both exports with bowtie2's MD:Z field)
     python -m metamlst_amd.cli merge FOLDER -d DB [-z 5] [--filter ...] [--meta ...] [--idField ...] [--aligner auto|gpu|muscle]   (metamlst-merge.py:35-49)
     python -m metamlst_amd.cli index -d DB [-s seqs.fasta,...] [-t typings.txt,...] [-q dump.fa] [--list]   (metamlst-index.py:24-33)
 
@@ -98,6 +99,12 @@ def _type_parser(sub):
                         "one sample on one GPU (plain, .gz, bgzip, `a.fq,b.fq`, -2): it goes with none of a reads BAM, --contigs, "
                         "--long-reads, --long-bam-reads, --alignments, a folder or several samples, and --gpus N.  The .nfo and the --log "
                         "file do not change")
+    p.add_argument("--md", dest="md", action="store_true",
+                   help="with --write-sam / --write-sam-all: every record also carries bowtie2's MD:Z field, between NM:i and YT:Z (the "
+                        "allele's letters under the mismatching and deleted columns: metamlst_amd/samout.py, md_text), so that the reference "
+                        "bases can be rebuilt from the record alone (samtools calmd -e, pysam get_reference_sequence).  --write-sam-all "
+                        "formats it on the GPU.  Accepted and refused where the export flags are; it combines with --read-names.  The "
+                        ".nfo and the --log file do not change")
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -234,6 +241,9 @@ def run_type(a, argv=None) -> int:
             if on:
                 print("--read-names: " + why)
                 return 1
+    if a.md and not (a.write_sam or a.write_sam_all):      # (with an export flag it is accepted and refused where that flag is: below)
+        print("--md: it adds MD:Z to the records of an export: give --write-sam or --write-sam-all")
+        return 1
     for flag in [f for f, on in (("--write-sam", a.write_sam), ("--write-sam-all", a.write_sam_all)) if on]:      # (refused before any GPU use)
         if a.alignments:
             print(flag + " writes the engine's own alignments: with --alignments the file is the input")
@@ -405,7 +415,7 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
     eng.typing_enqueue(penalty=targs.penalty)
     st, chosen, letters = eng.typing_fetch()
     rc = _finish_type(a, idx, database, targs, st, None, typed=(chosen, letters))
-    names = None
+    names, md = None, bool(getattr(a, "md", False))      # --md: MD:Z in both exports (write_sam on the host, the full export on the device)
     if rc == 0 and getattr(a, "read_names", False):      # the engine knows its switch: the text export needs no more than that
         names = eng.read_names()
         info = eng.read_names_info()
@@ -414,10 +424,10 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
     if rc == 0 and a.write_sam:
         from .samout import write_sam
         alleles = [chosen[l] for l in sorted(chosen)]
-        write_sam(a.o + "/" + sample_name(a.READS) + ".sam", idx, alleles, eng.export_alignments(alleles), paired, names=names)
+        write_sam(a.o + "/" + sample_name(a.READS) + ".sam", idx, alleles, eng.export_alignments(alleles), paired, names=names, md=md)
     if rc == 0 and a.write_sam_all:
         from .samout import write_sam_all
-        write_sam_all(a.o + "/" + sample_name(a.READS) + ".all.sam", idx, eng, paired)
+        write_sam_all(a.o + "/" + sample_name(a.READS) + ".all.sam", idx, eng, paired, md=md)
     return rc
 
 

@@ -3827,7 +3827,8 @@ struct mlst_handle {
     // every alignment as SAM text (mlst_alignments_text_open / _next / _close; csrc/aln_text.h): no part of a sample's state.  Per export:
     // the sorted item list (perm, pair_off, item_read, read_first), the RNAME labels and the rounds; per round (sized by the largest
     // one): AtPair and line offset per pair, the list of the banded SW, AtRead per read, the workgroups' sums; d_text = the round's text.
-    struct AtState { bool open = false, ready = false, with_names = false; size_t next = 0; std::vector<AtRound> rounds; u64 round_bytes = 0, round_recs = 0, max_pairs = 0;
+    // md: the switch of mlst_set_export_md; with_md: what the open export read of it; d_mdw: the pairs' MD:Z widths, only with it.
+    struct AtState { bool open = false, ready = false, with_names = false, md = false, with_md = false; u16* d_mdw = nullptr; size_t next = 0; std::vector<AtRound> rounds; u64 round_bytes = 0, round_recs = 0, max_pairs = 0;
              u32* d_perm = nullptr; u64* d_pair_off = nullptr; u32* d_item_read = nullptr; u64* d_read_first = nullptr; u8* d_names = nullptr; u64* d_name_off = nullptr;
              AtPair* d_meta = nullptr; AtRead* d_reads = nullptr; u64* d_wex = nullptr; u64* d_gsum = nullptr; u64* d_dp = nullptr; u8* d_desc = nullptr;
              u8* d_text = nullptr; u64 cap_text = 0; u8* h_tot = nullptr; } at;
@@ -6709,6 +6710,18 @@ extern "C" int mlst_set_read_names(mlst_handle* h, int on) {
     h->rn.on = on != 0;
     return MLST_OK;
 }
+// MD:Z in the text export (include/mlst.h): no part of the sample's state; mlst_alignments_text_open reads it
+extern "C" int mlst_set_export_md(mlst_handle* h, int on) {
+    if (!h) return MLST_E_INVALID;
+    if (h->at.open) return fail(h, MLST_E_INVALID, "an export is open: mlst_set_export_md changes only before mlst_alignments_text_open or behind mlst_alignments_text_close");
+    h->at.md = on != 0;
+    return MLST_OK;
+}
+extern "C" int mlst_get_export_md(mlst_handle* h, int* on) {
+    if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
+    *on = h->at.md ? 1 : 0;
+    return MLST_OK;
+}
 extern "C" int mlst_get_read_names(mlst_handle* h, int* on) {
     if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
     *on = h->rn.on ? 1 : 0;
@@ -7121,7 +7134,7 @@ extern "C" int mlst_alignments_fetch(mlst_handle* h, uint64_t* read_index, uint3
 static void at_free(mlst_handle* h) {
     auto& T = h->at;
     hipFree(T.d_perm); hipFree(T.d_pair_off); hipFree(T.d_item_read); hipFree(T.d_read_first); hipFree(T.d_names); hipFree(T.d_name_off);
-    hipFree(T.d_meta); hipFree(T.d_reads); hipFree(T.d_wex); hipFree(T.d_gsum); hipFree(T.d_dp);
+    hipFree(T.d_meta); hipFree(T.d_reads); hipFree(T.d_wex); hipFree(T.d_gsum); hipFree(T.d_dp); hipFree(T.d_mdw); T.d_mdw = nullptr;
     T.d_perm = nullptr; T.d_pair_off = nullptr; T.d_item_read = nullptr; T.d_read_first = nullptr; T.d_names = nullptr; T.d_name_off = nullptr;
     T.d_meta = nullptr; T.d_reads = nullptr; T.d_wex = nullptr; T.d_gsum = nullptr; T.d_dp = nullptr;
     T.rounds.clear(); T.next = 0; T.open = false; T.ready = false;
@@ -7145,6 +7158,7 @@ extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, c
     RnCtr rnc; { int rc_ = rn_fetch(h, &rnc); if (rc_) return rc_; }      // mlst_set_read_names: the longest kept name bounds the QNAME column
     const bool with_names = h->rn.on && h->rn.d_ctr;
     const u64 max_qname = with_names ? rnc.longest : 0;
+    const bool with_md = T.md;      // mlst_set_export_md: read here, fixed until the export is closed
     std::vector<u32> nall(nl ? nl : 1, 0);
     for (u64 a = 0; a < na; a++) nall[h->allele_locus[a]]++;
     for (u64 l = 0; l < nl; l++) if (nall[l] >= (1u << 20)) return fail(h, MLST_E_LIMIT, "locus %llu has %u alleles: the export takes fewer than 2^20", (unsigned long long)l, nall[l]);
@@ -7179,7 +7193,7 @@ extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, c
         if (k == 0 || ridx[it.ret] != ridx[items[perm[k - 1]].ret]) { read_first.push_back(k); read_bound.push_back(0); }
         item_read[k] = (u32)(read_first.size() - 1);
         pair_off[k + 1] = pair_off[k] + nall[it.locus];
-        read_bound.back() += (u64)nall[it.locus] * at_line_bound((u32)(rlen[it.ret] & 0x7FFFu), max_name, max_qname);
+        read_bound.back() += (u64)nall[it.locus] * at_line_bound((u32)(rlen[it.ret] & 0x7FFFu), max_name, max_qname, with_md);
     }
     const u64 nr = read_first.size();
     read_first.push_back(ni);
@@ -7202,6 +7216,7 @@ extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, c
     ATCHK(dmalloc(&T.d_names, nbytes)); ATCHK(dmalloc(&T.d_name_off, na + 1));
     ATCHK(dmalloc(&T.d_meta, max_pairs)); ATCHK(dmalloc(&T.d_reads, max_reads)); ATCHK(dmalloc(&T.d_wex, max_pairs)); ATCHK(dmalloc(&T.d_gsum, max_groups));
     ATCHK(dmalloc(&T.d_dp, max_pairs + 2));      // the list, its length and the round's records behind it
+    if (with_md) ATCHK(dmalloc(&T.d_mdw, max_pairs));
     if (!T.d_desc) ATCHK(dmalloc(&T.d_desc, sizeof(AtDev) + sizeof(FqtDev) + sizeof(FqtMeta)));
     if (!T.h_tot) { void* p = nullptr; ATCHK(hipHostMalloc(&p, sizeof(FqtMeta) + 8, hipHostMallocDefault)); T.h_tot = (u8*)p; }
     std::vector<u64> noff(na + 1);
@@ -7216,13 +7231,14 @@ extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, c
     D.ascii = h->d_ascii; D.aoff = h->d_aoff; D.meta = T.d_meta; D.reads = T.d_reads; D.wex = T.d_wex; D.gsum = T.d_gsum;
     D.dp_list = T.d_dp; D.dp_n = T.d_dp + max_pairs; D.n_rec = T.d_dp + max_pairs + 1; D.paired = paired ? 1 : 0;
     if (with_names) { D.rn_bytes = h->rn.d_bytes; D.rn_off = h->rn.d_off; D.rn_len = h->rn.d_len; }
+    D.mdw = T.d_mdw;
     FqtDev F; memset((void*)&F, 0, sizeof F);
     F.wex = T.d_wex; F.gsum = T.d_gsum; F.meta = (FqtMeta*)(T.d_desc + sizeof(AtDev) + sizeof(FqtDev));
     ATCHK(hipMemcpyAsync(T.d_desc, &D, sizeof D, hipMemcpyHostToDevice, h->stream));
     ATCHK(hipMemcpyAsync(T.d_desc + sizeof(AtDev), &F, sizeof F, hipMemcpyHostToDevice, h->stream));
     ATCHK(hipStreamSynchronize(h->stream));      // (the host vectors go out of scope)
 #undef ATCHK
-    T.rounds.swap(rounds); T.max_pairs = max_pairs; T.next = 0; T.ready = false; T.open = true; T.with_names = with_names;
+    T.rounds.swap(rounds); T.max_pairs = max_pairs; T.next = 0; T.ready = false; T.open = true; T.with_names = with_names; T.with_md = with_md;
     return MLST_OK;
 }
 // the kernels of round T.next up to the lines' offsets; leaves the round's bytes and records in T.round_bytes / T.round_recs
@@ -7236,11 +7252,20 @@ static int at_prepare(mlst_handle* h) {
     HIPCHK(h, hipMemsetAsync(d_M, 0, sizeof(FqtMeta), h->stream));
     HIPCHK(h, hipMemcpyAsync(&d_F->n_recs, &R.n_pairs, 8, hipMemcpyHostToDevice, h->stream));
     const unsigned gw = (unsigned)grid_for(R.k1 - R.k0, 1, 8192);      // one-wave workgroups, as k_pileup
-    if (h->max_wpr <= 10) hipLaunchKernelGGL(k_at_decide_160, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
-    else hipLaunchKernelGGL(k_at_decide_320, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
-    hipLaunchKernelGGL((k_at_dp<false, false>), dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, (u8*)nullptr);
-    if (T.with_names) hipLaunchKernelGGL(k_at_reads<true>, dim3((unsigned)grid_for(R.r1 - R.r0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R);
-    else hipLaunchKernelGGL(k_at_reads<false>, dim3((unsigned)grid_for(R.r1 - R.r0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R);
+    const unsigned gr = (unsigned)grid_for(R.r1 - R.r0, 1, 8192);
+    if (T.with_md) {      // (the export without the switch runs the kernels it ran before the switch existed)
+        if (h->max_wpr <= 10) hipLaunchKernelGGL(k_at_decide_160_md, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
+        else hipLaunchKernelGGL(k_at_decide_320_md, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
+        hipLaunchKernelGGL((k_at_dp<false, false, true>), dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, (u8*)nullptr);
+        if (T.with_names) hipLaunchKernelGGL((k_at_reads<true, true>), dim3(gr), dim3(64), 0, h->stream, h->d_E, d_D, R);
+        else hipLaunchKernelGGL((k_at_reads<false, true>), dim3(gr), dim3(64), 0, h->stream, h->d_E, d_D, R);
+    } else {
+        if (h->max_wpr <= 10) hipLaunchKernelGGL(k_at_decide_160, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
+        else hipLaunchKernelGGL(k_at_decide_320, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
+        hipLaunchKernelGGL((k_at_dp<false, false, false>), dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, (u8*)nullptr);
+        if (T.with_names) hipLaunchKernelGGL((k_at_reads<true, false>), dim3(gr), dim3(64), 0, h->stream, h->d_E, d_D, R);
+        else hipLaunchKernelGGL((k_at_reads<false, false>), dim3(gr), dim3(64), 0, h->stream, h->d_E, d_D, R);
+    }
     if (ng) {
         hipLaunchKernelGGL(k_at_local, dim3((unsigned)ng), dim3(1024), 0, h->stream, T.d_wex, R.n_pairs, T.d_gsum);
         hipLaunchKernelGGL(k_fqt_scan, dim3(1), dim3(1024), 0, h->stream, (const FqtDev*)d_F, ng);
@@ -7272,13 +7297,14 @@ extern "C" int mlst_alignments_text_next(mlst_handle* h, uint8_t* text, uint64_t
         const AtRound R = T.rounds[T.next];
         if (T.cap_text < T.round_bytes) { hipFree(T.d_text); T.d_text = nullptr; T.cap_text = 0; HIPCHK(h, dmalloc(&T.d_text, T.round_bytes)); T.cap_text = T.round_bytes; }
         const AtDev* d_D = (const AtDev*)T.d_desc;
-        if (T.with_names) {      // (the export without the switch runs the kernels it ran before the switch existed)
-            hipLaunchKernelGGL(k_at_write<true>, dim3((unsigned)grid_for(R.k1 - R.k0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R, T.d_text);
-            hipLaunchKernelGGL((k_at_dp<true, true>), dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, T.d_text);
-        } else {
-            hipLaunchKernelGGL(k_at_write<false>, dim3((unsigned)grid_for(R.k1 - R.k0, 1, 8192)), dim3(64), 0, h->stream, h->d_E, d_D, R, T.d_text);
-            hipLaunchKernelGGL((k_at_dp<true, false>), dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, T.d_text);
-        }
+        const unsigned gk = (unsigned)grid_for(R.k1 - R.k0, 1, 8192);
+#define AT_EMIT(NAMES, MD) do { \
+            hipLaunchKernelGGL((k_at_write<NAMES, MD>), dim3(gk), dim3(64), 0, h->stream, h->d_E, d_D, R, T.d_text); \
+            if (MD) hipLaunchKernelGGL((k_at_md<NAMES>), dim3(gk), dim3(64 * AT_MD_WAVES), 0, h->stream, h->d_E, d_D, R, T.d_text); \
+            hipLaunchKernelGGL((k_at_dp<true, NAMES, MD>), dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, T.d_text); } while (0)
+        if (T.with_names) { if (T.with_md) AT_EMIT(true, true); else AT_EMIT(true, false); }      // (the export without a switch runs the kernels it ran before the switch existed)
+        else { if (T.with_md) AT_EMIT(false, true); else AT_EMIT(false, false); }
+#undef AT_EMIT
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemcpyAsync(text, T.d_text, T.round_bytes, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));

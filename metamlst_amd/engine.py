@@ -168,6 +168,8 @@ def load_library(path: str | None = None):
         "mlst_get_read_tiling_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_set_read_names": (C.c_int, [H, C.c_int]),
         "mlst_get_read_names": (C.c_int, [H, C.POINTER(C.c_int)]),
+        "mlst_set_export_md": (C.c_int, [H, C.c_int]),
+        "mlst_get_export_md": (C.c_int, [H, C.POINTER(C.c_int)]),
         "mlst_read_names_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_read_names_fetch": (C.c_int, [H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)]),
         "mlst_submit_reads_device": (C.c_int, [H, u8p, u8p, u64p, C.c_uint64, C.c_uint32, C.c_int]),
@@ -817,6 +819,17 @@ class Engine:
         raw = data.tobytes()
         return {int(ridx[i]): raw[int(off[i]):int(off[i + 1])] for i in range(n)}
 
+    def set_export_md(self, on: bool = True) -> None:
+        """export_sam_text / write_sam_all write bowtie2's MD:Z field between NM:i and YT:Z, formatted on the GPU (mlst_set_export_md; off
+        by default; the rule: samout.md_text).  Read when an export is opened and refused while one is open; no part of the sample's
+        state, so it may change at any other time."""
+        self._check(self.lib.mlst_set_export_md(self._h, int(bool(on))), "mlst_set_export_md")
+
+    def get_export_md(self) -> bool:
+        on = C.c_int()
+        self._check(self.lib.mlst_get_export_md(self._h, C.byref(on)), "mlst_get_export_md")
+        return bool(on.value)
+
     @property
     def bgzf_verify(self) -> bool:
         on = C.c_int()
@@ -923,18 +936,23 @@ class Engine:
         self._check(self.lib.mlst_alignments_fetch(self._h, *[_ptr(getattr(a, f.name)) for f in dataclasses.fields(a)]), "mlst_alignments_fetch")
         return a
 
-    def export_sam_text(self, idx, paired: bool = False, round_bytes: int = 0):
+    def export_sam_text(self, idx, paired: bool = False, round_bytes: int = 0, md: bool = False):
         """Every alignment of the sample as SAM records, formatted on the device (mlst_alignments_text_open / _next / _close; the
         rule: samout's docstring): a generator of `bytes`, whole lines, one per round of at most round_bytes of bounded text
         (0: 256 MiB).  idx: the loaded AlleleIndex (its labels are the RNAMEs); paired: the sample was submitted as pairs.  The
         rounds leave the device through one page-locked buffer; the export is closed on exhaustion and on error.  Reads the
-        sample's state and changes none of it."""
+        sample's state and changes none of it.  md=True: the records of this export carry MD:Z -- the switch of
+        set_export_md is set for it and put back when the export is closed; md=False leaves the switch as it stands."""
         labels = [idx.label(a).encode() for a in range(idx.n_alleles)]
         name_off = np.zeros(len(labels) + 1, np.uint64)
         name_off[1:] = np.cumsum([len(x) for x in labels], dtype=np.uint64)
         names = np.frombuffer(b"".join(labels) or b"\0", np.uint8)
-        self._check(self.lib.mlst_alignments_text_open(self._h, _ptr(names), _ptr(name_off), int(bool(paired)), int(round_bytes)), "mlst_alignments_text_open")
+        set_md = bool(md) and not self.get_export_md()      # (md=False asks the library nothing)
+        if set_md:
+            self.lib.mlst_alignments_text_close(self._h)      # (an export left open: the open below would close it, the switch refuses it)
+            self.set_export_md(True)
         try:
+            self._check(self.lib.mlst_alignments_text_open(self._h, _ptr(names), _ptr(name_off), int(bool(paired)), int(round_bytes)), "mlst_alignments_text_open")
             buf = None
             nb, nr, done = C.c_uint64(), C.c_uint64(), C.c_int()
             while True:
@@ -952,6 +970,8 @@ class Engine:
                     break
         finally:
             self.lib.mlst_alignments_text_close(self._h)
+            if set_md:
+                self.set_export_md(False)
 
     # ---- typing tail on the device ----
     def typing_enqueue(self, penalty: int = 100, mincov: int = 1, none_char: str = "N"):

@@ -45,7 +45,14 @@ Python (they are the specification and the tests' yardstick; the command never c
     the file, and is the highest AS among the read's OTHER records.  A read with one record has no XS field, so XO stands in the
     15th column: Q1 by construction, as with bowtie2.  AS and XM are the true values; XO, XG and NM are `gap_figures` of the record.
 
-Not written: BAM / BGZF, MD:Z, the names of a reads BAM or of windows, pairing flags."""
+MD:Z (`cli type --md`, `md=True` below; off by default): both exports then write bowtie2's `MD:Z:<text>` between `NM:i` and
+`YT:Z:UU`, bowtie2's place -- columns 12 and 15 stay where they are, so Q1 and the positional parse of metamlst.py see what they
+saw.  The text is `md_text` below: the match runs' lengths, the allele's letter under every M column that counts towards NM, `^` and
+the allele's letters of every D run.  With SEQ and the CIGAR it gives the allele's bases under the record back, so a record stands
+for itself (samtools calmd -e, pysam get_reference_sequence) without the allele FASTA.  `write_sam` formats it here; the full
+export formats it on the device (Engine.set_export_md: mlst_set_export_md, csrc/aln_text.h).
+
+Not written: BAM / BGZF, the names of a reads BAM or of windows, pairing flags."""
 from __future__ import annotations
 
 import numpy as np
@@ -54,6 +61,7 @@ from .index import AlleleIndex
 from .samin import CIGAR_OPS
 
 PG_LINE = "@PG\tID:metamlst_amd\tPN:metamlst_amd"
+_QUAL_TAB = bytes(min(q, 93) + 33 for q in range(256))      # raw Phred -> QUAL character
 
 
 def read_qname(header_line: bytes, k: int) -> bytes:
@@ -98,6 +106,42 @@ def gap_figures(ops, seq: bytes, allele: str, pos0: int) -> tuple[int, int, int]
     return xo, xg, xg + mism
 
 
+def md_text(ops, seq: bytes, allele: str, pos0: int) -> str:
+    """The MD:Z text of one record (arguments as gap_figures takes them): the specification of the device's text and the tests'
+    yardstick.  The CIGAR is walked in reference orientation with q into SEQ, r = pos0 into the upper-cased allele and a match run u:
+      * an M column matches iff SEQ[q] == REF[r] and SEQ[q] != 'N' -- the predicate of NM (gap_figures; csrc/aln_text.h:
+        at_col_differs) and of samtools calmd, where an N on either side is a mismatch.  A match: u += 1.  Otherwise u in decimal, then
+        the letter REF[r], and u = 0;
+      * a D run: u (also when it is 0), then `^` and the run's allele letters, and u = 0;
+      * I and S runs advance q only and do not break the match run;
+      * at the end: u (also when it is 0).
+    So the text always matches [0-9]+(([A-Z]|\\^[A-Z]+)[0-9]+)*: the 0 between two neighbouring mismatches, and between a deletion and a
+    mismatch behind it, is no special case.  An allele byte that is not A-Z after upper-casing is written as N.  That can happen:
+    dbbuild.add_sequences stores a FASTA record's sequence lines as they are and AlleleIndex hands the bytes on unchanged (the engine
+    packs every byte outside ACGT as an N column), so `-`, `*`, `.` or a digit in a database's FASTA reaches this function."""
+    ref = allele.upper().encode()
+    out, u = [], 0
+    q, r = 0, int(pos0)
+    for o in ops:
+        ln, op = int(o) >> 4, int(o) & 15
+        if op == 0:
+            for k in range(ln):
+                x, y = seq[q + k], ref[r + k]
+                if x == y and x != 78:
+                    u += 1
+                else:
+                    out.append("%d%s" % (u, chr(y) if 65 <= y <= 90 else "N"))
+                    u = 0
+            q += ln; r += ln
+        elif op == 2:
+            out.append("%d^%s" % (u, "".join(chr(y) if 65 <= y <= 90 else "N" for y in ref[r:r + ln])))
+            u = 0; r += ln
+        elif op in (1, 4):
+            q += ln
+    out.append("%d" % u)
+    return "".join(out)
+
+
 def sam_order(chosen, aln) -> np.ndarray:
     """the records' order in the file: by (position of the allele in `chosen`, pos0, read_index, strand, diag)"""
     slot = {int(a): k for k, a in enumerate(chosen)}
@@ -105,10 +149,11 @@ def sam_order(chosen, aln) -> np.ndarray:
     return np.lexsort((aln.diag, aln.flags & 1, aln.read_index, aln.pos0, ref))
 
 
-def write_sam(path: str, idx: AlleleIndex, chosen, aln, paired: bool, names=None) -> int:
+def write_sam(path: str, idx: AlleleIndex, chosen, aln, paired: bool, names=None, md: bool = False) -> int:
     """Write the records `aln` (engine.Alignments) of the chosen alleles (allele indices, in @SQ order) to `path`; paired: the
     sample was submitted as pairs; names: {read index: name (bytes)} of Engine.read_names() -- a read in it gets its name as QNAME,
-    None gives r<k> throughout.  Returns the number of records written.  The rules: the module's docstring."""
+    None gives r<k> throughout; md: MD:Z:<md_text> between NM:i and YT:Z:UU.  Returns the number of records written.  The rules: the
+    module's docstring."""
     chosen = [int(a) for a in chosen]
     order = sam_order(chosen, aln)
     n = len(aln)
@@ -134,10 +179,11 @@ def write_sam(path: str, idx: AlleleIndex, chosen, aln, paired: bool, names=None
             ridx = int(aln.read_index[k])
             strand = int(aln.flags[k]) & 1
             xo, xg, nm = gap_figures(ops, seq, idx.sequence(a), int(aln.pos0[k]))
-            f.write("%s\t%d\t%s\t%d\t255\t%s\t*\t0\t0\t%s\t%s\tAS:i:%d\tXS:i:%d\tXN:i:0\tXM:i:%d\tXO:i:%d\tXG:i:%d\tNM:i:%d\tYT:Z:UU\n" % (
+            mdz = "\tMD:Z:" + md_text(ops, seq, idx.sequence(a), int(aln.pos0[k])) if md else ""
+            f.write("%s\t%d\t%s\t%d\t255\t%s\t*\t0\t0\t%s\t%s\tAS:i:%d\tXS:i:%d\tXN:i:0\tXM:i:%d\tXO:i:%d\tXG:i:%d\tNM:i:%d%s\tYT:Z:UU\n" % (
                 _qname(ridx, paired, names), 16 * strand + (0 if best[k] else 256), idx.label(a), int(aln.pos0[k]) + 1,
                 "".join("%d%s" % (int(o) >> 4, CIGAR_OPS[int(o) & 15]) for o in ops), seq.decode("ascii"), qual_all[s0:s1].decode("ascii"),
-                int(aln.as_[k]), int(aln.as_[k]), int(aln.xm[k]), xo, xg, nm))
+                int(aln.as_[k]), int(aln.as_[k]), int(aln.xm[k]), xo, xg, nm, mdz))
     return n
 
 
@@ -148,25 +194,30 @@ def sam_all_header(idx: AlleleIndex) -> str:
     return "@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + sq + PG_LINE + "\n"
 
 
-def format_record(idx: AlleleIndex, rec, paired: bool, secondary: bool, xs, names=None) -> bytes:
+def format_record(idx: AlleleIndex, rec, paired: bool, secondary: bool, xs, names=None, md: bool = False) -> bytes:
     """One line of the full export.  rec = (read index, strand, diag, locus, allele, pos0, AS, XM, CIGAR ops (len << 4 | op), SEQ
     (ASCII, reference strand), QUAL (raw Phred)); secondary: not the best record of its read index; xs: the highest AS among the
-    read's other records, None when it has no other record (no XS:i field then); names: {read index: name (bytes)} or None (r<k>)."""
+    read's other records, None when it has no other record (no XS:i field then); names: {read index: name (bytes)} or None (r<k>);
+    md: MD:Z:<md_text> between NM:i and YT:Z:UU."""
     ridx, strand, _diag, _locus, a, pos0, as_, xm, ops, seq, qual = rec
     xo, xg, nm = gap_figures(ops, bytes(seq), idx.sequence(int(a)), int(pos0))
     cols = [_qname(ridx, paired, names), "%d" % (16 * int(strand) + (256 if secondary else 0)), idx.label(int(a)), "%d" % (int(pos0) + 1), "255",
             "".join("%d%s" % (int(o) >> 4, CIGAR_OPS[int(o) & 15]) for o in ops), "*", "0", "0", bytes(seq).decode("ascii"),
-            "".join(chr(min(int(q), 93) + 33) for q in bytes(qual)), "AS:i:%d" % int(as_)]
+            bytes(qual).translate(_QUAL_TAB).decode("ascii"), "AS:i:%d" % int(as_)]
     if xs is not None:
         cols.append("XS:i:%d" % int(xs))
-    cols += ["XN:i:0", "XM:i:%d" % int(xm), "XO:i:%d" % xo, "XG:i:%d" % xg, "NM:i:%d" % nm, "YT:Z:UU"]
+    cols += ["XN:i:0", "XM:i:%d" % int(xm), "XO:i:%d" % xo, "XG:i:%d" % xg, "NM:i:%d" % nm]
+    if md:
+        cols.append("MD:Z:" + md_text(ops, bytes(seq), idx.sequence(int(a)), int(pos0)))
+    cols.append("YT:Z:UU")
     return ("\t".join(cols) + "\n").encode("ascii")
 
 
-def all_records_rule(idx: AlleleIndex, recs, paired: bool, names=None) -> list:
+def all_records_rule(idx: AlleleIndex, recs, paired: bool, names=None, md: bool = False) -> list:
     """The lines of the full export for a sample's records (tuples as format_record takes them, in any order): sorted by (read
     index, locus, strand, diag, allele); per read index the best record (highest AS, ties to the first in that order) is the one
-    without 256, and XS is the highest AS among the others.  names: {read index: name (bytes)} under --read-names, None: r<k>."""
+    without 256, and XS is the highest AS among the others.  names: {read index: name (bytes)} under --read-names, None: r<k>;
+    md: the records carry MD:Z."""
     order = sorted(recs, key=lambda r: (int(r[0]), int(r[3]), int(r[1]), int(r[2]), int(r[4])))
     out, k = [], 0
     while k < len(order):
@@ -177,18 +228,18 @@ def all_records_rule(idx: AlleleIndex, recs, paired: bool, names=None) -> list:
         best = scores.index(max(scores))
         for t, r in enumerate(order[k:e]):
             others = scores[:t] + scores[t + 1:]
-            out.append(format_record(idx, r, paired, t != best, max(others) if others else None, names))
+            out.append(format_record(idx, r, paired, t != best, max(others) if others else None, names, md))
         k = e
     return out
 
 
-def write_sam_all(path: str, idx: AlleleIndex, eng, paired: bool, round_bytes: int = 0) -> int:
+def write_sam_all(path: str, idx: AlleleIndex, eng, paired: bool, round_bytes: int = 0, md: bool = False) -> int:
     """Write every alignment of the sample on `eng` to `path`: the header here, the records as the device formats them, round by
-    round.  Returns the number of records written."""
+    round (md: with MD:Z, formatted there too).  Returns the number of records written."""
     n = 0
     with open(path, "wb") as f:
         f.write(sam_all_header(idx).encode("ascii"))
-        for chunk in eng.export_sam_text(idx, paired=paired, round_bytes=round_bytes):
+        for chunk in eng.export_sam_text(idx, paired=paired, round_bytes=round_bytes, md=md):
             f.write(chunk)
             n += chunk.count(b"\n")
     return n

@@ -116,4 +116,5 @@ with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "align_export
         f.write("`bench.py` against the commit before: not measured in this run (BENCH_AB not given).\n\n")
     if os.environ.get("KERNEL_RESOURCES"):
         f.write("Compiler's resource report of the new kernels (`-Rpass-analysis=kernel-resource-usage`, gfx950):\n\n%s\n\n" % os.environ["KERNEL_RESOURCES"])
+    f.write("`--write-sam --md` (MD:Z in every record): the field is formatted on the host, by `samout.md_text` inside `samout.write_sam`, one walk of the record's CIGAR next to the one `gap_figures` makes; the device export and fetch above are the same calls with and without it.  Wall time of `cli type --write-sam` with and without `--md`: not measured.  The device-formatted field of `--write-sam-all`: profiles/sam_all.md.\n\n")
     f.write("```\n%s\n```\n" % json.dumps(out))

@@ -10,7 +10,9 @@ Each is submitted, then timed by a host clock around calls that end in a device 
   * open + decide -- open, then mlst_alignments_text_next(NULL, 0): the first round's alignment, per-read figures, lengths and scan;
   * whole         -- open + every round with its formatting and its copy into page-locked host memory + close (ROUND_MB [256]);
   * copy          -- hipMemcpy of the same number of bytes from device memory into the same page-locked buffer, alone.
-"export alone" is whole - copy (derived; the copy is not overlapped with the kernels).  `BENCH_AB='<ms per step of the commit
+"export alone" is whole - copy (derived; the copy is not overlapped with the kernels).  With `--md` every sample is exported again with
+mlst_set_export_md on (MD:Z in every record): open + decide and whole with the switch on, then whole with it off once more (the
+off leg's own spread), reported beside the bytes the field adds.  `BENCH_AB='<ms per step of the commit
 before> <ms per step of this one> ...'` (pairs, alternating runs of bench.py --gpus 1 --steps 20 --warmup 5 on one machine in one
 session) and `KERNEL_RESOURCES=<text>` are copied into the report when set: bench.py never calls the export.
 One JSON line, and profiles/sam_all.md next to this script."""
@@ -38,6 +40,7 @@ RUNS = int(os.environ.get("RUNS", "5"))
 MANY_READS = int(os.environ.get("MANY_READS", "2000"))
 SMALL_READS = int(os.environ.get("SMALL_READS", "100"))
 ROUND_BYTES = int(os.environ.get("ROUND_MB", "256")) << 20
+MD = "--md" in sys.argv[1:]
 
 
 def timed(fn):
@@ -94,6 +97,10 @@ with tempfile.TemporaryDirectory() as tmp:
         chunks = list(eng.export_sam_text(idx, round_bytes=ROUND_BYTES))
         n_bytes, n_recs, biggest = sum(len(c) for c in chunks), sum(c.count(b"\n") for c in chunks), max([len(c) for c in chunks] + [1])
         assert n_recs == int(st.counters[0]), "the export does not hold the records pass 1 counted"
+        if MD:      # the same export with MD:Z: its bytes size the buffers too
+            chunks_md = list(eng.export_sam_text(idx, round_bytes=ROUND_BYTES, md=True))
+            assert sum(c.count(b"\n") for c in chunks_md) == n_recs and all(b"\tMD:Z:" in c for c in chunks_md)
+            biggest = max([len(c) for c in chunks_md] + [biggest])
         buf = pinned_array(biggest)
         dev = torch.empty(biggest, dtype=torch.uint8, device="cuda")
 
@@ -121,6 +128,13 @@ with tempfile.TemporaryDirectory() as tmp:
         s = {"name": name, "reads": len(off) - 1, "items": n_items, "records": n_recs, "bytes": n_bytes, "rounds": len(chunks),
              "open_ms": t_o[0], "open_runs_ms": t_o[1], "open_decide_first_round_ms": t_d[0], "open_decide_first_round_runs_ms": t_d[1],
              "whole_ms": t_w[0], "whole_runs_ms": t_w[1], "copy_ms": t_c[0], "copy_runs_ms": t_c[1]}
+        if MD:
+            eng.set_export_md(True)
+            t_dm, t_wm = timed(decide), timed(whole)
+            eng.set_export_md(False)
+            t_w2 = timed(whole)
+            s["md"] = {"bytes": sum(len(c) for c in chunks_md), "rounds": len(chunks_md), "open_decide_first_round_ms": t_dm[0], "open_decide_first_round_runs_ms": t_dm[1],
+                       "whole_ms": t_wm[0], "whole_runs_ms": t_wm[1], "whole_off_again_ms": t_w2[0], "whole_off_again_runs_ms": t_w2[1]}
         if name.startswith("small"):      # the same records through the plain-Python rule
             path = tmp + "/small.all.sam"
             with open(path, "wb") as f:
@@ -166,6 +180,20 @@ with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "sam_all.md")
         s = small[0]
         f.write("\nThe plain-Python rule (`samout.all_records_rule`, the specification) over the %d records of the small sample: %.1f ms, %.3g records/s (the same bytes: %s); "
                 "the device export of that sample: %.3f ms whole.\n" % (s["records"], s["python_rule_ms"], rate(s["records"], s["python_rule_ms"]), s["python_rule_same_bytes"], s["whole_ms"]))
+    if MD:
+        f.write("\n## With `--md` (`mlst_set_export_md`): MD:Z in every record\n\nThe same samples exported again with the switch on, then with it off once more; "
+                "whole export = open + every round into page-locked memory + close, median of %d.\n\n" % RUNS)
+        f.write("| sample | records | text bytes off | text bytes on | open + first round decided ms off / on | whole ms off | whole ms on | whole ms off again | time on against off | bytes on against off |\n"
+                "|---|---|---|---|---|---|---|---|---|---|\n")
+        for s in out["samples"]:
+            m = s["md"]
+            f.write("| %s | %d | %d | %d | %.3f / %.3f | %.3f | %.3f | %.3f | %+.2f %% | %+.2f %% |\n" % (
+                s["name"], s["records"], s["bytes"], m["bytes"], s["open_decide_first_round_ms"], m["open_decide_first_round_ms"], s["whole_ms"], m["whole_ms"], m["whole_off_again_ms"],
+                100.0 * (m["whole_ms"] / s["whole_ms"] - 1.0), 100.0 * (m["bytes"] / s["bytes"] - 1.0)))
+    else:
+        f.write("\nThe `--md` leg (MD:Z in every record, switch off against on): not measured in this run (`--md` not given).\n")
+    if os.environ.get("MD_OFF_AB"):      # whole export of the isolate with the switch off: a build of the commit before against this one's
+        f.write("\n%s\n" % os.environ["MD_OFF_AB"])
     if ab:
         b, t = ab[0::2], ab[1::2]
         f.write("\n`bench.py --gpus 1 --steps 20 --warmup 5`, ms per step, alternating runs in one session on one machine (a build of the commit before against this one's; "
