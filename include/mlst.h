@@ -424,6 +424,38 @@ int mlst_get_read_names(mlst_handle* h, int* on);
 int mlst_read_names_info(mlst_handle* h, uint64_t out[4]);
 int mlst_read_names_fetch(mlst_handle* h, uint64_t* read_index /* n */, uint64_t* off /* n+1 */, uint8_t* bytes);
 
+/* ---- reads prepared before they are aligned (off by default; csrc/read_prep.h; `cli type --trim5 / --trim3 / --trim-qual / --phred64`) --
+ * mlst_set_read_prep(h, &p): every read of FASTQ text is changed on the device before it is packed, as bowtie2 -5 / -3 / --phred64 and a
+ *   3' quality trimmer in front of it would have changed it; the engine then behaves as if it had been given the prepared text
+ *   (metamlst_amd.fastq.prep_fastq states the rule in Python and writes that text).  NULL or {0, 0, 0, 33} is off: nothing is queued,
+ *   nothing is allocated, and the kernels that run are those that ran before the switch existed.
+ * The rule, per record, in this order (header and '+' line are not looked at):
+ *   1. Phred: q[i] = clamp(character - phred_base, 0, 127), phred_base 33 or 64 (Illumina 1.3 - 1.7, bowtie2 --phred64).
+ *   2. Fixed trims (bowtie2's): a = min(trim5, n), n1 = max(0, n - trim5 - trim3); bases and qualities [a, a + n1) remain.
+ *   3. Quality trim of the 3' end (cutadapt -q T / bwa aln -q T, no minimum length) on what remains, T = trim_qual, 0 = off:
+ *        s = 0, best = 0, cut = n1;  for i = n1 - 1 .. 0: s += T - q[a + i]; stop when s < 0; if s > best: best = s, cut = i
+ *      and cut bases remain.
+ *   4. A read left without a base stays a read of length 0: read indices, pairing and the names of mlst_set_read_names are those of
+ *      the file.  It holds no seed and leaves no candidate.  Each mate of a pair is prepared on its own.
+ *   A malformed record (sequence and quality lengths differ) and a read beyond MLST_MAX_READ_LEN are judged on the record as it stands
+ *   in the file, before the trims.
+ * Entries it applies to: mlst_submit_fastq, mlst_submit_fastq_stream, mlst_submit_fastq_pair, mlst_submit_fastq_bgzf and
+ *   mlst_submit_fastq_bgzf_pair.  With the switch on every other way of adding reads (mlst_submit_reads, mlst_submit_reads_device,
+ *   mlst_submit_packed_device, mlst_submit_packed_host, mlst_submit_fasta, mlst_bam_reads_open) and mlst_set_read_tiling with a tile
+ *   are refused with MLST_E_INVALID ("<entry>: read preparation is on ..."), as is a setting other than off behind
+ *   mlst_set_read_tiling: a read that silently kept its tail would be worse than a refusal.  It combines with mlst_set_read_names.
+ * The setting may change only while the sample holds no reads (before the first submission or behind mlst_reset_sample; a non-zero
+ *   mlst_set_read_index_base counts as reads) and no stream is open: MLST_E_INVALID otherwise.  phred_base other than 33 / 64,
+ *   trim_qual > 93 or a trim > 65535: MLST_E_INVALID.  mlst_reset_sample zeroes the counters and keeps the setting.
+ * mlst_read_prep_info: out[0] = reads whose length changed, out[1] = bases removed, out[2] = reads of length >= 1 left without a base,
+ *   out[3] = 0.  All zero with the switch off.  An open BGZF piece is finished first.
+ * The packed rows (width, quality stride, lens with bit 15 for a non-ACGT base among the remaining bases only) are those of the
+ *   prepared text; no host synchronisation is added per chunk. */
+typedef struct { uint32_t trim5, trim3, trim_qual, phred_base; } mlst_read_prep;   /* phred_base 33 or 64 */
+int mlst_set_read_prep(mlst_handle* h, const mlst_read_prep* p);
+int mlst_get_read_prep(mlst_handle* h, mlst_read_prep* out);
+int mlst_read_prep_info(mlst_handle* h, uint64_t out[4]);
+
 /* ---- bowtie2's MD:Z field in the text export (off by default; csrc/aln_text.h; `cli type --md`) --------------------------------------
  * mlst_set_export_md(h, 1): every record of mlst_alignments_text_* carries MD:Z:<text> between NM:i and YT:Z:UU, bowtie2's place;
  *   columns 1-11 and every other field are the bytes they are without it.  With the switch off the export writes what it wrote

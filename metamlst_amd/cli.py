@@ -105,6 +105,21 @@ def _type_parser(sub):
                         "bases can be rebuilt from the record alone (samtools calmd -e, pysam get_reference_sequence).  --write-sam-all "
                         "formats it on the GPU.  Accepted and refused where the export flags are; it combines with --read-names.  The "
                         ".nfo and the --log file do not change")
+    p.add_argument("--trim5", default=0, type=int, metavar="N",
+                   help="FASTQ input: remove N bases from the 5' end of every read before it is aligned (bowtie2 -5 / --trim5), on the GPU "
+                        "(csrc/read_prep.h; the rule: metamlst_amd.fastq.prep_fastq).  The four read preparation flags (--trim5, --trim3, "
+                        "--trim-qual, --phred64) apply to plain, .gz and bgzip'd FASTQ, `a.fq,b.fq`, -2, a folder or several samples and "
+                        "--gpus N; they go with none of --alignments, --contigs, --long-reads, --long-bam-reads and a reads BAM.  A read "
+                        "left without a base stays a read (indices, pairing and --read-names are those of the file); the exports carry "
+                        "the prepared SEQ / QUAL, as bowtie2 prints trimmed reads")
+    p.add_argument("--trim3", default=0, type=int, metavar="N",
+                   help="FASTQ input: remove N bases from the 3' end of every read before it is aligned (bowtie2 -3 / --trim3); see --trim5")
+    p.add_argument("--trim-qual", dest="trim_qual", default=0, type=int, metavar="Q",
+                   help="FASTQ input: then trim the 3' end of every read by quality with threshold Q (the rule of cutadapt -q Q and "
+                        "bwa aln -q Q, no minimum length), behind --trim5 / --trim3; 0 (default) = off; see --trim5")
+    p.add_argument("--phred64", action="store_true",
+                   help="FASTQ input: the qualities are Phred+64 (Illumina 1.3 - 1.7, bowtie2 --phred64), not Phred+33.  Nothing detects "
+                        "the base: without the flag such a file is typed with every quality 31 too high; see --trim5")
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -241,6 +256,19 @@ def run_type(a, argv=None) -> int:
             if on:
                 print("--read-names: " + why)
                 return 1
+    read_prep = _read_prep_of(a)
+    if read_prep is not None:      # (refused before any GPU use, each with its reason)
+        if read_prep is False:
+            return 1
+        for on, why in ((a.alignments, "with --alignments the records are what they are: the file holds alignments, not reads to prepare"),
+                        (a.contigs, "--contigs cuts assemblies into windows, and a window is cut from the sequence as it stands"),
+                        (a.long_reads, "--long-reads cuts reads into windows, and a window is cut from the record as it stands"),
+                        (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and a window is cut from the record as it stands"),
+                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp),
+                         "a reads BAM stores raw Phred and its own strand, and its reads are not prepared: FASTQ input only")):
+            if on:
+                print("read preparation (--trim5, --trim3, --trim-qual, --phred64): " + why)
+                return 1
     if a.md and not (a.write_sam or a.write_sam_all):      # (with an export flag it is accepted and refused where that flag is: below)
         print("--md: it adds MD:Z to the records of an export: give --write-sam or --write-sam-all")
         return 1
@@ -305,6 +333,8 @@ def run_type(a, argv=None) -> int:
         eng.set_read_tiling(*(long_reads or long_bam))
     if a.read_names:      # (FASTQ input only: text, host-inflated .gz and BGZF all reach the device as text, where the names are kept)
         eng.set_read_names(True)
+    if read_prep:      # (the same entries: the reads are prepared where the text is parsed; before a rank's first read index base)
+        eng.set_read_prep(**read_prep)
     # the built host index is kept next to the database (as the reference keeps <idx>.1.bt2: metamlst-index.py:224-225) unless a
     # species filter made this index a one-off or MLST_INDEX_CACHE=0
     ref_cache = (a.database + ".mlstref") if (not a.filter and os.environ.get("MLST_INDEX_CACHE", "1") != "0") else ""
@@ -326,6 +356,8 @@ def run_type(a, argv=None) -> int:
             e2.set_bgzf_verify(a.verify_crc)
             if long_reads or long_bam:
                 e2.set_read_tiling(*(long_reads or long_bam))
+            if read_prep:
+                e2.set_read_prep(**read_prep)
             if a.depth_cap:
                 e2.set_depth_cap(a.depth_cap)
             engines.append(e2)
@@ -334,9 +366,12 @@ def run_type(a, argv=None) -> int:
     chunk_bytes = int(os.environ.get("MLST_FASTQ_CHUNK", str(256 << 20)))
     if many:
         from .multigpu import type_many_samples
+        prep_info = {"shortened": 0, "bases_removed": 0, "emptied": 0} if read_prep and not a.quiet else None
         rc = type_many_samples(engines, idx, database, targs, samples, rank, world, a.o, a.log, chunk_bytes,
                                printer=None if a.quiet else (lambda results: _print_results(a, results)), tile=tile, long_reads=long_reads,
-                               long_bam_reads=long_bam)
+                               long_bam_reads=long_bam, read_prep_info=prep_info)
+        if prep_info is not None:
+            _say_read_prep(prep_info, world)
         database.closeConnection()
         return rc
     if a.alignments:
@@ -392,6 +427,11 @@ def run_type(a, argv=None) -> int:
             _print_results(a, results)
         database.closeConnection()
         import torch.distributed as dist
+        if read_prep:      # one line for the sample: the ranks' counters, summed
+            box = [None] * world
+            dist.all_gather_object(box, eng.read_prep_info())
+            if rank == 0 and not a.quiet:
+                _say_read_prep({key: sum(b[key] for b in box) for key in box[0]}, 1)
         dist.destroy_process_group()
         return 0
     # FASTQ text goes to the GPU as is and is parsed there (mlst_submit_fastq); a reader thread stays two chunks ahead
@@ -415,6 +455,8 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
     eng.typing_enqueue(penalty=targs.penalty)
     st, chosen, letters = eng.typing_fetch()
     rc = _finish_type(a, idx, database, targs, st, None, typed=(chosen, letters))
+    if rc == 0 and not a.quiet and _read_prep_of(a):
+        _say_read_prep(eng.read_prep_info(), 1)
     names, md = None, bool(getattr(a, "md", False))      # --md: MD:Z in both exports (write_sam on the host, the full export on the device)
     if rc == 0 and getattr(a, "read_names", False):      # the engine knows its switch: the text export needs no more than that
         names = eng.read_names()
@@ -429,6 +471,27 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
         from .samout import write_sam_all
         write_sam_all(a.o + "/" + sample_name(a.READS) + ".all.sam", idx, eng, paired, md=md)
     return rc
+
+
+def _read_prep_of(a):
+    """The four read preparation flags -> the arguments of Engine.set_read_prep, None when none is given, False (said) when one is
+    out of range"""
+    t5, t3, tq, p64 = getattr(a, "trim5", 0), getattr(a, "trim3", 0), getattr(a, "trim_qual", 0), bool(getattr(a, "phred64", False))
+    if not (t5 or t3 or tq or p64):
+        return None
+    for flag, v, top in (("--trim5", t5, 65535), ("--trim3", t3, 65535), ("--trim-qual", tq, 93)):
+        if not 0 <= v <= top:
+            print("%s takes a number from 0 to %d, not %d" % (flag, top, v))
+            return False
+    return {"trim5": t5, "trim3": t3, "trim_qual": tq, "phred64": p64}
+
+
+def _say_read_prep(info: dict, world: int) -> None:
+    """The line on what the read preparation did (info: Engine.read_prep_info(), summed over the samples of a folder; a rank of --gpus N
+    speaks for its own reads)"""
+    n, m, k = info["shortened"], info["bases_removed"], info["emptied"]
+    rank = (" (the samples of rank %s of %d)" % (os.environ.get("RANK", "0"), world)) if world > 1 else ""
+    print("read preparation: %d reads shortened, %d bases removed, %d reads left without a base%s" % (n, m, k, rank), flush=True)
 
 
 class _FileReader:

@@ -241,7 +241,8 @@ __host__ __device__ inline u64 packed_words(u64 n_reads, u32 wpr) { return ((n_r
 // 0.18 TB/s).
 // seq_off / qual_off: byte offset of every read's bases / qualities inside `bases` / `quals` (the same array for ASCII
 // reads given by one offset table; FASTQ text has separate ones); len_of(r) gives the length.
-template <typename LenFn>
+// QB: the character of Phred 0 -- 33, or 64 for the text of a sample given with mlst_set_read_prep's phred_base 64.
+template <u32 QB, typename LenFn>
 __device__ inline void pack_group(const u8* __restrict__ bases, const u8* __restrict__ quals, const u64* __restrict__ seq_off,
                                   const u64* __restrict__ qual_off, LenFn len_of, u64 n_reads, u64 grp,
                                   u32* __restrict__ packed, u8* __restrict__ qrows, u16* __restrict__ lens, u32 wpr, u32 qstride,
@@ -260,7 +261,7 @@ __device__ inline void pack_group(const u8* __restrict__ bases, const u8* __rest
                 __builtin_memcpy(cs, bases + so + w * 16, 16); __builtin_memcpy(cq, quals + qo + w * 16, 16);
             } else {
                 #pragma unroll
-                for (int k = 0; k < 16; k++) { const u32 p = w * 16 + k; const bool in = p < n; cs[k] = in ? bases[so + p] : (u8)'A'; cq[k] = in ? quals[qo + p] : (u8)33; }
+                for (int k = 0; k < 16; k++) { const u32 p = w * 16 + k; const bool in = p < n; cs[k] = in ? bases[so + p] : (u8)'A'; cq[k] = in ? quals[qo + p] : (u8)33; }      // ('!' is Phred 0 under either base)
             }
             // sixteen bases and qualities, four at a time in 32-bit words (round 5; a compare chain per character before: ~350
             // instructions per word).  Bytes beyond the read are 'A' / '!' here (see above) and come out as zeros, as before.
@@ -275,15 +276,15 @@ __device__ inline void pack_group(const u8* __restrict__ bases, const u8* __rest
                 const u32 isn = ((diff | ((diff & 0x7F7F7F7Fu) + 0x7F7F7F7Fu)) >> 7) & 0x01010101u;
                 code &= ~(isn * 3u);                                                                      // (packed as A)
                 word |= ((code * 0x01041040u) >> 24) << (8 * j);                                          // four 2-bit codes -> one byte
-                // Phred = character - 33, kept in 0..127
+                // Phred = character - QB, kept in 0..127
                 u32 qv;
-                const u32 lowc = (q4 | 0x80808080u) - 0x21212121u;                                         // bit 7 of a byte survives iff its character is >= 33
-                const u32 okl = ((lowc & 0x80808080u) >> 7) | ((q4 & 0x80808080u) >> 7);                    // 1: character >= 33
-                if (okl == 0x01010101u && !(q4 & 0x80808080u)) qv = q4 - 0x21212121u;                      // the usual case: 33..127 everywhere
+                const u32 lowc = (q4 | 0x80808080u) - QB * 0x01010101u;                                    // bit 7 of a byte survives iff its character is >= QB
+                const u32 okl = ((lowc & 0x80808080u) >> 7) | ((q4 & 0x80808080u) >> 7);                    // 1: character >= QB
+                if (okl == 0x01010101u && !(q4 & 0x80808080u)) qv = q4 - QB * 0x01010101u;                 // the usual case: QB..127 everywhere
                 else {
                     qv = 0;
                     #pragma unroll
-                    for (int k = 0; k < 4; k++) { int q = (int)((q4 >> (8 * k)) & 0xFFu) - 33; q = q < 0 ? 0 : (q > 127 ? 127 : q); qv |= (u32)q << (8 * k); }
+                    for (int k = 0; k < 4; k++) { int q = (int)((q4 >> (8 * k)) & 0xFFu) - (int)QB; q = q < 0 ? 0 : (q > 127 ? 127 : q); qv |= (u32)q << (8 * k); }
                 }
                 qw[j] = qv | (isn << 7);
                 anyn |= isn;
@@ -307,7 +308,7 @@ __global__ __launch_bounds__(256) void k_pack(const u8* __restrict__ bases, cons
     __shared__ u32 s_words[64 * RW]; __shared__ u32 s_anyn[2];
     const u64 n_groups = (n_reads + 63) >> 6;
     for (u64 grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
-        pack_group(bases, quals, off, off, [&](u64 r) { return (u32)(off[r + 1] - off[r]); }, n_reads, grp, packed, qrows, lens, wpr, qstride, s_words, s_anyn);
+        pack_group<33>(bases, quals, off, off, [&](u64 r) { return (u32)(off[r + 1] - off[r]); }, n_reads, grp, packed, qrows, lens, wpr, qstride, s_words, s_anyn);
         __syncthreads();
     }
 }
@@ -1645,7 +1646,8 @@ __global__ __launch_bounds__(256) void k_fq_pair_records(const u8* __restrict__ 
     if (err) atomicOr(&flags[1], err);
 }
 // pack from text: same output format as k_pack, reads addressed by separate sequence / quality offsets; lens holds the
-// plain lengths on entry (k_fq_records)
+// plain lengths on entry (k_fq_records).  QB: the Phred base of the text (pack_group)
+template <u32 QB>
 __global__ __launch_bounds__(256) void k_pack_text(const u8* __restrict__ text, const u64* __restrict__ seq_off, const u64* __restrict__ qual_off,
                                                     u16* __restrict__ lens, u64 n_reads, u32* __restrict__ packed, u8* __restrict__ qrows, u32 wpr, u32 qstride) {
     __shared__ u32 s_words[64 * RW]; __shared__ u32 s_anyn[2]; __shared__ u16 s_len[64];
@@ -1653,7 +1655,7 @@ __global__ __launch_bounds__(256) void k_pack_text(const u8* __restrict__ text, 
     for (u64 grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
         if (threadIdx.x < 64) { const u64 r = grp * 64 + threadIdx.x; s_len[threadIdx.x] = r < n_reads ? (u16)(lens[r] & 0x7FFFu) : (u16)0; }
         __syncthreads();
-        pack_group(text, text, seq_off, qual_off, [&](u64 r) { return (u32)s_len[r & 63]; }, n_reads, grp, packed, qrows, lens, wpr, qstride, s_words, s_anyn);
+        pack_group<QB>(text, text, seq_off, qual_off, [&](u64 r) { return (u32)s_len[r & 63]; }, n_reads, grp, packed, qrows, lens, wpr, qstride, s_words, s_anyn);
         __syncthreads();
     }
 }
@@ -3687,6 +3689,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "msa_dev.h"
 #include "aln_export.h"
 #include "read_names.h"
+#include "read_prep.h"
 #include "aln_text.h"
 
 // ================================================================== host side
@@ -3837,6 +3840,9 @@ struct mlst_handle {
     // submission under the switch; src: where the header lines of the chunk being submitted start (set by the FASTQ parsers)
     struct { bool on = false; u64 want_bytes = 256ull << 20; RnCtr* d_ctr = nullptr; u8* d_bytes = nullptr; u64 cap_bytes = 0; u64* d_off = nullptr; u16* d_len = nullptr;
              RnSrc src = {nullptr, nullptr, 0}; } rn;
+    // reads prepared before they are packed (mlst_set_read_prep; csrc/read_prep.h): the switch (on: the setting is not {0,0,0,33}), the
+    // setting, the counters on the device -- allocated by the first submission that trims
+    struct { bool on = false; RpSet set = {0, 0, 0, 33}; RpCtr* d_ctr = nullptr; } rp;
 };
 
 static std::string g_create_err;
@@ -3855,6 +3861,7 @@ static int bam_flush(mlst_handle* h);     // BAM input: the piece in flight is f
 static void bam_drop(mlst_handle* h, bool release);      // the BAM stream is closed and forgotten (release: its buffers too)
 static bool bam_is_open(const mlst_handle* h);
 static int rn_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_names is on: an entry that carries no names is refused
+static int rp_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_prep is on: an entry that does not prepare its reads is refused
 static void at_free(mlst_handle* h);      // the per-export tables of mlst_alignments_text_*
 static const char* bam_kind(const mlst_handle* h);      // "BAM" or "SAM": what the open stream of ready-made alignments takes
 template <typename T> static hipError_t dmalloc(T** p, u64 n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
@@ -4025,7 +4032,7 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     if (h->copy_stream) hipStreamDestroy(h->copy_stream);
     hipFree(h->d_cand); hipFree(h->d_in_bases); hipFree(h->d_in_quals); hipFree(h->d_in_off);
     hipFree(h->d_fq_slot[0]); hipFree(h->d_fq_slot[1]); hipFree(h->d_fq_nl[0]); hipFree(h->d_fq_nl[1]); hipFree(h->d_fq_blk); hipFree(h->d_fq_lines); hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); hipFree(h->d_fq_meta);
-    hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta);
+    hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta); hipFree(h->rp.d_ctr);
     hipFree(h->fa.d_desc); hipFree(h->fa.d_meta); hipFree(h->fa.d_flat); hipFree(h->fa.d_kind); hipFree(h->fa.d_cseq); hipFree(h->fa.d_chdr); hipFree(h->fa.d_cstart); hipFree(h->fa.d_wcnt);
     if (h->fa.h_fa) hipHostFree(h->fa.h_fa);
     hipFree(h->tile.d_desc); hipFree(h->tile.d_meta); hipFree(h->tile.d_rlen); hipFree(h->tile.d_wex); hipFree(h->tile.d_gsum); hipFree(h->tile.d_soff); hipFree(h->tile.d_qoff);
@@ -4051,6 +4058,7 @@ static int reset_sample_state(mlst_handle* h) {
     HIPCHK(h, hipMemsetAsync(h->d_stats + h->off_first, 0xFF, h->stats_bytes - h->off_first, h->stream));
     if (h->d_acc64 && h->n_alleles) HIPCHK(h, hipMemsetAsync(h->d_acc64, 0, (u64)h->n_alleles * 8, h->stream));      // (zero after every complete submission already: k_accumulate; this is for one that was cut short)
     if (h->rn.d_ctr) HIPCHK(h, hipMemsetAsync(h->rn.d_ctr, 0, sizeof(RnCtr), h->stream));      // the name arena is empty; the switch stays
+    if (h->rp.d_ctr) HIPCHK(h, hipMemsetAsync(h->rp.d_ctr, 0, sizeof(RpCtr), h->stream));      // mlst_set_read_prep: the counters are the sample's; the setting stays
     h->reads_seen = 0; h->fq_carry_len = 0; h->max_wpr = 0;
     h->last_pack.n_reads = 0; h->last_pack.wpr = h->last_pack.qstride = 0;
     for (u64& x : h->tile.info) x = 0;
@@ -4664,6 +4672,7 @@ static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* 
 extern "C" int mlst_submit_packed_device(mlst_handle* h, const uint32_t* d_packed, const uint8_t* d_qrows, const uint16_t* d_lens,
                                          uint64_t n_reads, uint32_t wpr, uint32_t qstride, int paired) {
     { int rc_ = rn_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
+    { int rc_ = rp_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     return submit_impl(h, d_packed, d_qrows, d_lens, n_reads, wpr, qstride, paired, 0);
 }
 static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* d_qrows, const uint16_t* d_lens,
@@ -4811,6 +4820,7 @@ extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, 
                                         uint64_t n_reads, uint32_t max_len, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = rn_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
+    { int rc_ = rp_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     hipSetDevice(h->device);
@@ -4827,6 +4837,7 @@ extern "C" int mlst_submit_reads(mlst_handle* h, const uint8_t* bases, const uin
                                  uint64_t n_reads, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = rn_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
+    { int rc_ = rp_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (n_reads == 0) return MLST_OK;
@@ -4876,6 +4887,23 @@ static int rn_ensure(mlst_handle* h) {
 // with the switch on, reads come from FASTQ text only: every other way of adding reads is refused
 static int rn_refuse(mlst_handle* h, const char* entry) {
     if (h && h->rn.on) return fail(h, MLST_E_INVALID, "%s: read names are on (mlst_set_read_names) and only the FASTQ text and BGZF entries carry names", entry);
+    return MLST_OK;
+}
+// mlst_set_read_prep (csrc/read_prep.h): with the switch on, reads come from FASTQ text only, where they are prepared
+static int rp_refuse(mlst_handle* h, const char* entry) {
+    if (h && h->rp.on) return fail(h, MLST_E_INVALID, "%s: read preparation is on (mlst_set_read_prep) and only the FASTQ text and BGZF entries apply it", entry);
+    return MLST_OK;
+}
+// the parser has left offsets and lengths of n_reads reads of h->d_fq_text and the longest length in flags[0]: the trims, queued in
+// front of the read-back of the flags, so that the longest length the host reads is the longest prepared one (no synchronisation added)
+static int rp_apply(mlst_handle* h, u64 n_reads, u32* d_flags) {
+    const RpSet& P = h->rp.set;
+    if (!h->rp.on || !(P.trim5 | P.trim3 | P.trim_qual)) return MLST_OK;      // (the Phred base alone is k_pack_text's)
+    if (!h->rp.d_ctr) { HIPCHK(h, dmalloc(&h->rp.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->rp.d_ctr, 0, sizeof(RpCtr), h->stream)); }
+    HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
+    Prof pf(h, 18);      // (mlst_get_kernel_time 18: k_rp_qtrim alone)
+    hipLaunchKernelGGL(k_rp_qtrim, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, h->d_fq_soff, h->d_fq_qoff, h->d_lens, n_reads, P,
+                       d_flags, h->rp.d_ctr);
     return MLST_OK;
 }
 // the counters of the name arena; an arena that was too small is reported here (the next entry that looks)
@@ -4949,6 +4977,7 @@ static int fastq_pipeline(mlst_handle* h, u64 n_bytes, int paired, bool whole, u
                                  h->d_fq_soff, h->d_fq_qoff, h->d_lens, d_flags, pair_k, h->tile.read_len);
     else hipLaunchKernelGGL(k_fq_records<false>, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, h->d_fq_text, (u64)n_bytes, h->d_fq_lines, n_lines, n_reads,
                             h->d_fq_soff, h->d_fq_qoff, h->d_lens, d_flags, pair_k, 0u);
+    rc = rp_apply(h, n_reads, d_flags); if (rc) return rc;      // mlst_set_read_prep (never with a tile)
     u32 flags[2] = {0, 0};
     HIPCHK(h, hipMemcpyAsync(flags, d_flags, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -4978,12 +5007,15 @@ static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, i
             HIPCHK(h, hipMemcpyAsync(h->d_lens, keep.data(), n_reads * 2, hipMemcpyHostToDevice, h->stream)); HIPCHK(h, hipStreamSynchronize(h->stream));
         }
     }
-    hipLaunchKernelGGL(k_pack_text, dim3(grid_for((n_reads + 63) / 64, 1, 8192)), dim3(256), 0, h->stream, h->d_fq_text, h->d_fq_soff, h->d_fq_qoff,
+    if (h->rp.set.phred_base == 64) hipLaunchKernelGGL(k_pack_text<64>, dim3(grid_for((n_reads + 63) / 64, 1, 8192)), dim3(256), 0, h->stream, h->d_fq_text, h->d_fq_soff, h->d_fq_qoff,
+                                                       h->d_lens, n_reads, h->d_packed, h->d_qrows, wpr, qstride);      // mlst_set_read_prep: a Phred+64 text
+    else hipLaunchKernelGGL(k_pack_text<33>, dim3(grid_for((n_reads + 63) / 64, 1, 8192)), dim3(256), 0, h->stream, h->d_fq_text, h->d_fq_soff, h->d_fq_qoff,
                        h->d_lens, n_reads, h->d_packed, h->d_qrows, wpr, qstride);
     HIPCHK(h, hipGetLastError());
     if (!h->rn.on) HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
     if (n_reads_out) *n_reads_out = n_reads;
     h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
+    if (!h->rn.on && h->rp.on) return submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);      // (the public entry refuses under mlst_set_read_prep)
     if (!h->rn.on) return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired);
     // mlst_set_read_names: the text outlives pass 1 of its chunk -- the names of the reads it retained are copied out of the header
     // lines (csrc/read_names.h), behind the submission and outside its captured graph, and only then is the slot released
@@ -5051,7 +5083,7 @@ static int fq_tile_submit(mlst_handle* h, u64 n_bytes, u64 n_lines, u64 n_recs, 
         { Prof pf(h, 14);
           hipLaunchKernelGGL(k_fqt_emit, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const FqtDev*)T.d_desc, w0, w0 + n, T.d_soff, T.d_qoff, h->d_lens); }
         { Prof pf(h, 6);
-          hipLaunchKernelGGL(k_pack_text, dim3(grid_for((n + 63) / 64, 1, 8192)), dim3(256), 0, h->stream, h->d_fq_text, (const u64*)T.d_soff, (const u64*)T.d_qoff,
+          hipLaunchKernelGGL(k_pack_text<33>, dim3(grid_for((n + 63) / 64, 1, 8192)), dim3(256), 0, h->stream, h->d_fq_text, (const u64*)T.d_soff, (const u64*)T.d_qoff,
                              h->d_lens, n, h->d_packed, h->d_qrows, wpr, qstride); }
         HIPCHK(h, hipGetLastError());
         if (w0 + n == total) HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
@@ -5139,6 +5171,7 @@ extern "C" int mlst_submit_packed_host(mlst_handle* h, const uint32_t* packed, c
                                        uint32_t wpr, uint32_t qstride, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = rn_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
+    { int rc_ = rp_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (!packed || !qrows || !lens) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -5639,6 +5672,7 @@ static int bzp_finish_impl(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
         int rc = ensure_pack_buffers(h, n_reads, 2, 8); if (rc) return rc;
         hipLaunchKernelGGL(k_fq_pair_records, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)slot, (const u64*)lines1, (const u64*)lines2, k,
                            h->d_fq_soff, h->d_fq_qoff, h->d_lens, reinterpret_cast<u32*>(h->d_pr_meta + 1), h->d_pr_meta + 2);
+        rc = rp_apply(h, n_reads, reinterpret_cast<u32*>(h->d_pr_meta + 1)); if (rc) return rc;      // mlst_set_read_prep
         u64 back[3] = {0, 0, 0};      // flags, then the two cuts
         HIPCHK(h, hipMemcpyAsync(back, h->d_pr_meta + 1, 24, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -6466,6 +6500,7 @@ static int bamr_tile_submit(mlst_handle* h, BamSlot& S, const u32* rd_rec, const
 extern "C" int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip_bytes, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = rn_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
+    { int rc_ = rp_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6510,6 +6545,7 @@ extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n
                                  uint64_t* n_contigs_out, uint64_t* n_reads_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = rn_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
+    { int rc_ = rp_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6603,7 +6639,7 @@ extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n
     {
         Prof pf(h, 6);
         hipLaunchKernelGGL(k_fa_reads, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const FaDev*)F.d_desc, n_reads, read_len, stride, h->d_fq_soff, h->d_fq_qoff, h->d_lens);
-        hipLaunchKernelGGL(k_pack_text, dim3(grid_for((n_reads + 63) / 64, 1, 8192)), dim3(256), 0, h->stream, (const u8*)F.d_flat, (const u64*)h->d_fq_soff, (const u64*)h->d_fq_qoff,
+        hipLaunchKernelGGL(k_pack_text<33>, dim3(grid_for((n_reads + 63) / 64, 1, 8192)), dim3(256), 0, h->stream, (const u8*)F.d_flat, (const u64*)h->d_fq_soff, (const u64*)h->d_fq_qoff,
                            h->d_lens, n_reads, h->d_packed, h->d_qrows, wpr, qstride);
     }
     HIPCHK(h, hipGetLastError());
@@ -6680,6 +6716,7 @@ extern "C" int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t 
     if ((read_len == 0) != (stride == 0)) return fail(h, MLST_E_INVALID, "read_len and stride must both be positive (or both 0: no tiling)");
     if (read_len > (u32)MLST_MAX_READ_LEN) return fail(h, MLST_E_LIMIT, "read_len %u exceeds %d bases", read_len, MLST_MAX_READ_LEN);
     if (read_len) { int rc_ = rn_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window has no name)
+    if (read_len) { int rc_ = rp_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window is cut from the record as it stands)
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
     // (a reads stream took its tile when it was opened: include/mlst.h gives one message for every stream of reads)
     if (bam_is_open(h) && h->bam->reads) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (the reads stream of a BAM: its last chunk was not marked final)");
@@ -6708,6 +6745,41 @@ extern "C" int mlst_set_read_names(mlst_handle* h, int on) {
     if ((on != 0) != h->rn.on && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_names changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
     if (on && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_tiling is on: a window has no name");
     h->rn.on = on != 0;
+    return MLST_OK;
+}
+// reads prepared before they are packed (include/mlst.h; csrc/read_prep.h): like the names, the setting may change only while the sample
+// holds no reads and no stream is open -- one sample is prepared one way
+extern "C" int mlst_set_read_prep(mlst_handle* h, const mlst_read_prep* p) {
+    if (!h) return MLST_E_INVALID;
+    const RpSet want = p ? RpSet{p->trim5, p->trim3, p->trim_qual, p->phred_base} : RpSet{0, 0, 0, 33};
+    if (want.phred_base != 33 && want.phred_base != 64) return fail(h, MLST_E_INVALID, "mlst_set_read_prep: phred_base is %u, not 33 or 64", want.phred_base);
+    if (want.trim_qual > 93) return fail(h, MLST_E_INVALID, "mlst_set_read_prep: trim_qual %u exceeds 93", want.trim_qual);
+    if (want.trim5 > 65535 || want.trim3 > 65535) return fail(h, MLST_E_INVALID, "mlst_set_read_prep: a trim exceeds 65535 bases");
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
+    const RpSet& cur = h->rp.set;
+    const bool same = want.trim5 == cur.trim5 && want.trim3 == cur.trim3 && want.trim_qual == cur.trim_qual && want.phred_base == cur.phred_base;
+    if (!same && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_prep changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
+    const bool on = (want.trim5 | want.trim3 | want.trim_qual) != 0 || want.phred_base != 33;
+    if (on && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_prep: mlst_set_read_tiling is on and a window is cut from the record as it stands");
+    h->rp.set = want; h->rp.on = on;
+    return MLST_OK;
+}
+extern "C" int mlst_get_read_prep(mlst_handle* h, mlst_read_prep* out) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    out->trim5 = h->rp.set.trim5; out->trim3 = h->rp.set.trim3; out->trim_qual = h->rp.set.trim_qual; out->phred_base = h->rp.set.phred_base;
+    return MLST_OK;
+}
+extern "C" int mlst_read_prep_info(mlst_handle* h, uint64_t out[4]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
+    RpCtr c; memset(&c, 0, sizeof c);
+    if (h->rp.on && h->rp.d_ctr) {
+        HIPCHK(h, hipMemcpyAsync(&c, h->rp.d_ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    out[0] = c.shortened; out[1] = c.removed; out[2] = c.emptied; out[3] = 0;
     return MLST_OK;
 }
 // MD:Z in the text export (include/mlst.h): no part of the sample's state; mlst_alignments_text_open reads it

@@ -168,6 +168,9 @@ def load_library(path: str | None = None):
         "mlst_get_read_tiling_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_set_read_names": (C.c_int, [H, C.c_int]),
         "mlst_get_read_names": (C.c_int, [H, C.POINTER(C.c_int)]),
+        "mlst_set_read_prep": (C.c_int, [H, C.POINTER(C.c_uint32)]),      # (mlst_read_prep: four uint32_t)
+        "mlst_get_read_prep": (C.c_int, [H, C.POINTER(C.c_uint32)]),
+        "mlst_read_prep_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_set_export_md": (C.c_int, [H, C.c_int]),
         "mlst_get_export_md": (C.c_int, [H, C.POINTER(C.c_int)]),
         "mlst_read_names_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
@@ -818,6 +821,29 @@ class Engine:
                                                    data.ctypes.data_as(C.POINTER(C.c_uint8))), "mlst_read_names_fetch")
         raw = data.tobytes()
         return {int(ridx[i]): raw[int(off[i]):int(off[i + 1])] for i in range(n)}
+
+    def set_read_prep(self, trim5: int = 0, trim3: int = 0, trim_qual: int = 0, phred64: bool = False) -> None:
+        """Prepare every read of FASTQ text on the GPU before it is packed (mlst_set_read_prep; off by default; the rule:
+        fastq.prep_fastq): Phred base 64, bowtie2's fixed trims -5 / -3, then a 3' quality trim (cutadapt -q).  The engine then behaves
+        as if it had been given prep_fastq's text.  FASTQ text and BGZF entries only -- every other way of adding reads is refused
+        while it is on; may change only while the sample holds no reads and no stream is open.  All defaults: off."""
+        for v in (trim5, trim3, trim_qual):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("set_read_prep: %r is no unsigned 32-bit value" % (v,))
+        p = (C.c_uint32 * 4)(int(trim5), int(trim3), int(trim_qual), 64 if phred64 else 33)
+        self._check(self.lib.mlst_set_read_prep(self._h, p), "mlst_set_read_prep")
+
+    def get_read_prep(self) -> dict:
+        p = (C.c_uint32 * 4)()
+        self._check(self.lib.mlst_get_read_prep(self._h, p), "mlst_get_read_prep")
+        return {"trim5": int(p[0]), "trim3": int(p[1]), "trim_qual": int(p[2]), "phred64": int(p[3]) == 64}
+
+    def read_prep_info(self) -> dict:
+        """Since the last reset_sample: reads whose length changed, bases removed, reads of length >= 1 left without a base.  All zero
+        with the switch off."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.mlst_read_prep_info(self._h, out), "mlst_read_prep_info")
+        return {"shortened": int(out[0]), "bases_removed": int(out[1]), "emptied": int(out[2])}
 
     def set_export_md(self, on: bool = True) -> None:
         """export_sam_text / write_sam_all write bowtie2's MD:Z field between NM:i and YT:Z, formatted on the GPU (mlst_set_export_md; off

@@ -715,6 +715,62 @@ def tile_fastq(path: str, read_len: int = 150, stride: int = 25, chunk_reads: in
         yield b"".join(out)
 
 
+def qtrim_len(q, T: int) -> int:
+    """The 3' quality trim on Phred values q (cutadapt -q T / bwa aln -q T, no minimum length): how many values remain.  The sum of
+    T - q[i] is walked from the last value down; the walk ends at the first negative sum; the cut is where the sum first reached its
+    largest value (an equal sum further down does not move it).  T = 0: nothing is trimmed."""
+    n = len(q)
+    if T <= 0:
+        return n
+    s = best = 0
+    cut = n
+    for i in range(n - 1, -1, -1):
+        s += T - q[i]
+        if s < 0:
+            break
+        if s > best:
+            best, cut = s, i
+    return cut
+
+
+def prep_fastq(text: bytes, trim5: int = 0, trim3: int = 0, trim_qual: int = 0, phred64: bool = False) -> tuple[bytes, dict]:
+    """The FASTQ text the engine behaves as if it had been given under Engine.set_read_prep(trim5, trim3, trim_qual, phred64), and
+    the counters of Engine.read_prep_info().  This is the rule mlst_set_read_prep applies on the device (csrc/read_prep.h); it serves
+    the tests and whoever wants the prepared file -- the command never calls it.  Per record, header and '+' line untouched, line
+    ends LF, in this order:
+      1. Phred: q[i] = clamp(character - base, 0, 127), base 64 under phred64, else 33; written back as the character q[i] + 33.
+      2. Fixed trims (bowtie2 -5 / -3): a = min(trim5, n), n1 = max(0, n - trim5 - trim3); bases and qualities [a, a + n1) remain.
+      3. qtrim_len(q[a : a + n1], trim_qual) of them remain.
+      4. A read left without a base stays a record with an empty sequence and an empty quality line.
+    Each mate of a pair is prepared on its own (prepare each file).  Counters: shortened (reads whose length changed),
+    bases_removed, emptied (reads of length >= 1 that end with no base)."""
+    if trim5 < 0 or trim3 < 0 or trim_qual < 0:
+        raise ValueError("trims must not be negative")
+    base = 64 if phred64 else 33
+    lines = bytes(text).split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    if len(lines) % 4:
+        raise ValueError("FASTQ text holds %d lines: not a whole number of 4-line records" % len(lines))
+    out = []
+    info = {"shortened": 0, "bases_removed": 0, "emptied": 0}
+    for k in range(0, len(lines), 4):
+        h, s, p, ql = (x[:-1] if x.endswith(b"\r") else x for x in lines[k:k + 4])
+        if len(s) != len(ql):
+            raise ValueError("FASTQ record with different sequence and quality lengths: %r" % h[:60])
+        n = len(s)
+        q = [min(max(c - base, 0), 127) for c in ql]
+        a = min(trim5, n)
+        n1 = max(0, n - trim5 - trim3)
+        n2 = qtrim_len(q[a:a + n1], trim_qual)
+        if n2 != n:
+            info["shortened"] += 1
+            info["bases_removed"] += n - n2
+            info["emptied"] += n2 == 0
+        out.append(b"%s\n%s\n%s\n%s\n" % (h, s[a:a + n2], p, bytes(v + 33 for v in q[a:a + n2])))
+    return b"".join(out), info
+
+
 def _bgzf_block_size(buf, off: int) -> int:
     """Total size of the BGZF block that starts at buf[off], 0 if the header is incomplete, -1 if it is not BGZF."""
     if len(buf) - off < 18:

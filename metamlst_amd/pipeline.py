@@ -171,10 +171,12 @@ class TypingPipeline:
             e.close()
 
 
-def make_engines(idx, device: int = 0, depth: int = 4, params=None) -> list:
-    """`depth` engines on one device with `idx` loaded."""
+def make_engines(idx, device: int = 0, depth: int = 4, params=None, read_prep: dict | None = None) -> list:
+    """`depth` engines on one device with `idx` loaded.  read_prep: the arguments of Engine.set_read_prep, set on every engine."""
     from .engine import Engine
     engines = [Engine(device, params) for _ in range(depth)]
     for e in engines:
+        if read_prep:
+            e.set_read_prep(**read_prep)
         e.load_reference(idx)
     return engines
