@@ -456,6 +456,38 @@ int mlst_set_read_prep(mlst_handle* h, const mlst_read_prep* p);
 int mlst_get_read_prep(mlst_handle* h, mlst_read_prep* out);
 int mlst_read_prep_info(mlst_handle* h, uint64_t out[4]);
 
+/* ---- 3' adapters removed before the reads are aligned (off by default; csrc/read_adapt.h; `cli type --adapter`) -------------------------
+ * mlst_set_read_adapters(h, "SEQ[,SEQ...]", min_overlap, error_permille): a 3' adapter is removed from every read of FASTQ text on the
+ *   device before it is packed; the engine then behaves as if it had been given the cut text (metamlst_amd.fastq.adapter_cut /
+ *   trim_adapters state the rule in Python and write that text).  NULL or "" is off: nothing is queued, nothing is allocated, and the
+ *   kernels that run are those that ran before the switch existed.
+ * The rule is the project's own, modelled on `cutadapt -a ADAPTER --no-indels --times 1`; it does not claim cutadapt's bytes.  For a
+ *   read of n bases and the adapters A_0 .. A_{K-1} (1 <= K <= 8; A_k: m_k letters of ACGTN, 1 <= m_k <= 64, at least one not N;
+ *   either case, kept upper-cased):
+ *   1. A candidate is an adapter k and a start p, 0 <= p <= n - min(min_overlap, m_k).  Its overlap is L = min(m_k, n - p): the
+ *      adapter lies inside the read or hangs over its 3' end, never over the 5' end.
+ *   2. Position i < L matches if A_k[i] is N, or if the read's byte at p + i, upper-cased, equals A_k[i] -- a non-ACGT byte of the
+ *      read, N included, matches only an adapter N.  mism = L - matches.
+ *   3. The candidate is valid if mism <= (L * error_permille) / 1000, in integers.
+ *   4. The cut is the valid candidate with the most matches; among equals the smallest p, then the smallest k.  Bases and qualities
+ *      [0, p) remain.  With no valid candidate the read is untouched.  One adapter is removed per read.
+ *   5. It runs behind mlst_set_read_prep's steps (Phred base, fixed trims, quality trim -- cutadapt trims by quality first), on what
+ *      they left.  A read left without a base stays a read of length 0; read indices, pairing and the names of mlst_set_read_names are
+ *      those of the file.  Each mate of a pair is cut on its own, against the same adapters.
+ *   At min_overlap 3 (cutadapt's default) about 2 % of random reads lose three or more bases by chance.
+ * Entries it applies to, the entries refused while it is on ("<entry>: adapter removal is on (mlst_set_read_adapters) ...") and when
+ *   the setting may change: exactly as for mlst_set_read_prep, with which it combines, as it does with mlst_set_read_names and the
+ *   exports (they carry the cut SEQ / QUAL).  A letter outside ACGTN, an empty adapter or one of only Ns, more than 8 adapters, one
+ *   longer than 64 letters, min_overlap outside 1..64, error_permille above 500: MLST_E_INVALID with the reason.  mlst_reset_sample
+ *   zeroes the counters and keeps the setting.
+ * mlst_get_read_adapters: the adapters as set, upper-cased and comma-separated, into adapters[cap] (NULL: not wanted; "" when off; at
+ *   most 8 * 65 bytes with the final 0), and the two numbers (0, 0 when off).
+ * mlst_get_read_adapters_info: out[0] = reads cut, out[1] = bases removed, out[2] = reads of length >= 1 cut at 0, out[3] = K,
+ *   out[4 + k] = reads cut at adapter k.  The counters are separate from mlst_read_prep_info's.  An open BGZF piece is finished first. */
+int mlst_set_read_adapters(mlst_handle* h, const char* adapters, uint32_t min_overlap, uint32_t error_permille);
+int mlst_get_read_adapters(mlst_handle* h, char* adapters, uint64_t cap, uint32_t* min_overlap, uint32_t* error_permille);
+int mlst_get_read_adapters_info(mlst_handle* h, uint64_t out[12]);
+
 /* ---- bowtie2's MD:Z field in the text export (off by default; csrc/aln_text.h; `cli type --md`) --------------------------------------
  * mlst_set_export_md(h, 1): every record of mlst_alignments_text_* carries MD:Z:<text> between NM:i and YT:Z:UU, bowtie2's place;
  *   columns 1-11 and every other field are the bytes they are without it.  With the switch off the export writes what it wrote
@@ -743,7 +775,8 @@ int mlst_set_profiling(mlst_handle* h, int on);   /* 0 = off, 1 = events + sieve
  * which: 0=sieve (all its kernels) 1=seed 2=extend (k_extend + k_extend_pairs) 3=banded-SW 4=accumulate 5=pileup 6=pack 12=k_ext_prep (the item records of k_extend);
  * 13 = k_fqt_count (a BAM piece: k_bamt_count) + k_fqt_scan + k_fqt_add and 14 = k_fqt_emit (k_bamt_emit) (long reads cut into windows,
  * csrc/fastq_tile.h, csrc/bam_tile.h; outside 6); 15 = the line table of a SAM chunk (k_fq_count, k_fq_scan, k_fq_lines, k_sam_flags), 16 =
- * k_sam_accumulate and 17 = k_sam_pileup (csrc/sam_dev.h; two entries of 15 per chunk); 9 = k_route, 10 =
+ * k_sam_accumulate and 17 = k_sam_pileup (csrc/sam_dev.h; two entries of 15 per chunk); 18 = k_rp_qtrim (csrc/read_prep.h) and 19 = k_ra_cut
+ * (csrc/read_adapt.h), each alone (inside 6); 9 = k_route, 10 =
  * k_route_probe and 11 = k_route_verify, the three kernels of the routed sieve (inside 0) (events bracket the launch on the engine's
  * stream, so with several engines on one GPU they include the time a kernel queues behind another stream's kernel);
  * 7 = the sieve's execution window measured inside the kernel (wall clock at the first workgroup's start and the last

@@ -120,6 +120,21 @@ def _type_parser(sub):
     p.add_argument("--phred64", action="store_true",
                    help="FASTQ input: the qualities are Phred+64 (Illumina 1.3 - 1.7, bowtie2 --phred64), not Phred+33.  Nothing detects "
                         "the base: without the flag such a file is typed with every quality 31 too high; see --trim5")
+    p.add_argument("--adapter", default="", metavar="SEQ[,SEQ...]",
+                   help="FASTQ input: remove a 3' adapter from every read before it is aligned, on the GPU (csrc/read_adapt.h; the rule: "
+                        "metamlst_amd.fastq.adapter_cut, modelled on `cutadapt -a SEQ --no-indels`; it is the project's own and claims none "
+                        "of cutadapt's bytes).  1 to 8 adapters of 1 to 64 letters of ACGTN; illumina (AGATCGGAAGAGC), nextera (CTGTCTCTTATA) "
+                        "and smallrna (TGGAATTCTCGG) are taken in place of a sequence.  The adapter may lie inside the read or hang over "
+                        "its 3' end; the start with the most matching letters within the error rate is cut, one adapter per read, each "
+                        "mate on its own, behind --trim5 / --trim3 / --trim-qual.  Accepted and refused where those flags are; a read left "
+                        "without a base stays a read, and the exports carry the cut SEQ / QUAL.  At the default minimum overlap of 3 about "
+                        "2 %% of random 150-base reads lose three or more bases by chance (cutadapt's default and its known price): raise "
+                        "--adapter-min-overlap where that matters")
+    p.add_argument("--adapter-min-overlap", dest="adapter_min_overlap", default=None, type=int, metavar="N",
+                   help="--adapter: an adapter that hangs over the 3' end must lie on at least N bases of the read (1 to 64, default 3)")
+    p.add_argument("--adapter-error-rate", dest="adapter_error_rate", default=None, type=float, metavar="X",
+                   help="--adapter: at most floor(X * overlap) letters of the overlap may differ (0 to 0.5, default 0.1; kept as "
+                        "round(1000 * X) permille)")
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -269,6 +284,19 @@ def run_type(a, argv=None) -> int:
             if on:
                 print("read preparation (--trim5, --trim3, --trim-qual, --phred64): " + why)
                 return 1
+    adapters = _adapters_of(a)
+    if adapters is not None:      # (refused before any GPU use, each with its reason)
+        if adapters is False:
+            return 1
+        for on, why in ((a.alignments, "with --alignments the records are what they are: the file holds alignments, not reads to cut"),
+                        (a.contigs, "--contigs cuts assemblies into windows, and an assembly carries no adapter"),
+                        (a.long_reads, "--long-reads cuts reads into windows, and a window is cut from the record as it stands"),
+                        (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and a window is cut from the record as it stands"),
+                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp),
+                         "the reads of a BAM are taken as they are stored: FASTQ input only")):
+            if on:
+                print("--adapter: " + why)
+                return 1
     if a.md and not (a.write_sam or a.write_sam_all):      # (with an export flag it is accepted and refused where that flag is: below)
         print("--md: it adds MD:Z to the records of an export: give --write-sam or --write-sam-all")
         return 1
@@ -335,6 +363,8 @@ def run_type(a, argv=None) -> int:
         eng.set_read_names(True)
     if read_prep:      # (the same entries: the reads are prepared where the text is parsed; before a rank's first read index base)
         eng.set_read_prep(**read_prep)
+    if adapters:       # (likewise)
+        eng.set_read_adapters(**adapters)
     # the built host index is kept next to the database (as the reference keeps <idx>.1.bt2: metamlst-index.py:224-225) unless a
     # species filter made this index a one-off or MLST_INDEX_CACHE=0
     ref_cache = (a.database + ".mlstref") if (not a.filter and os.environ.get("MLST_INDEX_CACHE", "1") != "0") else ""
@@ -358,6 +388,8 @@ def run_type(a, argv=None) -> int:
                 e2.set_read_tiling(*(long_reads or long_bam))
             if read_prep:
                 e2.set_read_prep(**read_prep)
+            if adapters:
+                e2.set_read_adapters(**adapters)
             if a.depth_cap:
                 e2.set_depth_cap(a.depth_cap)
             engines.append(e2)
@@ -367,11 +399,14 @@ def run_type(a, argv=None) -> int:
     if many:
         from .multigpu import type_many_samples
         prep_info = {"shortened": 0, "bases_removed": 0, "emptied": 0} if read_prep and not a.quiet else None
+        adapt_info = {"trimmed": 0, "bases_removed": 0, "emptied": 0, "per_adapter": [0] * len(adapters["adapters"])} if adapters and not a.quiet else None
         rc = type_many_samples(engines, idx, database, targs, samples, rank, world, a.o, a.log, chunk_bytes,
                                printer=None if a.quiet else (lambda results: _print_results(a, results)), tile=tile, long_reads=long_reads,
-                               long_bam_reads=long_bam, read_prep_info=prep_info)
+                               long_bam_reads=long_bam, read_prep_info=prep_info, read_adapters_info=adapt_info)
         if prep_info is not None:
             _say_read_prep(prep_info, world)
+        if adapt_info is not None:
+            _say_read_adapters(adapt_info, adapters["adapters"], world)
         database.closeConnection()
         return rc
     if a.alignments:
@@ -432,6 +467,11 @@ def run_type(a, argv=None) -> int:
             dist.all_gather_object(box, eng.read_prep_info())
             if rank == 0 and not a.quiet:
                 _say_read_prep({key: sum(b[key] for b in box) for key in box[0]}, 1)
+        if adapters:
+            box = [None] * world
+            dist.all_gather_object(box, eng.read_adapters_info())
+            if rank == 0 and not a.quiet:
+                _say_read_adapters(_sum_adapter_infos(box), adapters["adapters"], 1)
         dist.destroy_process_group()
         return 0
     # FASTQ text goes to the GPU as is and is parsed there (mlst_submit_fastq); a reader thread stays two chunks ahead
@@ -457,6 +497,8 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
     rc = _finish_type(a, idx, database, targs, st, None, typed=(chosen, letters))
     if rc == 0 and not a.quiet and _read_prep_of(a):
         _say_read_prep(eng.read_prep_info(), 1)
+    if rc == 0 and not a.quiet and _adapters_of(a, say=False):
+        _say_read_adapters(eng.read_adapters_info(), eng.get_read_adapters()["adapters"], 1)
     names, md = None, bool(getattr(a, "md", False))      # --md: MD:Z in both exports (write_sam on the host, the full export on the device)
     if rc == 0 and getattr(a, "read_names", False):      # the engine knows its switch: the text export needs no more than that
         names = eng.read_names()
@@ -492,6 +534,49 @@ def _say_read_prep(info: dict, world: int) -> None:
     n, m, k = info["shortened"], info["bases_removed"], info["emptied"]
     rank = (" (the samples of rank %s of %d)" % (os.environ.get("RANK", "0"), world)) if world > 1 else ""
     print("read preparation: %d reads shortened, %d bases removed, %d reads left without a base%s" % (n, m, k, rank), flush=True)
+
+
+def _adapters_of(a, say: bool = True):
+    """--adapter, --adapter-min-overlap, --adapter-error-rate -> the arguments of Engine.set_read_adapters, None when --adapter is not
+    given, False (said) when a flag is out of range or given without --adapter"""
+    from .fastq import ADAPTER_NAMES, check_adapters
+    spec, mo, er = getattr(a, "adapter", ""), getattr(a, "adapter_min_overlap", None), getattr(a, "adapter_error_rate", None)
+    if not spec:
+        for flag, v in (("--adapter-min-overlap", mo), ("--adapter-error-rate", er)):
+            if v is not None:
+                if say:
+                    print(flag + " belongs to --adapter: give the adapter it applies to")
+                return False
+        return None
+    try:
+        if er is not None and not 0 <= er <= 0.5:
+            raise ValueError("--adapter-error-rate takes a number from 0 to 0.5, not %r" % er)
+        permille = 100 if er is None else int(round(1000 * er))
+        ads = check_adapters([ADAPTER_NAMES.get(x.strip().lower(), x.strip()) for x in spec.split(",")], 3 if mo is None else mo, permille)
+    except ValueError as e:
+        if say:
+            print("--adapter: %s" % e)
+        return False
+    return {"adapters": [x.decode() for x in ads], "min_overlap": 3 if mo is None else mo, "error_permille": permille}
+
+
+def _sum_adapter_infos(infos) -> dict:
+    """Engine.read_adapters_info() of several engines or ranks, added up"""
+    out = {"trimmed": 0, "bases_removed": 0, "emptied": 0, "per_adapter": [0] * len(infos[0]["per_adapter"])}
+    for b in infos:
+        for key in ("trimmed", "bases_removed", "emptied"):
+            out[key] += b[key]
+        out["per_adapter"] = [x + y for x, y in zip(out["per_adapter"], b["per_adapter"])]
+    return out
+
+
+def _say_read_adapters(info: dict, adapters: list, world: int) -> None:
+    """The line on what --adapter did (info: Engine.read_adapters_info(), summed over the samples of a folder; a rank of --gpus N speaks
+    for its own samples)"""
+    rank = (" (the samples of rank %s of %d)" % (os.environ.get("RANK", "0"), world)) if world > 1 else ""
+    per = ", ".join("%s %d" % (s, n) for s, n in zip(adapters, info["per_adapter"]))
+    print("adapter removal: %d reads cut, %d bases removed, %d reads left without a base (%s)%s"
+          % (info["trimmed"], info["bases_removed"], info["emptied"], per, rank), flush=True)
 
 
 class _FileReader:

@@ -3690,6 +3690,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "aln_export.h"
 #include "read_names.h"
 #include "read_prep.h"
+#include "read_adapt.h"
 #include "aln_text.h"
 
 // ================================================================== host side
@@ -3843,6 +3844,9 @@ struct mlst_handle {
     // reads prepared before they are packed (mlst_set_read_prep; csrc/read_prep.h): the switch (on: the setting is not {0,0,0,33}), the
     // setting, the counters on the device -- allocated by the first submission that trims
     struct { bool on = false; RpSet set = {0, 0, 0, 33}; RpCtr* d_ctr = nullptr; } rp;
+    // 3' adapters removed before the reads are packed (mlst_set_read_adapters; csrc/read_adapt.h): the switch, the adapters as the kernel
+    // takes them and as the caller gave them (upper-cased), the counters on the device -- allocated by the first submission that cuts
+    struct { bool on = false; RaSet set = {}; std::string text; RaCtr* d_ctr = nullptr; } ra;
 };
 
 static std::string g_create_err;
@@ -3862,6 +3866,7 @@ static void bam_drop(mlst_handle* h, bool release);      // the BAM stream is cl
 static bool bam_is_open(const mlst_handle* h);
 static int rn_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_names is on: an entry that carries no names is refused
 static int rp_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_prep is on: an entry that does not prepare its reads is refused
+static int ra_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_adapters is on: an entry that does not cut its reads is refused
 static void at_free(mlst_handle* h);      // the per-export tables of mlst_alignments_text_*
 static const char* bam_kind(const mlst_handle* h);      // "BAM" or "SAM": what the open stream of ready-made alignments takes
 template <typename T> static hipError_t dmalloc(T** p, u64 n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
@@ -4032,7 +4037,7 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     if (h->copy_stream) hipStreamDestroy(h->copy_stream);
     hipFree(h->d_cand); hipFree(h->d_in_bases); hipFree(h->d_in_quals); hipFree(h->d_in_off);
     hipFree(h->d_fq_slot[0]); hipFree(h->d_fq_slot[1]); hipFree(h->d_fq_nl[0]); hipFree(h->d_fq_nl[1]); hipFree(h->d_fq_blk); hipFree(h->d_fq_lines); hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); hipFree(h->d_fq_meta);
-    hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta); hipFree(h->rp.d_ctr);
+    hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta); hipFree(h->rp.d_ctr); hipFree(h->ra.d_ctr);
     hipFree(h->fa.d_desc); hipFree(h->fa.d_meta); hipFree(h->fa.d_flat); hipFree(h->fa.d_kind); hipFree(h->fa.d_cseq); hipFree(h->fa.d_chdr); hipFree(h->fa.d_cstart); hipFree(h->fa.d_wcnt);
     if (h->fa.h_fa) hipHostFree(h->fa.h_fa);
     hipFree(h->tile.d_desc); hipFree(h->tile.d_meta); hipFree(h->tile.d_rlen); hipFree(h->tile.d_wex); hipFree(h->tile.d_gsum); hipFree(h->tile.d_soff); hipFree(h->tile.d_qoff);
@@ -4059,6 +4064,7 @@ static int reset_sample_state(mlst_handle* h) {
     if (h->d_acc64 && h->n_alleles) HIPCHK(h, hipMemsetAsync(h->d_acc64, 0, (u64)h->n_alleles * 8, h->stream));      // (zero after every complete submission already: k_accumulate; this is for one that was cut short)
     if (h->rn.d_ctr) HIPCHK(h, hipMemsetAsync(h->rn.d_ctr, 0, sizeof(RnCtr), h->stream));      // the name arena is empty; the switch stays
     if (h->rp.d_ctr) HIPCHK(h, hipMemsetAsync(h->rp.d_ctr, 0, sizeof(RpCtr), h->stream));      // mlst_set_read_prep: the counters are the sample's; the setting stays
+    if (h->ra.d_ctr) HIPCHK(h, hipMemsetAsync(h->ra.d_ctr, 0, sizeof(RaCtr), h->stream));      // mlst_set_read_adapters: likewise
     h->reads_seen = 0; h->fq_carry_len = 0; h->max_wpr = 0;
     h->last_pack.n_reads = 0; h->last_pack.wpr = h->last_pack.qstride = 0;
     for (u64& x : h->tile.info) x = 0;
@@ -4673,6 +4679,7 @@ extern "C" int mlst_submit_packed_device(mlst_handle* h, const uint32_t* d_packe
                                          uint64_t n_reads, uint32_t wpr, uint32_t qstride, int paired) {
     { int rc_ = rn_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
+    { int rc_ = ra_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     return submit_impl(h, d_packed, d_qrows, d_lens, n_reads, wpr, qstride, paired, 0);
 }
 static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* d_qrows, const uint16_t* d_lens,
@@ -4821,6 +4828,7 @@ extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, 
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = rn_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
+    { int rc_ = ra_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     hipSetDevice(h->device);
@@ -4838,6 +4846,7 @@ extern "C" int mlst_submit_reads(mlst_handle* h, const uint8_t* bases, const uin
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = rn_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
+    { int rc_ = ra_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (n_reads == 0) return MLST_OK;
@@ -4894,16 +4903,34 @@ static int rp_refuse(mlst_handle* h, const char* entry) {
     if (h && h->rp.on) return fail(h, MLST_E_INVALID, "%s: read preparation is on (mlst_set_read_prep) and only the FASTQ text and BGZF entries apply it", entry);
     return MLST_OK;
 }
+// mlst_set_read_adapters (csrc/read_adapt.h): likewise
+static int ra_refuse(mlst_handle* h, const char* entry) {
+    if (h && h->ra.on) return fail(h, MLST_E_INVALID, "%s: adapter removal is on (mlst_set_read_adapters) and only the FASTQ text and BGZF entries apply it", entry);
+    return MLST_OK;
+}
 // the parser has left offsets and lengths of n_reads reads of h->d_fq_text and the longest length in flags[0]: the trims, queued in
 // front of the read-back of the flags, so that the longest length the host reads is the longest prepared one (no synchronisation added)
+// Behind them, mlst_set_read_adapters' cut (csrc/read_adapt.h): flags[0] is zeroed in front of either kernel, so the last one alone feeds what is read
 static int rp_apply(mlst_handle* h, u64 n_reads, u32* d_flags) {
     const RpSet& P = h->rp.set;
-    if (!h->rp.on || !(P.trim5 | P.trim3 | P.trim_qual)) return MLST_OK;      // (the Phred base alone is k_pack_text's)
-    if (!h->rp.d_ctr) { HIPCHK(h, dmalloc(&h->rp.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->rp.d_ctr, 0, sizeof(RpCtr), h->stream)); }
+    const bool trims = h->rp.on && (P.trim5 | P.trim3 | P.trim_qual);      // (the Phred base alone is k_pack_text's)
+    if (!trims && !h->ra.on) return MLST_OK;
+    if (trims && !h->rp.d_ctr) { HIPCHK(h, dmalloc(&h->rp.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->rp.d_ctr, 0, sizeof(RpCtr), h->stream)); }
+    if (h->ra.on && !h->ra.d_ctr) { HIPCHK(h, dmalloc(&h->ra.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->ra.d_ctr, 0, sizeof(RaCtr), h->stream)); }
     HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
-    Prof pf(h, 18);      // (mlst_get_kernel_time 18: k_rp_qtrim alone)
-    hipLaunchKernelGGL(k_rp_qtrim, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, h->d_fq_soff, h->d_fq_qoff, h->d_lens, n_reads, P,
-                       d_flags, h->rp.d_ctr);
+    if (trims) {
+        Prof pf(h, 18);      // (mlst_get_kernel_time 18: k_rp_qtrim alone)
+        hipLaunchKernelGGL(k_rp_qtrim, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, h->d_fq_soff, h->d_fq_qoff, h->d_lens, n_reads, P,
+                           d_flags, h->rp.d_ctr);
+    }
+    // k_rp_qtrim has fed the longest PREPARED length, and an atomicMax with the shorter cut lengths would leave it standing: zeroed again,
+    // so that the longest length the host reads is that of the prepared, cut text
+    if (trims && h->ra.on) HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
+    if (h->ra.on) {
+        Prof pf(h, 19);      // (mlst_get_kernel_time 19: k_ra_cut alone)
+        hipLaunchKernelGGL(k_ra_cut, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, h->d_lens, n_reads, h->ra.set,
+                           d_flags, h->ra.d_ctr);
+    }
     return MLST_OK;
 }
 // the counters of the name arena; an arena that was too small is reported here (the next entry that looks)
@@ -5015,7 +5042,7 @@ static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, i
     if (!h->rn.on) HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
     if (n_reads_out) *n_reads_out = n_reads;
     h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
-    if (!h->rn.on && h->rp.on) return submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);      // (the public entry refuses under mlst_set_read_prep)
+    if (!h->rn.on && (h->rp.on || h->ra.on)) return submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);      // (the public entry refuses under mlst_set_read_prep / mlst_set_read_adapters)
     if (!h->rn.on) return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired);
     // mlst_set_read_names: the text outlives pass 1 of its chunk -- the names of the reads it retained are copied out of the header
     // lines (csrc/read_names.h), behind the submission and outside its captured graph, and only then is the slot released
@@ -5172,6 +5199,7 @@ extern "C" int mlst_submit_packed_host(mlst_handle* h, const uint32_t* packed, c
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = rn_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
+    { int rc_ = ra_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (!packed || !qrows || !lens) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -6501,6 +6529,7 @@ extern "C" int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = rn_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
+    { int rc_ = ra_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6546,6 +6575,7 @@ extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     { int rc_ = rn_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
+    { int rc_ = ra_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6717,6 +6747,7 @@ extern "C" int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t 
     if (read_len > (u32)MLST_MAX_READ_LEN) return fail(h, MLST_E_LIMIT, "read_len %u exceeds %d bases", read_len, MLST_MAX_READ_LEN);
     if (read_len) { int rc_ = rn_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window has no name)
     if (read_len) { int rc_ = rp_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window is cut from the record as it stands)
+    if (read_len) { int rc_ = ra_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
     // (a reads stream took its tile when it was opened: include/mlst.h gives one message for every stream of reads)
     if (bam_is_open(h) && h->bam->reads) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (the reads stream of a BAM: its last chunk was not marked final)");
@@ -6780,6 +6811,68 @@ extern "C" int mlst_read_prep_info(mlst_handle* h, uint64_t out[4]) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     out[0] = c.shortened; out[1] = c.removed; out[2] = c.emptied; out[3] = 0;
+    return MLST_OK;
+}
+// 3' adapters removed before the reads are packed (include/mlst.h; csrc/read_adapt.h): the life cycle is mlst_set_read_prep's
+extern "C" int mlst_set_read_adapters(mlst_handle* h, const char* adapters, uint32_t min_overlap, uint32_t error_permille) {
+    if (!h) return MLST_E_INVALID;
+    RaSet want = {}; std::string text;
+    if (adapters && *adapters) {
+        if (min_overlap < 1 || min_overlap > RA_MAX_LEN) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: min_overlap %u is outside 1..%d", min_overlap, RA_MAX_LEN);
+        if (error_permille > 500) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: error_permille %u exceeds 500", error_permille);
+        want.permille = error_permille; want.min_overlap = min_overlap;
+        for (const char* c = adapters;; c++) {      // letter by letter; ',' or the end closes an adapter
+            if (want.K >= RA_MAX_ADAPTERS) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: more than %d adapters", RA_MAX_ADAPTERS);
+            RaAd& A = want.ad[want.K];
+            if (*c == ',' || !*c) {
+                if (!A.m) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: adapter %u is empty", want.K + 1);
+                if (!(A.care[0] | A.care[1])) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: adapter %u holds only N", want.K + 1);
+                A.mo = min_overlap < A.m ? min_overlap : A.m;
+                want.K++;
+                if (!*c) break;
+                text.push_back(',');
+                continue;
+            }
+            const char up = (char)(*c & 0xDF);
+            const char* at = (up && !(*c & 0x80)) ? strchr("ACGTN", up) : nullptr;
+            if (!at) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: adapter %u holds a letter outside ACGTN (byte 0x%02x)", want.K + 1, (unsigned)(unsigned char)*c);
+            if (A.m >= RA_MAX_LEN) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: adapter %u is longer than %d letters", want.K + 1, RA_MAX_LEN);
+            const u32 w = A.m >> 5, sh = 2 * (A.m & 31);
+            if (up == 'N') A.anyn[w] |= 1ull << sh;
+            else { A.code[w] |= (u64)(at - "ACGTN") << sh; A.care[w] |= 1ull << sh; }
+            A.m++;
+            text.push_back(up);
+        }
+    }
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
+    const bool same = text == h->ra.text && want.permille == h->ra.set.permille && want.min_overlap == h->ra.set.min_overlap;
+    if (!same && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_adapters changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
+    if (want.K && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: mlst_set_read_tiling is on and a window is cut from the record as it stands");
+    h->ra.set = want; h->ra.text = text; h->ra.on = want.K != 0;
+    return MLST_OK;
+}
+extern "C" int mlst_get_read_adapters(mlst_handle* h, char* adapters, uint64_t cap, uint32_t* min_overlap, uint32_t* error_permille) {
+    if (!h) return MLST_E_INVALID;
+    if (adapters) {
+        if (cap < h->ra.text.size() + 1) return fail(h, MLST_E_INVALID, "mlst_get_read_adapters: the buffer holds %llu bytes, %llu are needed", (unsigned long long)cap, (unsigned long long)(h->ra.text.size() + 1));
+        memcpy(adapters, h->ra.text.c_str(), h->ra.text.size() + 1);
+    }
+    if (min_overlap) *min_overlap = h->ra.set.min_overlap;
+    if (error_permille) *error_permille = h->ra.set.permille;
+    return MLST_OK;
+}
+extern "C" int mlst_get_read_adapters_info(mlst_handle* h, uint64_t out[12]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
+    RaCtr c; memset(&c, 0, sizeof c);
+    if (h->ra.on && h->ra.d_ctr) {
+        HIPCHK(h, hipMemcpyAsync(&c, h->ra.d_ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    out[0] = c.trimmed; out[1] = c.removed; out[2] = c.emptied; out[3] = h->ra.set.K;
+    for (int k = 0; k < RA_MAX_ADAPTERS; k++) out[4 + k] = c.per_adapter[k];
     return MLST_OK;
 }
 // MD:Z in the text export (include/mlst.h): no part of the sample's state; mlst_alignments_text_open reads it

@@ -171,6 +171,9 @@ def load_library(path: str | None = None):
         "mlst_set_read_prep": (C.c_int, [H, C.POINTER(C.c_uint32)]),      # (mlst_read_prep: four uint32_t)
         "mlst_get_read_prep": (C.c_int, [H, C.POINTER(C.c_uint32)]),
         "mlst_read_prep_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "mlst_set_read_adapters": (C.c_int, [H, C.c_char_p, C.c_uint32, C.c_uint32]),
+        "mlst_get_read_adapters": (C.c_int, [H, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "mlst_get_read_adapters_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_set_export_md": (C.c_int, [H, C.c_int]),
         "mlst_get_export_md": (C.c_int, [H, C.POINTER(C.c_int)]),
         "mlst_read_names_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
@@ -844,6 +847,39 @@ class Engine:
         out = (C.c_uint64 * 4)()
         self._check(self.lib.mlst_read_prep_info(self._h, out), "mlst_read_prep_info")
         return {"shortened": int(out[0]), "bases_removed": int(out[1]), "emptied": int(out[2])}
+
+    def set_read_adapters(self, adapters=None, min_overlap: int = 3, error_permille: int = 100) -> None:
+        """Remove a 3' adapter from every read of FASTQ text on the GPU before it is packed (mlst_set_read_adapters; off by default;
+        the rule: fastq.adapter_cut, modelled on `cutadapt -a ADAPTER --no-indels`), behind set_read_prep's steps.  The engine then
+        behaves as if it had been given fastq.trim_adapters' text.  adapters: one str / bytes with commas between the adapters or a
+        sequence of them (1 to 8, 1 to 64 letters of ACGTN each); None, "" or an empty sequence: off.  FASTQ text and BGZF entries only
+        -- every other way of adding reads is refused while it is on; may change only while the sample holds no reads and no stream is
+        open."""
+        if adapters is not None and not isinstance(adapters, (str, bytes, bytearray)):
+            adapters = b",".join(a.encode() if isinstance(a, str) else bytes(a) for a in adapters)
+        if isinstance(adapters, str):
+            adapters = adapters.encode()
+        for v in (min_overlap, error_permille):
+            if not 0 <= int(v) < 1 << 32:
+                raise ValueError("set_read_adapters: %r is no unsigned 32-bit value" % (v,))
+        if adapters and b"\0" in bytes(adapters):
+            raise ValueError("set_read_adapters: a zero byte among the adapters")
+        self._check(self.lib.mlst_set_read_adapters(self._h, bytes(adapters) if adapters else None, int(min_overlap), int(error_permille)), "mlst_set_read_adapters")
+
+    def get_read_adapters(self) -> dict:
+        """{"adapters": [upper-case str], "min_overlap", "error_permille"}; no adapters and 0, 0 with the switch off"""
+        buf = C.create_string_buffer(8 * 65)
+        mo, pm = C.c_uint32(), C.c_uint32()
+        self._check(self.lib.mlst_get_read_adapters(self._h, buf, len(buf), C.byref(mo), C.byref(pm)), "mlst_get_read_adapters")
+        text = buf.value.decode()
+        return {"adapters": text.split(",") if text else [], "min_overlap": int(mo.value), "error_permille": int(pm.value)}
+
+    def read_adapters_info(self) -> dict:
+        """Since the last reset_sample: reads cut, bases removed, reads of length >= 1 cut at 0, reads cut per adapter.  All zero (and
+        no adapter) with the switch off.  Separate from read_prep_info()."""
+        out = (C.c_uint64 * 12)()
+        self._check(self.lib.mlst_get_read_adapters_info(self._h, out), "mlst_get_read_adapters_info")
+        return {"trimmed": int(out[0]), "bases_removed": int(out[1]), "emptied": int(out[2]), "per_adapter": [int(out[4 + k]) for k in range(int(out[3]))]}
 
     def set_export_md(self, on: bool = True) -> None:
         """export_sam_text / write_sam_all write bowtie2's MD:Z field between NM:i and YT:Z, formatted on the GPU (mlst_set_export_md; off

@@ -771,6 +771,93 @@ def prep_fastq(text: bytes, trim5: int = 0, trim3: int = 0, trim_qual: int = 0, 
     return b"".join(out), info
 
 
+ADAPTER_NAMES = {"illumina": "AGATCGGAAGAGC", "nextera": "CTGTCTCTTATA", "smallrna": "TGGAATTCTCGG"}      # (the three Trim Galore knows)
+
+
+def check_adapters(adapters, min_overlap: int = 3, error_permille: int = 100) -> list:
+    """The adapters of Engine.set_read_adapters as a list of upper-case bytes; ValueError for a setting mlst_set_read_adapters refuses:
+    a letter outside ACGTN, an adapter of only Ns, an empty one, more than 8 adapters, one longer than 64 letters, min_overlap outside
+    1..64, error_permille outside 0..500.  adapters: one str / bytes with commas between the adapters, or a sequence of them."""
+    if isinstance(adapters, (str, bytes, bytearray)):
+        adapters = (adapters.encode() if isinstance(adapters, str) else bytes(adapters)).split(b",")
+    out = [(a.encode() if isinstance(a, str) else bytes(a)).upper() for a in adapters]
+    if not 1 <= len(out) <= 8:
+        raise ValueError("%d adapters: 1 to 8 are taken" % len(out))
+    for a in out:
+        if not 1 <= len(a) <= 64:
+            raise ValueError("an adapter holds %d letters: 1 to 64 are taken" % len(a))
+        if a.strip(b"ACGTN"):
+            raise ValueError("adapter %r holds a letter outside ACGTN" % a.decode("latin-1"))
+        if not a.strip(b"N"):
+            raise ValueError("adapter %r holds only N" % a.decode())
+    if not 1 <= int(min_overlap) <= 64:
+        raise ValueError("min_overlap %r is outside 1..64" % (min_overlap,))
+    if not 0 <= int(error_permille) <= 500:
+        raise ValueError("error_permille %r is outside 0..500" % (error_permille,))
+    return out
+
+
+def adapter_cut(seq: bytes, adapters, min_overlap: int = 3, error_permille: int = 100) -> tuple[int, int]:
+    """Where a 3' adapter is removed from the read seq: (new length, index of the adapter), or (len(seq), -1) when none is found.  The
+    rule is the project's own, modelled on `cutadapt -a ADAPTER --no-indels --times 1`; it does not claim cutadapt's bytes.
+      * A candidate is an adapter k (m letters of ACGTN) and a start p, 0 <= p <= n - min(min_overlap, m).  Its overlap is
+        L = min(m, n - p): the adapter lies inside the read or hangs over its 3' end, never over the 5' end.
+      * Position i < L matches if adapter[i] is N or the read's byte at p + i, upper-cased, equals adapter[i]: a non-ACGT byte of the
+        read, N included, matches only an adapter N.  mism = L - matches.
+      * The candidate is valid if mism <= (L * error_permille) // 1000 (integers).
+      * The cut is the valid candidate with the most matches; among equals the smallest p, then the smallest k.  Bases [0, p) remain."""
+    ads = check_adapters(adapters, min_overlap, error_permille)
+    s = np.frombuffer(bytes(seq).upper(), np.uint8)
+    n = len(s)
+    best, cut, which = 0, n, -1
+    for k, a in enumerate(ads):
+        m = len(a)
+        last = n - min(min_overlap, m)                      # the last start
+        if last < 0:
+            continue
+        matches = np.zeros(last + 1, np.int64)              # per start p
+        for i in range(min(m, n)):                          # letter i lies on base p + i, inside the read for p < n - i
+            top = min(last + 1, n - i)
+            matches[:top] += 1 if a[i] == 78 else (s[i:i + top] == a[i])      # (78: 'N')
+        L = np.minimum(m, n - np.arange(last + 1))
+        valid = L - matches <= (L * error_permille) // 1000
+        if valid.any():
+            p = int(np.where(valid, matches, -1).argmax())  # the most matches, the smallest p among equals
+            if which < 0 or matches[p] > best or (matches[p] == best and p < cut):
+                best, cut, which = int(matches[p]), p, k
+    return cut, which
+
+
+def trim_adapters(text: bytes, adapters, min_overlap: int = 3, error_permille: int = 100) -> tuple[bytes, dict]:
+    """The FASTQ text the engine behaves as if it had been given under Engine.set_read_adapters(adapters, min_overlap, error_permille),
+    and the counters of Engine.read_adapters_info().  This is the rule mlst_set_read_adapters applies on the device
+    (csrc/read_adapt.h, adapter_cut per read); it serves the tests and whoever wants the cut file -- the command never calls it.  Per
+    record, header and '+' line untouched, line ends LF: bases and quality characters [0, adapter_cut(...)[0]) remain; a read left
+    without a base stays a record with two empty lines.  One adapter is removed per read; each mate of a pair is cut on its own (cut
+    each file).  Behind read preparation: trim_adapters(prep_fastq(text, ...)[0], ...).  Counters: trimmed (reads cut), bases_removed,
+    emptied (reads of length >= 1 cut at 0), per_adapter (reads cut, by adapter)."""
+    ads = check_adapters(adapters, min_overlap, error_permille)
+    lines = bytes(text).split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    if len(lines) % 4:
+        raise ValueError("FASTQ text holds %d lines: not a whole number of 4-line records" % len(lines))
+    out = []
+    info = {"trimmed": 0, "bases_removed": 0, "emptied": 0, "per_adapter": [0] * len(ads)}
+    for k in range(0, len(lines), 4):
+        h, s, p, ql = (x[:-1] if x.endswith(b"\r") else x for x in lines[k:k + 4])
+        if len(s) != len(ql):
+            raise ValueError("FASTQ record with different sequence and quality lengths: %r" % h[:60])
+        cut, which = adapter_cut(s, ads, min_overlap, error_permille)
+        if which >= 0:
+            info["trimmed"] += 1
+            info["bases_removed"] += len(s) - cut
+            info["emptied"] += cut == 0
+            info["per_adapter"][which] += 1
+        out.append(b"%s\n%s\n%s\n%s\n" % (h, s[:cut], p, ql[:cut]))
+    return b"".join(out), info
+
+
 def _bgzf_block_size(buf, off: int) -> int:
     """Total size of the BGZF block that starts at buf[off], 0 if the header is incomplete, -1 if it is not BGZF."""
     if len(buf) - off < 18:
