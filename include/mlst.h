@@ -396,6 +396,38 @@ int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, const uint64
 int mlst_alignments_text_next(mlst_handle* h, uint8_t* text, uint64_t cap, uint64_t* n_bytes, uint64_t* n_records, int* done);
 int mlst_alignments_text_close(mlst_handle* h);
 
+/* ---- the reads that align to the loci as FASTQ text, formatted on the device (what `bowtie2 --al FILE` writes; csrc/reads_text.h) -------
+ * Which reads: a read index is written iff it has at least one record in the export above -- some (work item of the read, allele of
+ *   the item's locus) whose alignment, decided exactly as pass 1 decides it, has score >= the floor of the read's length && score > 0:
+ *   the records mlst_alignments_text_* writes and MLST_CNT_TOTAL_RECORDS counts.  Records that fail the AS / XM tag filter count;
+ *   mlst_set_depth_cap is ignored.  A retained read without a record is not written.  The pairs are decided by the kernels of that
+ *   export, so the set is its QNAMEs by construction.
+ * Order: ascending read index; each read once, however many records it has.
+ * Record: four lines with LF ends, `@<name>` / SEQ / `+` / QUAL.  <name> is the QNAME of the export above: r<k>, k = the read index
+ *   (read index >> 1 with paired != 0), or with mlst_set_read_names the kept name (r<k> for a fallback).  With paired != 0 `/1` follows for
+ *   an even read index and `/2` for an odd one (the mates share a QNAME; a FASTQ must tell them apart).  SEQ is the read as the engine
+ *   holds it -- prepared and cut where mlst_set_read_prep / mlst_set_read_adapters ran --, in read orientation, never turned to the
+ *   reference strand: ACGT, and N where the stored quality byte has bit 7 set.  QUAL is chr(min(q, 93) + 33) of the stored Phred.
+ * Mates: each mate is written on its own, and only if it has a record itself -- the engine does not retain a mate that hit nothing.
+ * mlst_reads_text_open plans the rounds with the planner of mlst_alignments_text_open (the same sort, rounds cut at read boundaries).
+ *   What is summed against round_bytes (0: 256 MiB) per read of n bases with P (item, allele) pairs is
+ *       max(2 n + max(21, the longest kept name) + 10,  36 P)
+ *   -- a bound on its text (`@`, r + 20 digits or the name, `/1`, SEQ, `+`, QUAL, four LFs), or the bytes of the round's device tables
+ *   for its pairs (AtPair 20, the entry of the banded list 8, the offsets entry 8), whichever is larger: for an isolate the tables
+ *   dominate the text by orders of magnitude, and device memory for a round stays O(round_bytes).  A read whose own bound exceeds
+ *   round_bytes: MLST_E_LIMIT, the message names the bytes needed.  The bytes depend neither on the order of the item list nor on
+ *   round_bytes.
+ * mlst_reads_text_next formats one round: whole records only, n_bytes of them into text (host memory of cap bytes), n_reads records;
+ *   done = 1 with the last round that holds text, and at once (n_bytes = 0) when no read is left that has a record.  text = NULL with
+ *   cap = 0 asks for the size of the round that comes next and consumes nothing.
+ * The sample's state is read and none of it is changed; an open BGZF piece is finished first; mlst_reset_sample closes the export.
+ * One text export exists at a time: opening either kind closes whichever was open, and _next of the kind that is not open is
+ *   MLST_E_INVALID.  Also refused with MLST_E_INVALID: a call while a BAM, SAM or paired stream is open on the handle,
+ *   mlst_reads_text_next without an open export, cap smaller than the round.  mlst_set_export_md has no bearing on this export. */
+int mlst_reads_text_open(mlst_handle* h, int paired, uint64_t round_bytes /* 0: 256 MiB */);
+int mlst_reads_text_next(mlst_handle* h, uint8_t* text, uint64_t cap, uint64_t* n_bytes, uint64_t* n_reads, int* done);
+int mlst_reads_text_close(mlst_handle* h);
+
 /* ---- the reads' own names as QNAME (off by default; csrc/read_names.h; `cli type --read-names`) ---------------------------------------
  * mlst_set_read_names(h, 1): the name of every read pass 1 retains is copied out of the FASTQ text on the device, before the text
  *   slot of its chunk is reused; mlst_alignments_text_* then writes that name as QNAME and mlst_read_names_fetch hands the names to the

@@ -8,6 +8,7 @@
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam-all -d DB  (also <out>/<sample>.all.sam: every alignment, as bowtie2 -a would leave it)
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam-all --read-names -d DB  (QNAME = the reads' own names, kept on the GPU)
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam --write-sam-all --md -d DB  (both exports with bowtie2's MD:Z field)
+    python -m metamlst_amd.cli type  SAMPLE.fastq --write-reads -d DB    (also <out>/<sample>.loci.fastq: the reads that align to the loci, as bowtie2 --al)
     python -m metamlst_amd.cli merge FOLDER -d DB [-z 5] [--filter ...] [--meta ...] [--idField ...] [--aligner auto|gpu|muscle]   (metamlst-merge.py:35-49)
     python -m metamlst_amd.cli index -d DB [-s seqs.fasta,...] [-t typings.txt,...] [-q dump.fa] [--list]   (metamlst-index.py:24-33)
 
@@ -92,8 +93,15 @@ def _type_parser(sub):
                         "allele of its locus, what `bowtie2 -a` leaves in front of metamlst.py -- as SAM text formatted on the GPU "
                         "(metamlst_amd/samout.py: one @SQ per loaded allele, XS:i only where the read has a second record).  Accepted and "
                         "refused where --write-sam is; both may be given")
+    p.add_argument("--write-reads", dest="write_reads", action="store_true",
+                   help="after the .nfo (and the SAM files), write <out>/<sample>.loci.fastq: the reads that have at least one alignment to "
+                        "a locus -- what `bowtie2 --al` writes --, as FASTQ formatted on the GPU in ascending read index "
+                        "(metamlst_amd/samout.py: reads_fastq_rule).  Names are those of the SAM exports (r<read index>, or the reads' own "
+                        "with --read-names), with /1 and /2 when the sample is typed as pairs; SEQ / QUAL are the reads as they were "
+                        "aligned (prepared and cut where --trim* / --adapter ran).  A mate is written only if it aligns itself.  Accepted "
+                        "and refused where --write-sam is; the .nfo and the --log file do not change")
     p.add_argument("--read-names", dest="read_names", action="store_true",
-                   help="with --write-sam / --write-sam-all: QNAME is the read's own name (the FASTQ header behind the @ up to the first "
+                   help="with --write-sam / --write-sam-all / --write-reads: QNAME is the read's own name (the FASTQ header behind the @ up to the first "
                         "white space, bowtie2's rule) instead of r<read index>; the names of the reads on the loci are copied out of the "
                         "FASTQ text on the GPU.  A name that is no legal SAM QNAME keeps r<k>, and such reads are counted.  FASTQ input of "
                         "one sample on one GPU (plain, .gz, bgzip, `a.fq,b.fq`, -2): it goes with none of a reads BAM, --contigs, "
@@ -267,7 +275,7 @@ def run_type(a, argv=None) -> int:
                         (a.long_reads, "--long-reads cuts reads into windows, and a window has no name"),
                         (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and a window has no name"),
                         (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the names of a reads BAM are not carried to the exports: FASTQ input only"),
-                        (not (a.write_sam or a.write_sam_all), "it names the reads of an export: give --write-sam or --write-sam-all")):
+                        (not (a.write_sam or a.write_sam_all or a.write_reads), "it names the reads of an export: give --write-sam or --write-sam-all")):
             if on:
                 print("--read-names: " + why)
                 return 1
@@ -300,7 +308,7 @@ def run_type(a, argv=None) -> int:
     if a.md and not (a.write_sam or a.write_sam_all):      # (with an export flag it is accepted and refused where that flag is: below)
         print("--md: it adds MD:Z to the records of an export: give --write-sam or --write-sam-all")
         return 1
-    for flag in [f for f, on in (("--write-sam", a.write_sam), ("--write-sam-all", a.write_sam_all)) if on]:      # (refused before any GPU use)
+    for flag in [f for f, on in (("--write-sam", a.write_sam), ("--write-sam-all", a.write_sam_all), ("--write-reads", a.write_reads)) if on]:      # (refused before any GPU use)
         if a.alignments:
             print(flag + " writes the engine's own alignments: with --alignments the file is the input")
             return 1
@@ -481,7 +489,7 @@ def run_type(a, argv=None) -> int:
         print(e, file=sys.stderr)
         database.closeConnection()
         return 1
-    if (a.write_sam or a.write_sam_all) and not paired and not (long_reads or long_bam) and all(_is_reads_bam(f) for f in paths):      # (as submit_bam_reads decides it)
+    if (a.write_sam or a.write_sam_all or a.write_reads) and not paired and not (long_reads or long_bam) and all(_is_reads_bam(f) for f in paths):      # (as submit_bam_reads decides it)
         from .samin import bam_first_read_flags
         paired = any((bam_first_read_flags(f) or 0) & 1 for f in paths)
     return _finish_type_device(a, eng, idx, database, targs, paired=paired)
@@ -491,7 +499,8 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
     """Allele choice (metamlst.py:133-151, 244), pile-up and majority consensus on the device, queued behind pass 1
     (mlst_typing_enqueue): one host synchronisation per sample instead of three (statistics, host choice, pile-up).
     --write-sam: then the alignments to the alleles chosen there, as <out>/<sample>.sam (paired: the reads were submitted as pairs);
-    --write-sam-all: then every alignment, as <out>/<sample>.all.sam."""
+    --write-sam-all: then every alignment, as <out>/<sample>.all.sam;
+    --write-reads: then the reads that have an alignment, as <out>/<sample>.loci.fastq."""
     eng.typing_enqueue(penalty=targs.penalty)
     st, chosen, letters = eng.typing_fetch()
     rc = _finish_type(a, idx, database, targs, st, None, typed=(chosen, letters))
@@ -512,6 +521,11 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
     if rc == 0 and a.write_sam_all:
         from .samout import write_sam_all
         write_sam_all(a.o + "/" + sample_name(a.READS) + ".all.sam", idx, eng, paired, md=md)
+    if rc == 0 and getattr(a, "write_reads", False):
+        from .samout import write_reads
+        n_written = write_reads(a.o + "/" + sample_name(a.READS) + ".loci.fastq", eng, paired)
+        if not a.quiet:
+            print("--write-reads: %d reads with an alignment written" % n_written)
     return rc
 
 

@@ -3692,6 +3692,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "read_prep.h"
 #include "read_adapt.h"
 #include "aln_text.h"
+#include "reads_text.h"
 
 // ================================================================== host side
 struct EvPair { hipEvent_t a, b; int which; };
@@ -3832,7 +3833,9 @@ struct mlst_handle {
     // the sorted item list (perm, pair_off, item_read, read_first), the RNAME labels and the rounds; per round (sized by the largest
     // one): AtPair and line offset per pair, the list of the banded SW, AtRead per read, the workgroups' sums; d_text = the round's text.
     // md: the switch of mlst_set_export_md; with_md: what the open export read of it; d_mdw: the pairs' MD:Z widths, only with it.
-    struct AtState { bool open = false, ready = false, with_names = false, md = false, with_md = false; u16* d_mdw = nullptr; size_t next = 0; std::vector<AtRound> rounds; u64 round_bytes = 0, round_recs = 0, max_pairs = 0;
+    // reads: the open export is the one of mlst_reads_text_* (csrc/reads_text.h) -- one text export exists at a time; it has no d_names,
+    // d_name_off, d_reads and d_mdw, and its d_wex / d_gsum are per READ of a round (max_reads + 1 entries), not per pair.
+    struct AtState { bool open = false, ready = false, with_names = false, md = false, with_md = false, reads = false; u64 max_reads = 0; u16* d_mdw = nullptr; size_t next = 0; std::vector<AtRound> rounds; u64 round_bytes = 0, round_recs = 0, max_pairs = 0;
              u32* d_perm = nullptr; u64* d_pair_off = nullptr; u32* d_item_read = nullptr; u64* d_read_first = nullptr; u8* d_names = nullptr; u64* d_name_off = nullptr;
              AtPair* d_meta = nullptr; AtRead* d_reads = nullptr; u64* d_wex = nullptr; u64* d_gsum = nullptr; u64* d_dp = nullptr; u8* d_desc = nullptr;
              u8* d_text = nullptr; u64 cap_text = 0; u8* h_tot = nullptr; } at;
@@ -6878,7 +6881,7 @@ extern "C" int mlst_get_read_adapters_info(mlst_handle* h, uint64_t out[12]) {
 // MD:Z in the text export (include/mlst.h): no part of the sample's state; mlst_alignments_text_open reads it
 extern "C" int mlst_set_export_md(mlst_handle* h, int on) {
     if (!h) return MLST_E_INVALID;
-    if (h->at.open) return fail(h, MLST_E_INVALID, "an export is open: mlst_set_export_md changes only before mlst_alignments_text_open or behind mlst_alignments_text_close");
+    if (h->at.open && !h->at.reads) return fail(h, MLST_E_INVALID, "an export is open: mlst_set_export_md changes only before mlst_alignments_text_open or behind mlst_alignments_text_close");
     h->at.md = on != 0;
     return MLST_OK;
 }
@@ -7302,28 +7305,16 @@ static void at_free(mlst_handle* h) {
     hipFree(T.d_meta); hipFree(T.d_reads); hipFree(T.d_wex); hipFree(T.d_gsum); hipFree(T.d_dp); hipFree(T.d_mdw); T.d_mdw = nullptr;
     T.d_perm = nullptr; T.d_pair_off = nullptr; T.d_item_read = nullptr; T.d_read_first = nullptr; T.d_names = nullptr; T.d_name_off = nullptr;
     T.d_meta = nullptr; T.d_reads = nullptr; T.d_wex = nullptr; T.d_gsum = nullptr; T.d_dp = nullptr;
-    T.rounds.clear(); T.next = 0; T.open = false; T.ready = false;
+    T.rounds.clear(); T.next = 0; T.open = false; T.ready = false; T.reads = false;
 }
-extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, const uint64_t* name_off, int paired, uint64_t round_bytes) {
-    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
-    auto& T = h->at;
-    hipSetDevice(h->device);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    at_free(h);      // (an export left open, or one whose sample was reset)
-    { int rc_ = ax_refuse_open(h); if (rc_) return rc_; }
-    { int rc_ = bz_flush(h); if (rc_) return rc_; }
-    if (!names || !name_off) return fail(h, MLST_E_INVALID, "NULL argument");
+// The host part of a text export's open, shared by mlst_alignments_text_open and mlst_reads_text_open: the item list to the host, the sort
+// of a permutation of it by (read index, locus, strand, diag), pair_off / item_read / read_first, a bound on every read and the rounds
+// cut at read boundaries against round_bytes.  item_bound(n, alleles of the item's locus) is summed over a read's items;
+// read_floor(n of the read's first item, its pairs) is the least the read counts.  what: the words of MLST_E_LIMIT.
+struct AtPlan { u64 ni = 0, nr = 0, max_pairs = 0, max_reads = 0; std::vector<u32> perm, item_read; std::vector<u64> pair_off, read_first; std::vector<AtRound> rounds; };
+template <class FItem, class FRead>
+static int at_plan(mlst_handle* h, u64 round_bytes, const char* what, FItem item_bound, FRead read_floor, AtPlan& P) {
     const u64 na = h->n_alleles, nl = h->n_loci;
-    u64 max_name = 0;
-    for (u64 a = 0; a < na; a++) {
-        if (name_off[a + 1] < name_off[a]) return fail(h, MLST_E_INVALID, "name_off descends at allele %llu", (unsigned long long)a);
-        max_name = std::max<u64>(max_name, name_off[a + 1] - name_off[a]);
-    }
-    if (!round_bytes) round_bytes = 256ull << 20;
-    RnCtr rnc; { int rc_ = rn_fetch(h, &rnc); if (rc_) return rc_; }      // mlst_set_read_names: the longest kept name bounds the QNAME column
-    const bool with_names = h->rn.on && h->rn.d_ctr;
-    const u64 max_qname = with_names ? rnc.longest : 0;
-    const bool with_md = T.md;      // mlst_set_export_md: read here, fixed until the export is closed
     std::vector<u32> nall(nl ? nl : 1, 0);
     for (u64 a = 0; a < na; a++) nall[h->allele_locus[a]]++;
     for (u64 l = 0; l < nl; l++) if (nall[l] >= (1u << 20)) return fail(h, MLST_E_LIMIT, "locus %llu has %u alleles: the export takes fewer than 2^20", (unsigned long long)l, nall[l]);
@@ -7340,7 +7331,7 @@ extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, c
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     for (u64 i = 0; i < ni; i++) if (items[i].ret >= nret || items[i].locus >= nl) return fail(h, MLST_E_HIP, "work item %llu is inconsistent", (unsigned long long)i);
-    std::vector<u32> perm(ni ? ni : 1);
+    std::vector<u32>& perm = P.perm; perm.assign(ni ? ni : 1, 0);
     for (u64 i = 0; i < ni; i++) perm[i] = (u32)i;
     std::sort(perm.begin(), perm.begin() + ni, [&](u32 x, u32 y) {
         const ItemDev& a = items[x]; const ItemDev& b = items[y];
@@ -7351,33 +7342,78 @@ extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, c
         if (a.diag != b.diag) return a.diag < b.diag;
         return x < y;
     });
-    // reads, pairs in front of every item, a bound on every read's text; rounds cut at read boundaries
-    std::vector<u64> pair_off(ni + 1, 0), read_first; std::vector<u32> item_read(ni ? ni : 1); std::vector<u64> read_bound;
+    // reads, pairs in front of every item, a bound on every read; rounds cut at read boundaries
+    std::vector<u64>& pair_off = P.pair_off; std::vector<u64>& read_first = P.read_first; std::vector<u32>& item_read = P.item_read;
+    pair_off.assign(ni + 1, 0); read_first.clear(); item_read.assign(ni ? ni : 1, 0);
+    std::vector<u64> read_bound;
     for (u64 k = 0; k < ni; k++) {
         const ItemDev& it = items[perm[k]];
         if (k == 0 || ridx[it.ret] != ridx[items[perm[k - 1]].ret]) { read_first.push_back(k); read_bound.push_back(0); }
         item_read[k] = (u32)(read_first.size() - 1);
         pair_off[k + 1] = pair_off[k] + nall[it.locus];
-        read_bound.back() += (u64)nall[it.locus] * at_line_bound((u32)(rlen[it.ret] & 0x7FFFu), max_name, max_qname, with_md);
+        read_bound.back() += item_bound((u32)(rlen[it.ret] & 0x7FFFu), (u64)nall[it.locus]);
     }
     const u64 nr = read_first.size();
     read_first.push_back(ni);
     u64 worst = 0;
-    for (u64 r = 0; r < nr; r++) worst = std::max(worst, read_bound[r]);
-    if (worst > round_bytes) return fail(h, MLST_E_LIMIT, "round_bytes %llu is too small: the records of one read may need %llu bytes", (unsigned long long)round_bytes, (unsigned long long)worst);
-    std::vector<AtRound> rounds;
-    u64 max_pairs = 0, max_reads = 0;
+    for (u64 r = 0; r < nr; r++) {
+        const u64 k0 = read_first[r];
+        read_bound[r] = std::max<u64>(read_bound[r], read_floor((u32)(rlen[items[perm[k0]].ret] & 0x7FFFu), pair_off[read_first[r + 1]] - pair_off[k0]));
+        worst = std::max(worst, read_bound[r]);
+    }
+    if (worst > round_bytes) return fail(h, MLST_E_LIMIT, "round_bytes %llu is too small: %s may need %llu bytes", (unsigned long long)round_bytes, what, (unsigned long long)worst);
+    P.rounds.clear(); P.max_pairs = 0; P.max_reads = 0;
     for (u64 r = 0; r < nr;) {
         u64 r1 = r, sum = 0;
         while (r1 < nr && sum + read_bound[r1] <= round_bytes) sum += read_bound[r1++];
         AtRound R; R.r0 = r; R.r1 = r1; R.k0 = read_first[r]; R.k1 = read_first[r1]; R.pb = pair_off[R.k0]; R.n_pairs = pair_off[R.k1] - R.pb;
-        rounds.push_back(R); max_pairs = std::max(max_pairs, R.n_pairs); max_reads = std::max(max_reads, r1 - r);
+        P.rounds.push_back(R); P.max_pairs = std::max(P.max_pairs, R.n_pairs); P.max_reads = std::max(P.max_reads, r1 - r);
         r = r1;
     }
+    P.ni = ni; P.nr = nr;
+    return MLST_OK;
+}
+// the sorted item list of a plan on the device (both exports)
+static hipError_t at_upload_plan(mlst_handle* h, const AtPlan& P) {
+    auto& T = h->at;
+    hipError_t e;
+    if ((e = dmalloc(&T.d_perm, P.ni)) != hipSuccess || (e = dmalloc(&T.d_pair_off, P.ni + 1)) != hipSuccess || (e = dmalloc(&T.d_item_read, P.ni)) != hipSuccess ||
+        (e = dmalloc(&T.d_read_first, P.nr + 1)) != hipSuccess) return e;
+    if (P.ni) {
+        if ((e = hipMemcpyAsync(T.d_perm, P.perm.data(), P.ni * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(T.d_item_read, P.item_read.data(), P.ni * 4, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return e;
+    }
+    if ((e = hipMemcpyAsync(T.d_pair_off, P.pair_off.data(), (P.ni + 1) * 8, hipMemcpyHostToDevice, h->stream)) != hipSuccess) return e;
+    return hipMemcpyAsync(T.d_read_first, P.read_first.data(), (P.nr + 1) * 8, hipMemcpyHostToDevice, h->stream);
+}
+extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, const uint64_t* name_off, int paired, uint64_t round_bytes) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    auto& T = h->at;
+    hipSetDevice(h->device);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    at_free(h);      // (an export left open, or one whose sample was reset)
+    { int rc_ = ax_refuse_open(h); if (rc_) return rc_; }
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    if (!names || !name_off) return fail(h, MLST_E_INVALID, "NULL argument");
+    const u64 na = h->n_alleles;
+    u64 max_name = 0;
+    for (u64 a = 0; a < na; a++) {
+        if (name_off[a + 1] < name_off[a]) return fail(h, MLST_E_INVALID, "name_off descends at allele %llu", (unsigned long long)a);
+        max_name = std::max<u64>(max_name, name_off[a + 1] - name_off[a]);
+    }
+    if (!round_bytes) round_bytes = 256ull << 20;
+    RnCtr rnc; { int rc_ = rn_fetch(h, &rnc); if (rc_) return rc_; }      // mlst_set_read_names: the longest kept name bounds the QNAME column
+    const bool with_names = h->rn.on && h->rn.d_ctr;
+    const u64 max_qname = with_names ? rnc.longest : 0;
+    const bool with_md = T.md;      // mlst_set_export_md: read here, fixed until the export is closed
+    AtPlan P;
+    { int rc_ = at_plan(h, round_bytes, "the records of one read",
+                        [&](u32 n, u64 alleles) { return alleles * at_line_bound(n, max_name, max_qname, with_md); }, [](u32, u64) { return 0ull; }, P); if (rc_) return rc_; }
+    const u64 max_pairs = P.max_pairs, max_reads = P.max_reads;
     const u64 nbytes = name_off[na] - name_off[0], max_groups = (max_pairs + FQT_GROUP - 1) / FQT_GROUP;
     auto bad = [&](hipError_t e) { at_free(h); return fail(h, MLST_E_HIP, "mlst_alignments_text_open: %s", hipGetErrorString(e)); };
 #define ATCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bad(e_); } while (0)
-    ATCHK(dmalloc(&T.d_perm, ni)); ATCHK(dmalloc(&T.d_pair_off, ni + 1)); ATCHK(dmalloc(&T.d_item_read, ni)); ATCHK(dmalloc(&T.d_read_first, nr + 1));
+    ATCHK(at_upload_plan(h, P));
     ATCHK(dmalloc(&T.d_names, nbytes)); ATCHK(dmalloc(&T.d_name_off, na + 1));
     ATCHK(dmalloc(&T.d_meta, max_pairs)); ATCHK(dmalloc(&T.d_reads, max_reads)); ATCHK(dmalloc(&T.d_wex, max_pairs)); ATCHK(dmalloc(&T.d_gsum, max_groups));
     ATCHK(dmalloc(&T.d_dp, max_pairs + 2));      // the list, its length and the round's records behind it
@@ -7386,9 +7422,6 @@ extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, c
     if (!T.h_tot) { void* p = nullptr; ATCHK(hipHostMalloc(&p, sizeof(FqtMeta) + 8, hipHostMallocDefault)); T.h_tot = (u8*)p; }
     std::vector<u64> noff(na + 1);
     for (u64 a = 0; a <= na; a++) noff[a] = name_off[a] - name_off[0];
-    if (ni) { ATCHK(hipMemcpyAsync(T.d_perm, perm.data(), ni * 4, hipMemcpyHostToDevice, h->stream)); ATCHK(hipMemcpyAsync(T.d_item_read, item_read.data(), ni * 4, hipMemcpyHostToDevice, h->stream)); }
-    ATCHK(hipMemcpyAsync(T.d_pair_off, pair_off.data(), (ni + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    ATCHK(hipMemcpyAsync(T.d_read_first, read_first.data(), (nr + 1) * 8, hipMemcpyHostToDevice, h->stream));
     if (nbytes) ATCHK(hipMemcpyAsync(T.d_names, names + name_off[0], nbytes, hipMemcpyHostToDevice, h->stream));
     ATCHK(hipMemcpyAsync(T.d_name_off, noff.data(), (na + 1) * 8, hipMemcpyHostToDevice, h->stream));
     AtDev D; memset((void*)&D, 0, sizeof D);
@@ -7403,7 +7436,7 @@ extern "C" int mlst_alignments_text_open(mlst_handle* h, const uint8_t* names, c
     ATCHK(hipMemcpyAsync(T.d_desc + sizeof(AtDev), &F, sizeof F, hipMemcpyHostToDevice, h->stream));
     ATCHK(hipStreamSynchronize(h->stream));      // (the host vectors go out of scope)
 #undef ATCHK
-    T.rounds.swap(rounds); T.max_pairs = max_pairs; T.next = 0; T.ready = false; T.open = true; T.with_names = with_names; T.with_md = with_md;
+    T.rounds.swap(P.rounds); T.max_pairs = max_pairs; T.max_reads = max_reads; T.reads = false; T.next = 0; T.ready = false; T.open = true; T.with_names = with_names; T.with_md = with_md;
     return MLST_OK;
 }
 // the kernels of round T.next up to the lines' offsets; leaves the round's bytes and records in T.round_bytes / T.round_recs
@@ -7448,6 +7481,7 @@ extern "C" int mlst_alignments_text_next(mlst_handle* h, uint8_t* text, uint64_t
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
     auto& T = h->at;
     if (!T.open) return fail(h, MLST_E_INVALID, "no export is open (mlst_alignments_text_open comes first)");
+    if (T.reads) return fail(h, MLST_E_INVALID, "the open export is the one of mlst_reads_text_open: mlst_reads_text_next takes its rounds");
     { int rc_ = ax_refuse_open(h); if (rc_) return rc_; }
     if (!n_bytes || !n_records || !done) return fail(h, MLST_E_INVALID, "NULL argument");
     hipSetDevice(h->device);
@@ -7485,6 +7519,119 @@ extern "C" int mlst_alignments_text_close(mlst_handle* h) {
     at_free(h);
     return MLST_OK;
 }
+
+// ---- the reads that align to the loci as FASTQ text, written on the device (include/mlst.h; kernels: csrc/reads_text.h) ----
+// The state is the text export's (h->at, reads = true): one text export exists at a time, and opening either kind closes the other.
+extern "C" int mlst_reads_text_open(mlst_handle* h, int paired, uint64_t round_bytes) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    auto& T = h->at;
+    hipSetDevice(h->device);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    at_free(h);      // (an export of either kind left open, or one whose sample was reset)
+    { int rc_ = ax_refuse_open(h); if (rc_) return rc_; }
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    if (!round_bytes) round_bytes = 256ull << 20;
+    RnCtr rnc; { int rc_ = rn_fetch(h, &rnc); if (rc_) return rc_; }      // mlst_set_read_names: the longest kept name bounds the name line
+    const bool with_names = h->rn.on && h->rn.d_ctr;
+    const u64 max_qname = with_names ? rnc.longest : 0;
+    AtPlan P;
+    { int rc_ = at_plan(h, round_bytes, "the text and the tables of one read",
+                        [](u32, u64 alleles) { return RT_PAIR_BYTES * alleles; }, [&](u32 n, u64 pairs) { return rt_read_bound(n, max_qname, pairs); }, P); if (rc_) return rc_; }
+    const u64 max_pairs = P.max_pairs, max_reads = P.max_reads, max_groups = (max_reads + 1 + FQT_GROUP - 1) / FQT_GROUP;
+    auto bad = [&](hipError_t e) { at_free(h); return fail(h, MLST_E_HIP, "mlst_reads_text_open: %s", hipGetErrorString(e)); };
+#define ATCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bad(e_); } while (0)
+    ATCHK(at_upload_plan(h, P));
+    ATCHK(dmalloc(&T.d_meta, max_pairs)); ATCHK(dmalloc(&T.d_wex, max_reads + 1)); ATCHK(dmalloc(&T.d_gsum, max_groups));
+    ATCHK(dmalloc(&T.d_dp, max_pairs + 2));      // the list, its length and the round's written reads behind it
+    if (!T.d_desc) ATCHK(dmalloc(&T.d_desc, sizeof(AtDev) + sizeof(FqtDev) + sizeof(FqtMeta)));
+    if (!T.h_tot) { void* p = nullptr; ATCHK(hipHostMalloc(&p, sizeof(FqtMeta) + 8, hipHostMallocDefault)); T.h_tot = (u8*)p; }
+    AtDev D; memset((void*)&D, 0, sizeof D);
+    D.perm = T.d_perm; D.pair_off = T.d_pair_off; D.item_read = T.d_item_read; D.read_first = T.d_read_first;
+    D.ascii = h->d_ascii; D.aoff = h->d_aoff; D.meta = T.d_meta; D.wex = T.d_wex; D.gsum = T.d_gsum;
+    D.dp_list = T.d_dp; D.dp_n = T.d_dp + max_pairs; D.n_rec = T.d_dp + max_pairs + 1; D.paired = paired ? 1 : 0;
+    if (with_names) { D.rn_bytes = h->rn.d_bytes; D.rn_off = h->rn.d_off; D.rn_len = h->rn.d_len; }
+    FqtDev F; memset((void*)&F, 0, sizeof F);
+    F.wex = T.d_wex; F.gsum = T.d_gsum; F.meta = (FqtMeta*)(T.d_desc + sizeof(AtDev) + sizeof(FqtDev));
+    ATCHK(hipMemcpyAsync(T.d_desc, &D, sizeof D, hipMemcpyHostToDevice, h->stream));
+    ATCHK(hipMemcpyAsync(T.d_desc + sizeof(AtDev), &F, sizeof F, hipMemcpyHostToDevice, h->stream));
+    ATCHK(hipStreamSynchronize(h->stream));      // (the host vectors go out of scope)
+#undef ATCHK
+    T.rounds.swap(P.rounds); T.max_pairs = max_pairs; T.max_reads = max_reads; T.reads = true; T.next = 0; T.ready = false; T.open = true; T.with_names = with_names; T.with_md = false;
+    return MLST_OK;
+}
+// the kernels of round T.next up to the records' offsets; leaves the round's bytes and written reads in T.round_bytes / T.round_recs
+static int rt_prepare(mlst_handle* h) {
+    auto& T = h->at;
+    const AtRound R = T.rounds[T.next];
+    const AtDev* d_D = (const AtDev*)T.d_desc; FqtDev* d_F = (FqtDev*)(T.d_desc + sizeof(AtDev)); FqtMeta* d_M = (FqtMeta*)(T.d_desc + sizeof(AtDev) + sizeof(FqtDev));
+    u64* dp_n = T.d_dp + T.max_pairs;      // the list's length and the round's written reads sit behind the largest round's list
+    const u64 n_ent = R.r1 - R.r0 + 1;     // the reads of the round and the closing entry: its offset is the text's end
+    const u64 ng = (n_ent + FQT_GROUP - 1) / FQT_GROUP;
+    HIPCHK(h, hipMemsetAsync(dp_n, 0, 16, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_M, 0, sizeof(FqtMeta), h->stream));
+    HIPCHK(h, hipMemcpyAsync(&d_F->n_recs, &n_ent, 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.d_wex + (n_ent - 1), 0, 8, h->stream));
+    const unsigned gw = (unsigned)grid_for(R.k1 - R.k0, 1, 8192);      // one-wave workgroups, as k_pileup
+    const unsigned gr = (unsigned)grid_for(R.r1 - R.r0, 1, 8192);
+    // the pairs are decided by the kernels of the full export without a switch, launched as at_prepare launches them
+    if (h->max_wpr <= 10) hipLaunchKernelGGL(k_at_decide_160, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
+    else hipLaunchKernelGGL(k_at_decide_320, dim3(gw), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R);
+    hipLaunchKernelGGL((k_at_dp<false, false, false>), dim3(64), dim3(64), 0, h->stream, h->d_E, h->kp, d_D, R, h->d_tb, (u8*)nullptr);
+    if (T.with_names) hipLaunchKernelGGL((k_rt_mark<true>), dim3(gr), dim3(64), 0, h->stream, h->d_E, d_D, R);
+    else hipLaunchKernelGGL((k_rt_mark<false>), dim3(gr), dim3(64), 0, h->stream, h->d_E, d_D, R);
+    hipLaunchKernelGGL(k_at_local, dim3((unsigned)ng), dim3(1024), 0, h->stream, T.d_wex, n_ent, T.d_gsum);
+    hipLaunchKernelGGL(k_fqt_scan, dim3(1), dim3(1024), 0, h->stream, (const FqtDev*)d_F, ng);
+    hipLaunchKernelGGL(k_fqt_add, dim3((unsigned)ng), dim3(1024), 0, h->stream, (const FqtDev*)d_F);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(T.h_tot, d_M, sizeof(FqtMeta), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.h_tot + sizeof(FqtMeta), dp_n + 1, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // the total sizes the text
+    T.round_bytes = ((const FqtMeta*)T.h_tot)->n_windows; memcpy(&T.round_recs, T.h_tot + sizeof(FqtMeta), 8);
+    T.ready = true;
+    return MLST_OK;
+}
+extern "C" int mlst_reads_text_next(mlst_handle* h, uint8_t* text, uint64_t cap, uint64_t* n_bytes, uint64_t* n_reads, int* done) {
+    if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
+    auto& T = h->at;
+    if (!T.open) return fail(h, MLST_E_INVALID, "no export is open (mlst_reads_text_open comes first)");
+    if (!T.reads) return fail(h, MLST_E_INVALID, "the open export is the one of mlst_alignments_text_open: mlst_alignments_text_next takes its rounds");
+    { int rc_ = ax_refuse_open(h); if (rc_) return rc_; }
+    if (!n_bytes || !n_reads || !done) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    *n_bytes = 0; *n_reads = 0;
+    // a round none of whose reads has a record holds no text: it is passed over, so done = 1 comes at once when nothing is left to write
+    while (T.next < T.rounds.size()) {
+        if (!T.ready) { int rc_ = rt_prepare(h); if (rc_) return rc_; }
+        if (T.round_bytes) break;
+        T.next++; T.ready = false;
+    }
+    if (T.next >= T.rounds.size()) { *done = 1; return MLST_OK; }
+    *n_bytes = T.round_bytes; *n_reads = T.round_recs; *done = 0;
+    if (!text && !cap) return MLST_OK;      // the size of the round that comes next: nothing is consumed
+    if (!text) return fail(h, MLST_E_INVALID, "NULL argument");
+    if (cap < T.round_bytes) return fail(h, MLST_E_INVALID, "cap %llu is smaller than the round: %llu bytes", (unsigned long long)cap, (unsigned long long)T.round_bytes);
+    {
+        const AtRound R = T.rounds[T.next];
+        if (T.cap_text < T.round_bytes) { hipFree(T.d_text); T.d_text = nullptr; T.cap_text = 0; HIPCHK(h, dmalloc(&T.d_text, T.round_bytes)); T.cap_text = T.round_bytes; }
+        const AtDev* d_D = (const AtDev*)T.d_desc;
+        const unsigned gr = (unsigned)grid_for(R.r1 - R.r0, 1, 8192);
+        if (T.with_names) hipLaunchKernelGGL((k_rt_write<true>), dim3(gr), dim3(64), 0, h->stream, h->d_E, d_D, R, T.d_text);
+        else hipLaunchKernelGGL((k_rt_write<false>), dim3(gr), dim3(64), 0, h->stream, h->d_E, d_D, R, T.d_text);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(text, T.d_text, T.round_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    T.next++; T.ready = false;
+    // done = 1 with the last round that holds text: the rounds behind it are looked at now
+    while (T.next < T.rounds.size()) {
+        int rc_ = rt_prepare(h); if (rc_) return rc_;
+        if (T.round_bytes) break;
+        T.next++; T.ready = false;
+    }
+    *done = T.next >= T.rounds.size() ? 1 : 0;
+    return MLST_OK;
+}
+extern "C" int mlst_reads_text_close(mlst_handle* h) { return mlst_alignments_text_close(h); }
 
 extern "C" long long mlst_round_tenths(long long p, uint32_t q) { return q ? round_tenths(p, q) : 0; }
 

@@ -201,6 +201,9 @@ def load_library(path: str | None = None):
         "mlst_alignments_text_open": (C.c_int, [H, u8p, u64p, C.c_int, C.c_uint64]),
         "mlst_alignments_text_next": (C.c_int, [H, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
         "mlst_alignments_text_close": (C.c_int, [H]),
+        "mlst_reads_text_open": (C.c_int, [H, C.c_int, C.c_uint64]),
+        "mlst_reads_text_next": (C.c_int, [H, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+        "mlst_reads_text_close": (C.c_int, [H]),
         "mlst_typing_layout": (C.c_int, [H, u64p, C.POINTER(C.c_uint64)]),
         "mlst_typing_enqueue": (C.c_int, [H, C.c_int32, C.c_uint32, C.c_char]),
         "mlst_typing_choose_pileup": (C.c_int, [H, C.c_int32, u32p]),
@@ -1034,6 +1037,32 @@ class Engine:
             self.lib.mlst_alignments_text_close(self._h)
             if set_md:
                 self.set_export_md(False)
+
+    def export_reads_text(self, paired: bool = False, round_bytes: int = 0):
+        """The reads that have at least one record in the full export, as FASTQ text formatted on the device (mlst_reads_text_open /
+        _next / _close; the rule: samout.reads_fastq_rule): a generator of `bytes`, whole four-line records in ascending read index,
+        one per round of at most round_bytes (0: 256 MiB) of bounded text and tables.  paired: the sample was submitted as pairs
+        (names r<pair>/1, /2).  With set_read_names the names are the reads' own.  The export is closed on exhaustion, on error and
+        when the generator is abandoned.  Reads the sample's state and changes none of it."""
+        try:
+            self._check(self.lib.mlst_reads_text_open(self._h, int(bool(paired)), int(round_bytes)), "mlst_reads_text_open")
+            buf = None
+            nb, nr, done = C.c_uint64(), C.c_uint64(), C.c_int()
+            while True:
+                # the size of the round that comes next, then the round itself
+                self._check(self.lib.mlst_reads_text_next(self._h, None, 0, C.byref(nb), C.byref(nr), C.byref(done)), "mlst_reads_text_next")
+                if done.value:
+                    break
+                need = int(nb.value)
+                if buf is None or len(buf) < need:
+                    buf = pinned_array(max(need, 1 << 16))
+                self._check(self.lib.mlst_reads_text_next(self._h, _ptr(buf), len(buf), C.byref(nb), C.byref(nr), C.byref(done)), "mlst_reads_text_next")
+                if nb.value:
+                    yield buf[:int(nb.value)].tobytes()
+                if done.value:
+                    break
+        finally:
+            self.lib.mlst_reads_text_close(self._h)
 
     # ---- typing tail on the device ----
     def typing_enqueue(self, penalty: int = 100, mincov: int = 1, none_char: str = "N"):

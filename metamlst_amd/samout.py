@@ -1,4 +1,5 @@
-"""The engine's alignments as SAM text (`cli type --write-sam` / `--write-sam-all`).
+"""The engine's alignments as SAM text and its aligned reads as FASTQ (`cli type --write-sam` / `--write-sam-all` / `--write-reads`;
+DESIGN.md section 6).
 
 The reference leaves a BAM of each sample's reads on the MLST loci behind (the bowtie2 run in front of metamlst.py); here the
 alignments are the engine's own, exported as records by Engine.export_alignments (mlst_alignments_export, include/mlst.h) and
@@ -52,7 +53,24 @@ the allele's letters of every D run.  With SEQ and the CIGAR it gives the allele
 for itself (samtools calmd -e, pysam get_reference_sequence) without the allele FASTA.  `write_sam` formats it here; the full
 export formats it on the device (Engine.set_export_md: mlst_set_export_md, csrc/aln_text.h).
 
-Not written: BAM / BGZF, the names of a reads BAM or of windows, pairing flags."""
+THE READS THEMSELVES (`cli type --write-reads`, `write_reads(path, eng, paired)`): the reads that align to the loci as FASTQ, what
+`bowtie2 --al FILE` writes and `samtools fastq` makes of the BAM in front of metamlst.py, formatted on the device
+(Engine.export_reads_text: mlst_reads_text_open / _next / _close, csrc/reads_text.h).  The rule, which `reads_fastq_rule` below states
+in plain Python (the device is held to it byte for byte; the command never calls it):
+
+  * which reads: a read index is written iff it has at least one record in the full export above -- "aligned at least once".  Records
+    that fail the AS / XM tag filter count, mlst_set_depth_cap is ignored, and a retained read without a record is not written;
+  * order: ascending read index, each read once, however many records it has;
+  * record: four lines with LF ends, `@<name>\n<SEQ>\n+\n<QUAL>\n`.  <name> is the QNAME of the SAM exports (r<k>, or under
+    --read-names the kept name and r<k> for a fallback); when the sample was submitted as pairs `/1` follows for an even read index and
+    `/2` for an odd one -- the mates share a QNAME there, and a FASTQ must tell them apart.  SEQ is the read as the engine holds it, in
+    read orientation and never turned to the reference strand (the prepared, cut read where --trim* / --adapter ran): ACGT, and N for
+    every other letter.  QUAL is chr(min(q, 93) + 33) of the stored Phred, `_QUAL_TAB`;
+  * mates: each mate is written on its own, and only if it has a record itself.  The engine does not retain a mate that hit nothing, so
+    the file is no `--al-conc`: the unaligned mate of an aligned read is not in it.
+
+Not written: BAM / BGZF, the names of a reads BAM or of windows, pairing flags, the mate that hit nothing, reads without a record,
+gzip'd FASTQ, the original letter case and IUPAC codes."""
 from __future__ import annotations
 
 import numpy as np
@@ -242,4 +260,33 @@ def write_sam_all(path: str, idx: AlleleIndex, eng, paired: bool, round_bytes: i
         for chunk in eng.export_sam_text(idx, paired=paired, round_bytes=round_bytes, md=md):
             f.write(chunk)
             n += chunk.count(b"\n")
+    return n
+
+
+# ------------------------------------------------------------------ the reads that align to the loci (--write-reads)
+_SEQ_TAB = bytes(c if c in b"ACGT" else (c - 32 if c in b"acgt" else 78) for c in range(256))      # the letters the engine holds: ACGT, else N
+
+
+def reads_fastq_rule(reads, aligned, paired: bool, names=None) -> list:
+    """The records of the reads export, one `bytes` of four lines per written read, in file order.  reads: read index -> (bases as
+    ASCII, raw Phred bytes) of the read as the engine holds it (a mapping or a sequence; the prepared, cut read where the engine
+    prepared it); aligned: the read indices that have a record in the full export, in any order and with repeats (one per record will
+    do); paired: the sample was submitted as pairs; names: {read index: name (bytes)} under --read-names, None: r<k>.  The
+    specification of csrc/reads_text.h and the tests' yardstick; the command never calls it."""
+    out = []
+    for ri in sorted(set(int(r) for r in aligned)):
+        bases, quals = reads[ri]
+        name = _qname(ri, paired, names).encode("ascii") + ((b"/2" if ri & 1 else b"/1") if paired else b"")
+        out.append(b"@" + name + b"\n" + bytes(bases).translate(_SEQ_TAB) + b"\n+\n" + bytes(quals).translate(_QUAL_TAB) + b"\n")
+    return out
+
+
+def write_reads(path: str, eng, paired: bool, round_bytes: int = 0) -> int:
+    """Write the reads of the sample on `eng` that have an alignment to `path` as FASTQ, as the device formats them, round by round
+    (a sample without such a read gets an empty file).  Returns the number of reads written."""
+    n = 0
+    with open(path, "wb") as f:
+        for chunk in eng.export_reads_text(paired=paired, round_bytes=round_bytes):
+            f.write(chunk)
+            n += chunk.count(b"\n") // 4
     return n
