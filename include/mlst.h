@@ -520,6 +520,53 @@ int mlst_set_read_adapters(mlst_handle* h, const char* adapters, uint32_t min_ov
 int mlst_get_read_adapters(mlst_handle* h, char* adapters, uint64_t cap, uint32_t* min_overlap, uint32_t* error_permille);
 int mlst_get_read_adapters_info(mlst_handle* h, uint64_t out[12]);
 
+/* ---- per-cycle read statistics counted on the device (off by default; csrc/read_stats.h; `cli type --read-stats`) ----------------------
+ * mlst_set_read_stats(h, 1): every read of FASTQ text is counted into per-cycle tables on the device, next to the parser, from bytes that
+ *   are already there (metamlst_amd.fastq.read_stats states the rule in Python).  Typing is untouched: packed rows, statistics, counters
+ *   and exports are the bytes they are without the switch.  Off: nothing is queued, nothing is allocated, and the kernels that run are
+ *   those that ran before the switch existed.
+ * The rule, per side (0 = unpaired reads and first mates, 1 = second mates) and stage, over the records counted:
+ *   reads, bases (the sum of lengths);
+ *   len_hist[0..320]: reads by length (a read of length 0 counts here and in reads only);
+ *   base[c][0..4], c = 0..319: letters A, C, G, T (either case) and other at cycle c -- "other" is every byte the packed rows mark as a
+ *     non-ACGT base (N, IUPAC codes, '.', anything else);
+ *   qual[c][0..93]: Phred at cycle c = min(clamp(character - phred_base, 0, 127), 93), the character taken as 0..255 and phred_base
+ *     that of mlst_set_read_prep (33, or 64); under 33 every character of 128 and above lands in bin 93;
+ *   gc_hist[0..100]: reads of length n >= 1 by (100 * (#G + #C)) / n;  readqual_hist[0..93]: reads of length n >= 1 by (sum of Phred) / n,
+ *     Phred as binned above, both in integers;
+ *   clamped_low: quality characters below phred_base (stage raw only: a Phred+33 file read as Phred+64 shows here).
+ * Sides: in a paired submission read 2k is side 0 and read 2k + 1 side 1; an unpaired submission counts into the current side,
+ *   mlst_set_read_stats_side(h, 0 | 1), which may change whenever no stream is open and is 0 again behind mlst_reset_sample (mate files
+ *   whose names differ go in as two unpaired texts and are still reported apart).
+ * Stages: 0 = raw, the record as it stands in the file (offsets and lengths as the parser leaves them); 1 = prepared, the read as it is
+ *   packed, behind mlst_set_read_prep's trims and mlst_set_read_adapters' cut, cycle 0 at the first remaining base.  With neither a trim
+ *   nor an adapter set only raw is counted (one launch per chunk, not two) and stage 1 is reported as stage 0's block.
+ * Entries it applies to: the five FASTQ entries (mlst_submit_fastq, _stream, _pair, _bgzf, _bgzf_pair).  While it is on every other way
+ *   of adding reads and mlst_set_read_tiling with a tile are refused with MLST_E_INVALID ("<entry>: read statistics are on
+ *   (mlst_set_read_stats) ..."): a report that silently covered part of a sample would be worse than a refusal.  It combines with
+ *   mlst_set_read_names, mlst_set_read_prep, mlst_set_read_adapters and the exports.  The switch may change only while the sample holds
+ *   no reads and no stream is open (mlst_set_read_prep's test).  mlst_reset_sample zeroes the tables and keeps the switch.
+ * mlst_read_stats_fetch(h, stage, side, out, cap): one block of MLST_RS_WORDS 64-bit counters (cap >= MLST_RS_WORDS, else MLST_E_INVALID):
+ *   out[MLST_RS_READS], out[MLST_RS_BASES], out[MLST_RS_CLAMPED_LOW], one word of padding, then len_hist at MLST_RS_LEN (321),
+ *   base[320][5] at MLST_RS_BASE, qual[320][94] at MLST_RS_QUAL, gc_hist at MLST_RS_GC (101), readqual_hist at MLST_RS_READQUAL (94).
+ *   All zero with the switch off.  An open BGZF piece is finished first.  A chunk refused as malformed is not counted.
+ * mlst_read_stats_info: out[0] = launches of stage raw, out[1] = launches of stage prepared, out[2] = table bytes allocated, out[3] = 0.
+ * No host synchronisation is added per chunk; mlst_get_kernel_time 20 is the counting kernel alone. */
+#define MLST_RS_READS 0
+#define MLST_RS_BASES 1
+#define MLST_RS_CLAMPED_LOW 2
+#define MLST_RS_LEN 4
+#define MLST_RS_BASE 325
+#define MLST_RS_QUAL 1925
+#define MLST_RS_GC 32005
+#define MLST_RS_READQUAL 32106
+#define MLST_RS_WORDS 32200
+int mlst_set_read_stats(mlst_handle* h, int on);
+int mlst_get_read_stats(mlst_handle* h, int* on);
+int mlst_set_read_stats_side(mlst_handle* h, int side);
+int mlst_read_stats_fetch(mlst_handle* h, int stage, int side, uint64_t* out, uint64_t cap);
+int mlst_read_stats_info(mlst_handle* h, uint64_t out[4]);
+
 /* ---- bowtie2's MD:Z field in the text export (off by default; csrc/aln_text.h; `cli type --md`) --------------------------------------
  * mlst_set_export_md(h, 1): every record of mlst_alignments_text_* carries MD:Z:<text> between NM:i and YT:Z:UU, bowtie2's place;
  *   columns 1-11 and every other field are the bytes they are without it.  With the switch off the export writes what it wrote
@@ -808,7 +855,7 @@ int mlst_set_profiling(mlst_handle* h, int on);   /* 0 = off, 1 = events + sieve
  * 13 = k_fqt_count (a BAM piece: k_bamt_count) + k_fqt_scan + k_fqt_add and 14 = k_fqt_emit (k_bamt_emit) (long reads cut into windows,
  * csrc/fastq_tile.h, csrc/bam_tile.h; outside 6); 15 = the line table of a SAM chunk (k_fq_count, k_fq_scan, k_fq_lines, k_sam_flags), 16 =
  * k_sam_accumulate and 17 = k_sam_pileup (csrc/sam_dev.h; two entries of 15 per chunk); 18 = k_rp_qtrim (csrc/read_prep.h) and 19 = k_ra_cut
- * (csrc/read_adapt.h), each alone (inside 6); 9 = k_route, 10 =
+ * (csrc/read_adapt.h), each alone (inside 6); 20 = k_rs_count (csrc/read_stats.h; alone, inside 6); 9 = k_route, 10 =
  * k_route_probe and 11 = k_route_verify, the three kernels of the routed sieve (inside 0) (events bracket the launch on the engine's
  * stream, so with several engines on one GPU they include the time a kernel queues behind another stream's kernel);
  * 7 = the sieve's execution window measured inside the kernel (wall clock at the first workgroup's start and the last

@@ -143,6 +143,14 @@ def _type_parser(sub):
     p.add_argument("--adapter-error-rate", dest="adapter_error_rate", default=None, type=float, metavar="X",
                    help="--adapter: at most floor(X * overlap) letters of the overlap may differ (0 to 0.5, default 0.1; kept as "
                         "round(1000 * X) permille)")
+    p.add_argument("--read-stats", dest="read_stats", action="store_true",
+                   help="FASTQ input: count per-cycle quality and base tables of the sample's reads on the GPU, next to the parser "
+                        "(csrc/read_stats.h; the rule: metamlst_amd.fastq.read_stats), as they stand in the file (raw) and, where --trim* / "
+                        "--adapter ran, as they are aligned (prepared); R1 and R2 apart.  After the .nfo, write <out>/<sample>.readstats.tsv "
+                        "(the format: metamlst_amd.fastq.read_stats_text; the project's own) and, unless --quiet, print one line per stage "
+                        "and side, and a hint when the qualities look like the other Phred base.  One sample on one GPU: plain, .gz and "
+                        "bgzip'd FASTQ, `a.fq,b.fq`, -2; refused with --alignments, --contigs, --long-reads, --long-bam-reads, a reads BAM, "
+                        "a folder or several samples, and --gpus N.  The .nfo, the --log file and every export do not change")
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -305,6 +313,17 @@ def run_type(a, argv=None) -> int:
             if on:
                 print("--adapter: " + why)
                 return 1
+    if getattr(a, "read_stats", False):      # (refused before any GPU use, each with its reason)
+        for on, why in ((a.alignments, "with --alignments the file holds alignments, not the reads of a FASTQ file"),
+                        (a.contigs, "--contigs cuts assemblies into windows, and an assembly has neither cycles nor qualities"),
+                        (a.long_reads, "--long-reads cuts reads into windows, and the tables hold the 320 cycles of a short read"),
+                        (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and the tables hold the 320 cycles of a short read"),
+                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the reads of a BAM are not counted: FASTQ input only"),
+                        (many, "it reports one sample: several samples or a folder are typed without it"),
+                        (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "the tables are one GPU's: a rank of --gpus N counts its own share of the reads only")):
+            if on:
+                print("--read-stats: " + why)
+                return 1
     if a.md and not (a.write_sam or a.write_sam_all):      # (with an export flag it is accepted and refused where that flag is: below)
         print("--md: it adds MD:Z to the records of an export: give --write-sam or --write-sam-all")
         return 1
@@ -373,6 +392,8 @@ def run_type(a, argv=None) -> int:
         eng.set_read_prep(**read_prep)
     if adapters:       # (likewise)
         eng.set_read_adapters(**adapters)
+    if getattr(a, "read_stats", False):      # (likewise: counted where the text is parsed)
+        eng.set_read_stats(True)
     # the built host index is kept next to the database (as the reference keeps <idx>.1.bt2: metamlst-index.py:224-225) unless a
     # species filter made this index a one-off or MLST_INDEX_CACHE=0
     ref_cache = (a.database + ".mlstref") if (not a.filter and os.environ.get("MLST_INDEX_CACHE", "1") != "0") else ""
@@ -484,7 +505,9 @@ def run_type(a, argv=None) -> int:
         return 0
     # FASTQ text goes to the GPU as is and is parsed there (mlst_submit_fastq); a reader thread stays two chunks ahead
     try:
-        submit_sample_files(eng, paths, paired, chunk_bytes, report=None if a.quiet else print, long_reads=long_reads, long_bam_reads=long_bam)
+        # --read-stats: mates whose names differ go in as unpaired text, the mate file counted into side 1 (R1 and R2 are reported apart)
+        side1_from = len(paths) - 1 if (getattr(a, "read_stats", False) and a.mates and not paired) else None
+        submit_sample_files(eng, paths, paired, chunk_bytes, report=None if a.quiet else print, long_reads=long_reads, long_bam_reads=long_bam, side1_from=side1_from)
     except CorruptInput as e:      # nothing of the sample is typed: no .nfo
         print(e, file=sys.stderr)
         database.closeConnection()
@@ -508,6 +531,8 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
         _say_read_prep(eng.read_prep_info(), 1)
     if rc == 0 and not a.quiet and _adapters_of(a, say=False):
         _say_read_adapters(eng.read_adapters_info(), eng.get_read_adapters()["adapters"], 1)
+    if rc == 0 and getattr(a, "read_stats", False):
+        _write_read_stats(a, eng)
     names, md = None, bool(getattr(a, "md", False))      # --md: MD:Z in both exports (write_sam on the host, the full export on the device)
     if rc == 0 and getattr(a, "read_names", False):      # the engine knows its switch: the text export needs no more than that
         names = eng.read_names()
@@ -572,6 +597,40 @@ def _adapters_of(a, say: bool = True):
             print("--adapter: %s" % e)
         return False
     return {"adapters": [x.decode() for x in ads], "min_overlap": 3 if mo is None else mo, "error_permille": permille}
+
+
+def read_stats_lines(stats: dict) -> list:
+    """One line per counted stage and side of Engine.read_stats(): reads, bases, mean length, share of bases >= Q20 and >= Q30, GC %,
+    share of non-ACGT bases"""
+    out = []
+    for stage in ["raw"] + (["prepared"] if stats.get("prepared_counted") else []):
+        for side in (0, 1):
+            t = stats[stage][side]
+            reads, bases = int(t["reads"]), int(t["bases"])
+            if side and not reads:
+                continue
+            q = t["qual"].sum(axis=0)
+            b = t["base"].sum(axis=0)
+            d = max(bases, 1)
+            out.append("read statistics (%s, side %d): %d reads, %d bases, mean length %.1f, >= Q20 %.1f %%, >= Q30 %.1f %%, GC %.1f %%, non-ACGT %.2f %%"
+                       % (stage, side, reads, bases, bases / max(reads, 1), 100.0 * int(q[20:].sum()) / d, 100.0 * int(q[30:].sum()) / d,
+                          100.0 * int(b[1] + b[2]) / d, 100.0 * int(b[4]) / d))
+    return out
+
+
+def _write_read_stats(a, eng) -> None:
+    """--read-stats: <out>/<sample>.readstats.tsv (fastq.read_stats_text) and, unless --quiet, the lines and the Phred hint"""
+    from .fastq import phred_hint, read_stats_text
+    stats = eng.read_stats()
+    name = sample_name(a.READS)
+    with open(a.o + "/" + name + ".readstats.tsv", "wb") as f:
+        f.write(read_stats_text(stats, name))
+    if not a.quiet:
+        for line in read_stats_lines(stats):
+            print(line, flush=True)
+    hint = phred_hint(stats)
+    if hint:
+        print(hint, flush=True)
 
 
 def _sum_adapter_infos(infos) -> dict:
@@ -664,13 +723,14 @@ def submit_contigs(eng, path: str, tile) -> int:
 
 
 def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader=None, report=None, tile=None, long_reads=None,
-                        long_bam_reads=None) -> None:
+                        long_bam_reads=None, side1_from=None) -> None:
     """All reads of one sample's file(s) into one engine: FASTQ (first_reader: open_sample_reader(paths, ...), if opened ahead), or
     BAMs whose records are taken as reads (report: see submit_bam_reads).  tile = (read_len, stride, min_len): the files are
     assemblies (FASTA), cut into windows on the GPU (submit_contigs).  long_reads = (read_len, stride): unpaired FASTQ whose records
     longer than read_len are cut into windows on the GPU (Engine.set_read_tiling: plain text and bgzip on the device path, single-
     stream .gz inflated on the host as always and cut on the device); report gets one line on what was cut.  long_bam_reads =
-    (read_len, stride): the files are BAMs of unpaired reads, cut into windows the same way (submit_bam_reads)."""
+    (read_len, stride): the files are BAMs of unpaired reads, cut into windows the same way (submit_bam_reads).  side1_from = k: under
+    Engine.set_read_stats the unpaired files from paths[k] on count into side 1 (a mate file whose names differ from its first file's)."""
     if long_bam_reads is not None:
         if paired or not all(_is_reads_bam(p) for p in paths):
             raise ValueError("long BAM reads are the unpaired reads of BAM files")
@@ -702,6 +762,8 @@ def submit_sample_files(eng, paths, paired: bool, chunk_bytes: int, first_reader
         release_buffers(ring)
         return
     for k, path in enumerate(paths):
+        if side1_from is not None and k == side1_from:
+            eng.set_read_stats_side(1)
         if _is_reads_bam(path):      # a BAM that holds reads: inflated, chosen, strand-corrected and packed on the GPU
             submit_bam_reads(eng, path, report)
             continue

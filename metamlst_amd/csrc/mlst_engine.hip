@@ -3691,6 +3691,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "read_names.h"
 #include "read_prep.h"
 #include "read_adapt.h"
+#include "read_stats.h"
 #include "aln_text.h"
 #include "reads_text.h"
 
@@ -3798,7 +3799,7 @@ struct mlst_handle {
     GraphSlot g_submit, g_typing; bool use_graphs = true;
     std::vector<EvPair> events;
     std::vector<hipEvent_t> ev_pool;
-    double k_ms[20] = {0}; u64 k_n[20] = {0};      // see mlst_get_kernel_time
+    double k_ms[21] = {0}; u64 k_n[21] = {0};      // see mlst_get_kernel_time
     double wall_khz = 100000.0;                  // wall_clock64 rate (hipDeviceAttributeWallClockRate)
     struct BamStream* bam = nullptr;             // BAM input (mlst_bam_open / mlst_submit_bam_bgzf), allocated by the first stream
     u32 bam_force_miss = 0; u64 bam_max_entries = 0;      // mlst_debug_bam_split, mlst_bam_set_capacity
@@ -3850,6 +3851,10 @@ struct mlst_handle {
     // 3' adapters removed before the reads are packed (mlst_set_read_adapters; csrc/read_adapt.h): the switch, the adapters as the kernel
     // takes them and as the caller gave them (upper-cased), the counters on the device -- allocated by the first submission that cuts
     struct { bool on = false; RaSet set = {}; std::string text; RaCtr* d_ctr = nullptr; } ra;
+    // per-cycle read statistics (mlst_set_read_stats; csrc/read_stats.h): the switch, the side unpaired submissions count into, the
+    // tables on the device ([stage][side][RS_WORDS]) -- allocated by the first submission under the switch --, the launches per stage
+    // since the last reset and the device's CU count (the grid is at most one workgroup per CU)
+    struct { bool on = false; u32 side = 0; u64* d_tab = nullptr; u64 launches[2] = {0, 0}; int n_cu = 0; } rs;
 };
 
 static std::string g_create_err;
@@ -3870,6 +3875,7 @@ static bool bam_is_open(const mlst_handle* h);
 static int rn_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_names is on: an entry that carries no names is refused
 static int rp_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_prep is on: an entry that does not prepare its reads is refused
 static int ra_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_adapters is on: an entry that does not cut its reads is refused
+static int rs_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_stats is on: an entry whose reads are not counted is refused
 static void at_free(mlst_handle* h);      // the per-export tables of mlst_alignments_text_*
 static const char* bam_kind(const mlst_handle* h);      // "BAM" or "SAM": what the open stream of ready-made alignments takes
 template <typename T> static hipError_t dmalloc(T** p, u64 n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
@@ -4040,7 +4046,7 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     if (h->copy_stream) hipStreamDestroy(h->copy_stream);
     hipFree(h->d_cand); hipFree(h->d_in_bases); hipFree(h->d_in_quals); hipFree(h->d_in_off);
     hipFree(h->d_fq_slot[0]); hipFree(h->d_fq_slot[1]); hipFree(h->d_fq_nl[0]); hipFree(h->d_fq_nl[1]); hipFree(h->d_fq_blk); hipFree(h->d_fq_lines); hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); hipFree(h->d_fq_meta);
-    hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta); hipFree(h->rp.d_ctr); hipFree(h->ra.d_ctr);
+    hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta); hipFree(h->rp.d_ctr); hipFree(h->ra.d_ctr); hipFree(h->rs.d_tab);
     hipFree(h->fa.d_desc); hipFree(h->fa.d_meta); hipFree(h->fa.d_flat); hipFree(h->fa.d_kind); hipFree(h->fa.d_cseq); hipFree(h->fa.d_chdr); hipFree(h->fa.d_cstart); hipFree(h->fa.d_wcnt);
     if (h->fa.h_fa) hipHostFree(h->fa.h_fa);
     hipFree(h->tile.d_desc); hipFree(h->tile.d_meta); hipFree(h->tile.d_rlen); hipFree(h->tile.d_wex); hipFree(h->tile.d_gsum); hipFree(h->tile.d_soff); hipFree(h->tile.d_qoff);
@@ -4068,6 +4074,8 @@ static int reset_sample_state(mlst_handle* h) {
     if (h->rn.d_ctr) HIPCHK(h, hipMemsetAsync(h->rn.d_ctr, 0, sizeof(RnCtr), h->stream));      // the name arena is empty; the switch stays
     if (h->rp.d_ctr) HIPCHK(h, hipMemsetAsync(h->rp.d_ctr, 0, sizeof(RpCtr), h->stream));      // mlst_set_read_prep: the counters are the sample's; the setting stays
     if (h->ra.d_ctr) HIPCHK(h, hipMemsetAsync(h->ra.d_ctr, 0, sizeof(RaCtr), h->stream));      // mlst_set_read_adapters: likewise
+    if (h->rs.d_tab) HIPCHK(h, hipMemsetAsync(h->rs.d_tab, 0, 4ull * RS_WORDS * 8, h->stream));      // mlst_set_read_stats: the tables are the sample's; the switch stays, the side is 0 again
+    h->rs.side = 0; h->rs.launches[0] = h->rs.launches[1] = 0;
     h->reads_seen = 0; h->fq_carry_len = 0; h->max_wpr = 0;
     h->last_pack.n_reads = 0; h->last_pack.wpr = h->last_pack.qstride = 0;
     for (u64& x : h->tile.info) x = 0;
@@ -4683,6 +4691,7 @@ extern "C" int mlst_submit_packed_device(mlst_handle* h, const uint32_t* d_packe
     { int rc_ = rn_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
+    { int rc_ = rs_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     return submit_impl(h, d_packed, d_qrows, d_lens, n_reads, wpr, qstride, paired, 0);
 }
 static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* d_qrows, const uint16_t* d_lens,
@@ -4832,6 +4841,7 @@ extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, 
     { int rc_ = rn_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
+    { int rc_ = rs_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     hipSetDevice(h->device);
@@ -4850,6 +4860,7 @@ extern "C" int mlst_submit_reads(mlst_handle* h, const uint8_t* bases, const uin
     { int rc_ = rn_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
+    { int rc_ = rs_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (n_reads == 0) return MLST_OK;
@@ -4911,12 +4922,38 @@ static int ra_refuse(mlst_handle* h, const char* entry) {
     if (h && h->ra.on) return fail(h, MLST_E_INVALID, "%s: adapter removal is on (mlst_set_read_adapters) and only the FASTQ text and BGZF entries apply it", entry);
     return MLST_OK;
 }
+// mlst_set_read_stats (csrc/read_stats.h): with the switch on, reads come from FASTQ text only, where they are counted
+static int rs_refuse(mlst_handle* h, const char* entry) {
+    if (h && h->rs.on) return fail(h, MLST_E_INVALID, "%s: read statistics are on (mlst_set_read_stats) and only the FASTQ text and BGZF entries count their reads", entry);
+    return MLST_OK;
+}
+// one launch of k_rs_count over the chunk's reads as offsets and lengths stand now: stage 0 in front of k_rp_qtrim (which rewrites the
+// offsets in place), stage 1 behind k_ra_cut.  At most one workgroup per CU, fewer for few reads (each flushes its LDS tables once); a
+// paired chunk takes an even number, a workgroup counting one side
+static int rs_launch(mlst_handle* h, u64 n_reads, u32* d_flags, int paired, int stage) {
+    auto& S = h->rs;
+    if (!S.d_tab) { HIPCHK(h, dmalloc(&S.d_tab, 4ull * RS_WORDS)); HIPCHK(h, hipMemsetAsync(S.d_tab, 0, 4ull * RS_WORDS * 8, h->stream)); }
+    if (!S.n_cu) { HIPCHK(h, hipDeviceGetAttribute(&S.n_cu, hipDeviceAttributeMultiprocessorCount, h->device)); if (S.n_cu < 2) S.n_cu = 2; }
+    u64 want = (n_reads + RS_WG_READS - 1) / RS_WG_READS; if (want < 1) want = 1;
+    u32 grid = (u32)std::min<u64>(want, (u64)S.n_cu);
+    if (paired) { grid = (grid + 1) & ~1u; if (grid > (u32)S.n_cu) grid -= 2; if (grid < 2) grid = 2; }
+    u64* const tab = S.d_tab + (u64)stage * 2 * RS_WORDS;
+    Prof pf(h, 20);      // (mlst_get_kernel_time 20: k_rs_count alone)
+    if (h->rp.set.phred_base == 64) hipLaunchKernelGGL(k_rs_count<64>, dim3(grid), dim3(1024), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, (const u64*)h->d_fq_qoff,
+                                                       (const u16*)h->d_lens, n_reads, paired ? 1u : 0u, S.side, stage == 0 ? 1u : 0u, (const u32*)d_flags, tab);
+    else hipLaunchKernelGGL(k_rs_count<33>, dim3(grid), dim3(1024), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, (const u64*)h->d_fq_qoff,
+                            (const u16*)h->d_lens, n_reads, paired ? 1u : 0u, S.side, stage == 0 ? 1u : 0u, (const u32*)d_flags, tab);
+    S.launches[stage]++;
+    return MLST_OK;
+}
 // the parser has left offsets and lengths of n_reads reads of h->d_fq_text and the longest length in flags[0]: the trims, queued in
 // front of the read-back of the flags, so that the longest length the host reads is the longest prepared one (no synchronisation added)
 // Behind them, mlst_set_read_adapters' cut (csrc/read_adapt.h): flags[0] is zeroed in front of either kernel, so the last one alone feeds what is read
-static int rp_apply(mlst_handle* h, u64 n_reads, u32* d_flags) {
+// mlst_set_read_stats: the raw tables are counted in front of the trims, the prepared ones behind the cut, only when either ran
+static int rp_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
     const RpSet& P = h->rp.set;
     const bool trims = h->rp.on && (P.trim5 | P.trim3 | P.trim_qual);      // (the Phred base alone is k_pack_text's)
+    if (h->rs.on) { int rc = rs_launch(h, n_reads, d_flags, paired, 0); if (rc) return rc; }
     if (!trims && !h->ra.on) return MLST_OK;
     if (trims && !h->rp.d_ctr) { HIPCHK(h, dmalloc(&h->rp.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->rp.d_ctr, 0, sizeof(RpCtr), h->stream)); }
     if (h->ra.on && !h->ra.d_ctr) { HIPCHK(h, dmalloc(&h->ra.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->ra.d_ctr, 0, sizeof(RaCtr), h->stream)); }
@@ -4934,6 +4971,7 @@ static int rp_apply(mlst_handle* h, u64 n_reads, u32* d_flags) {
         hipLaunchKernelGGL(k_ra_cut, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, h->d_lens, n_reads, h->ra.set,
                            d_flags, h->ra.d_ctr);
     }
+    if (h->rs.on) return rs_launch(h, n_reads, d_flags, paired, 1);
     return MLST_OK;
 }
 // the counters of the name arena; an arena that was too small is reported here (the next entry that looks)
@@ -5007,7 +5045,7 @@ static int fastq_pipeline(mlst_handle* h, u64 n_bytes, int paired, bool whole, u
                                  h->d_fq_soff, h->d_fq_qoff, h->d_lens, d_flags, pair_k, h->tile.read_len);
     else hipLaunchKernelGGL(k_fq_records<false>, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, h->d_fq_text, (u64)n_bytes, h->d_fq_lines, n_lines, n_reads,
                             h->d_fq_soff, h->d_fq_qoff, h->d_lens, d_flags, pair_k, 0u);
-    rc = rp_apply(h, n_reads, d_flags); if (rc) return rc;      // mlst_set_read_prep (never with a tile)
+    rc = rp_apply(h, n_reads, d_flags, paired || pair_boundary); if (rc) return rc;      // mlst_set_read_prep (never with a tile)
     u32 flags[2] = {0, 0};
     HIPCHK(h, hipMemcpyAsync(flags, d_flags, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -5045,7 +5083,7 @@ static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, i
     if (!h->rn.on) HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
     if (n_reads_out) *n_reads_out = n_reads;
     h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
-    if (!h->rn.on && (h->rp.on || h->ra.on)) return submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);      // (the public entry refuses under mlst_set_read_prep / mlst_set_read_adapters)
+    if (!h->rn.on && (h->rp.on || h->ra.on || h->rs.on)) return submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);      // (the public entry refuses under mlst_set_read_prep / mlst_set_read_adapters)
     if (!h->rn.on) return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired);
     // mlst_set_read_names: the text outlives pass 1 of its chunk -- the names of the reads it retained are copied out of the header
     // lines (csrc/read_names.h), behind the submission and outside its captured graph, and only then is the slot released
@@ -5203,6 +5241,7 @@ extern "C" int mlst_submit_packed_host(mlst_handle* h, const uint32_t* packed, c
     { int rc_ = rn_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
+    { int rc_ = rs_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (!packed || !qrows || !lens) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -5703,7 +5742,7 @@ static int bzp_finish_impl(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
         int rc = ensure_pack_buffers(h, n_reads, 2, 8); if (rc) return rc;
         hipLaunchKernelGGL(k_fq_pair_records, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)slot, (const u64*)lines1, (const u64*)lines2, k,
                            h->d_fq_soff, h->d_fq_qoff, h->d_lens, reinterpret_cast<u32*>(h->d_pr_meta + 1), h->d_pr_meta + 2);
-        rc = rp_apply(h, n_reads, reinterpret_cast<u32*>(h->d_pr_meta + 1)); if (rc) return rc;      // mlst_set_read_prep
+        rc = rp_apply(h, n_reads, reinterpret_cast<u32*>(h->d_pr_meta + 1), 1); if (rc) return rc;      // mlst_set_read_prep
         u64 back[3] = {0, 0, 0};      // flags, then the two cuts
         HIPCHK(h, hipMemcpyAsync(back, h->d_pr_meta + 1, 24, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -6533,6 +6572,7 @@ extern "C" int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip
     { int rc_ = rn_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
+    { int rc_ = rs_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6579,6 +6619,7 @@ extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n
     { int rc_ = rn_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = rp_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
+    { int rc_ = rs_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6751,6 +6792,7 @@ extern "C" int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t 
     if (read_len) { int rc_ = rn_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window has no name)
     if (read_len) { int rc_ = rp_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window is cut from the record as it stands)
     if (read_len) { int rc_ = ra_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
+    if (read_len) { int rc_ = rs_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
     // (a reads stream took its tile when it was opened: include/mlst.h gives one message for every stream of reads)
     if (bam_is_open(h) && h->bam->reads) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (the reads stream of a BAM: its last chunk was not marked final)");
@@ -6876,6 +6918,50 @@ extern "C" int mlst_get_read_adapters_info(mlst_handle* h, uint64_t out[12]) {
     }
     out[0] = c.trimmed; out[1] = c.removed; out[2] = c.emptied; out[3] = h->ra.set.K;
     for (int k = 0; k < RA_MAX_ADAPTERS; k++) out[4 + k] = c.per_adapter[k];
+    return MLST_OK;
+}
+// per-cycle read statistics (include/mlst.h; csrc/read_stats.h): the switch's life cycle is mlst_set_read_prep's
+extern "C" int mlst_set_read_stats(mlst_handle* h, int on) {
+    if (!h) return MLST_E_INVALID;
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
+    if ((on != 0) != h->rs.on && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_stats changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
+    if (on && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_stats: mlst_set_read_tiling is on and the windows of a read would be counted, not the read");
+    h->rs.on = on != 0;
+    return MLST_OK;
+}
+extern "C" int mlst_get_read_stats(mlst_handle* h, int* on) {
+    if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
+    *on = h->rs.on ? 1 : 0;
+    return MLST_OK;
+}
+extern "C" int mlst_set_read_stats_side(mlst_handle* h, int side) {
+    if (!h) return MLST_E_INVALID;
+    if (side != 0 && side != 1) return fail(h, MLST_E_INVALID, "mlst_set_read_stats_side: side is %d, not 0 or 1", side);
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
+    h->rs.side = (u32)side;
+    return MLST_OK;
+}
+extern "C" int mlst_read_stats_fetch(mlst_handle* h, int stage, int side, uint64_t* out, uint64_t cap) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    if ((stage != 0 && stage != 1) || (side != 0 && side != 1)) return fail(h, MLST_E_INVALID, "mlst_read_stats_fetch: stage %d, side %d: each is 0 or 1", stage, side);
+    if (cap < RS_WORDS) return fail(h, MLST_E_INVALID, "mlst_read_stats_fetch: the buffer holds %llu words, %d are needed", (unsigned long long)cap, RS_WORDS);
+    hipSetDevice(h->device);
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
+    memset(out, 0, (size_t)RS_WORDS * 8);
+    if (!h->rs.on || !h->rs.d_tab) return MLST_OK;
+    if (stage == 1 && !h->rs.launches[1]) stage = 0;      // neither a trim nor an adapter ran: the prepared read is the raw one
+    HIPCHK(h, hipMemcpyAsync(out, h->rs.d_tab + ((u64)stage * 2 + (u64)side) * RS_WORDS, (size_t)RS_WORDS * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLST_OK;
+}
+extern "C" int mlst_read_stats_info(mlst_handle* h, uint64_t out[4]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }
+    const bool live = h->rs.on && h->rs.d_tab;
+    out[0] = live ? h->rs.launches[0] : 0; out[1] = live ? h->rs.launches[1] : 0; out[2] = h->rs.d_tab ? 4ull * RS_WORDS * 8 : 0; out[3] = 0;
     return MLST_OK;
 }
 // MD:Z in the text export (include/mlst.h): no part of the sample's state; mlst_alignments_text_open reads it
@@ -7918,13 +8004,13 @@ extern "C" int mlst_get_items(mlst_handle* h, mlst_item* out, uint64_t cap, uint
 
 extern "C" int mlst_set_profiling(mlst_handle* h, int on) { if (!h) return MLST_E_INVALID; drain_events(h); h->profiling = on == 1; h->window = on != 0; return MLST_OK; }
 extern "C" int mlst_get_kernel_time(mlst_handle* h, int which, double* total_ms, uint64_t* launches) {
-    if (!h || which < 0 || which >= 20) return MLST_E_INVALID;
+    if (!h || which < 0 || which >= 21) return MLST_E_INVALID;
     hipSetDevice(h->device); drain_events(h);
     if (total_ms) *total_ms = h->k_ms[which];
     if (launches) *launches = h->k_n[which];
     return MLST_OK;
 }
-extern "C" int mlst_reset_kernel_time(mlst_handle* h) { if (!h) return MLST_E_INVALID; drain_events(h); for (int i = 0; i < 20; i++) { h->k_ms[i] = 0; h->k_n[i] = 0; } return MLST_OK; }
+extern "C" int mlst_reset_kernel_time(mlst_handle* h) { if (!h) return MLST_E_INVALID; drain_events(h); for (int i = 0; i < 21; i++) { h->k_ms[i] = 0; h->k_n[i] = 0; } return MLST_OK; }
 extern "C" int mlst_get_index_bytes(mlst_handle* h, uint64_t out[4]) {
     if (!h || !out) return MLST_E_INVALID;
     out[0] = h->bytes_arena + h->bytes_hap; out[1] = h->bytes_sieve; out[2] = h->bytes_table; out[3] = (u64)(h->bitmap_fill * 1e6); return MLST_OK;

@@ -174,6 +174,11 @@ def load_library(path: str | None = None):
         "mlst_set_read_adapters": (C.c_int, [H, C.c_char_p, C.c_uint32, C.c_uint32]),
         "mlst_get_read_adapters": (C.c_int, [H, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "mlst_get_read_adapters_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "mlst_set_read_stats": (C.c_int, [H, C.c_int]),
+        "mlst_get_read_stats": (C.c_int, [H, C.POINTER(C.c_int)]),
+        "mlst_set_read_stats_side": (C.c_int, [H, C.c_int]),
+        "mlst_read_stats_fetch": (C.c_int, [H, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint64]),
+        "mlst_read_stats_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_set_export_md": (C.c_int, [H, C.c_int]),
         "mlst_get_export_md": (C.c_int, [H, C.POINTER(C.c_int)]),
         "mlst_read_names_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
@@ -883,6 +888,49 @@ class Engine:
         out = (C.c_uint64 * 12)()
         self._check(self.lib.mlst_get_read_adapters_info(self._h, out), "mlst_get_read_adapters_info")
         return {"trimmed": int(out[0]), "bases_removed": int(out[1]), "emptied": int(out[2]), "per_adapter": [int(out[4 + k]) for k in range(int(out[3]))]}
+
+    def set_read_stats(self, on: bool = True) -> None:
+        """Count per-cycle quality and base tables of every read of FASTQ text on the GPU, next to the parser (mlst_set_read_stats; off
+        by default; the rule: fastq.read_stats).  Typing is untouched.  FASTQ text and BGZF entries only -- every other way of adding
+        reads is refused while it is on; may change only while the sample holds no reads and no stream is open."""
+        self._check(self.lib.mlst_set_read_stats(self._h, 1 if on else 0), "mlst_set_read_stats")
+
+    def get_read_stats(self) -> bool:
+        on = C.c_int()
+        self._check(self.lib.mlst_get_read_stats(self._h, C.byref(on)), "mlst_get_read_stats")
+        return bool(on.value)
+
+    def set_read_stats_side(self, side: int) -> None:
+        """The side (0 or 1) unpaired submissions count into from here on (mlst_set_read_stats_side): 1 in front of a mate file that
+        goes in as unpaired text.  Refused while a stream is open; 0 again behind reset_sample."""
+        self._check(self.lib.mlst_set_read_stats_side(self._h, int(side)), "mlst_set_read_stats_side")
+
+    def read_stats(self) -> dict:
+        """{"raw": [side 0, side 1], "prepared": [side 0, side 1]}: the tables since the last reset_sample as dicts shaped as
+        fastq.read_stats': reads, bases, clamped_low (int), len_hist (321), base (320 x 5), qual (320 x 94), gc_hist (101),
+        readqual_hist (94) as numpy int64.  With neither a trim nor an adapter set "prepared" is the raw block.  All zero with the
+        switch off."""
+        from .fastq import RS_BASE, RS_GC, RS_LEN, RS_QUAL, RS_READQUAL, RS_WORDS
+        out = {}
+        for stage, name in enumerate(("raw", "prepared")):
+            out[name] = []
+            for side in (0, 1):
+                w = np.zeros(RS_WORDS, np.uint64)
+                self._check(self.lib.mlst_read_stats_fetch(self._h, stage, side, w.ctypes.data_as(C.POINTER(C.c_uint64)), RS_WORDS), "mlst_read_stats_fetch")
+                w = w.astype(np.int64)
+                out[name].append({"reads": int(w[0]), "bases": int(w[1]), "clamped_low": int(w[2]), "len_hist": w[RS_LEN:RS_BASE].copy(),
+                                  "base": w[RS_BASE:RS_QUAL].reshape(320, 5).copy(), "qual": w[RS_QUAL:RS_GC].reshape(320, 94).copy(),
+                                  "gc_hist": w[RS_GC:RS_READQUAL].copy(), "readqual_hist": w[RS_READQUAL:RS_WORDS].copy()})
+        out["phred_base"] = 64 if self.get_read_prep()["phred64"] else 33      # (what fastq.read_stats_text and fastq.phred_hint ask for)
+        out["prepared_counted"] = self.read_stats_info()["prepared_launches"] > 0
+        return out
+
+    def read_stats_info(self) -> dict:
+        """Launches of the counting kernel per stage since the last reset_sample and the bytes of the tables on the device; all zero
+        with the switch off (nothing is queued or allocated)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.mlst_read_stats_info(self._h, out), "mlst_read_stats_info")
+        return {"raw_launches": int(out[0]), "prepared_launches": int(out[1]), "table_bytes": int(out[2])}
 
     def set_export_md(self, on: bool = True) -> None:
         """export_sam_text / write_sam_all write bowtie2's MD:Z field between NM:i and YT:Z, formatted on the GPU (mlst_set_export_md; off

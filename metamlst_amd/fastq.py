@@ -858,6 +858,142 @@ def trim_adapters(text: bytes, adapters, min_overlap: int = 3, error_permille: i
     return b"".join(out), info
 
 
+# the table block of mlst_read_stats_fetch in 64-bit words (MLST_RS_* of include/mlst.h): reads, bases, clamped_low, padding, then
+RS_LEN, RS_BASE, RS_QUAL, RS_GC, RS_READQUAL, RS_WORDS = 4, 325, 1925, 32005, 32106, 32200
+_RS_COL = np.full(256, 4, np.int64)      # letter -> column of base[c]: A, C, G, T in either case, 4 = every other byte (pack_group's N bit)
+for _k, _c in enumerate(b"ACGT"):
+    _RS_COL[_c] = _RS_COL[_c | 0x20] = _k
+
+
+def read_stats_empty() -> dict:
+    """One side's tables, all zero"""
+    return {"reads": 0, "bases": 0, "clamped_low": 0, "len_hist": np.zeros(321, np.int64), "base": np.zeros((320, 5), np.int64),
+            "qual": np.zeros((320, 94), np.int64), "gc_hist": np.zeros(101, np.int64), "readqual_hist": np.zeros(94, np.int64)}
+
+
+def read_stats_sum(a: dict, b: dict) -> dict:
+    """The tables of two texts counted into one side: every figure is additive"""
+    return {k: a[k] + b[k] for k in a}
+
+
+def read_stats_equal(a: dict, b: dict, skip=()) -> bool:
+    return all(np.array_equal(a[k], b[k]) for k in a if k not in skip)
+
+
+def read_stats(text: bytes, phred64: bool = False, side: int = 0, paired: bool = False) -> list:
+    """The tables Engine.read_stats() holds for FASTQ text under Engine.set_read_stats(): [side 0, side 1], each a dict of reads, bases,
+    clamped_low (int) and len_hist (321), base (320 x 5), qual (320 x 94), gc_hist (101), readqual_hist (94) as numpy int64.  This is the
+    rule mlst_set_read_stats counts by on the device (csrc/read_stats.h); it serves the tests and the docs -- the command never calls it.
+    Sides: paired -- record 2k is side 0 and record 2k + 1 side 1 (interleaved text); else every record counts into `side`.
+    Per side, over its records (a record of more than 320 bases is refused, as the engine refuses it):
+      reads, bases = the sum of lengths; len_hist[n]: reads of length n (a read of length 0 counts here and in reads only);
+      base[c][0..4]: letters A, C, G, T (either case) and other at cycle c -- other is every byte the packed rows mark non-ACGT;
+      qual[c][v]: v = min(clamp(character - base, 0, 127), 93) at cycle c, base 64 under phred64, else 33, the character 0..255
+        (under base 33 every character of 128 and above lands in bin 93);
+      gc_hist[(100 * (#G + #C)) // n] and readqual_hist[(sum of v) // n] for reads of length n >= 1;
+      clamped_low: quality characters below the base.
+    The stage "raw" of the engine is read_stats(text, phred64=...) of the file; "prepared" is
+    read_stats(trim_adapters(prep_fastq(text, ...)[0], ...)[0]) with base 33 (prep_fastq writes Phred + 33)."""
+    base = 64 if phred64 else 33
+    if side not in (0, 1):
+        raise ValueError("side is %r, not 0 or 1" % (side,))
+    lines = bytes(text).split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    if len(lines) % 4:
+        raise ValueError("FASTQ text holds %d lines: not a whole number of 4-line records" % len(lines))
+    if paired and len(lines) % 8:
+        raise ValueError("paired FASTQ text holds %d records: not whole pairs" % (len(lines) // 4))
+    out = [read_stats_empty(), read_stats_empty()]
+    cyc, col, val = ([], []), ([], []), ([], [])
+    for k in range(0, len(lines), 4):
+        s, ql = (x[:-1] if x.endswith(b"\r") else x for x in (lines[k + 1], lines[k + 3]))
+        if len(s) != len(ql):
+            raise ValueError("FASTQ record with different sequence and quality lengths: %r" % lines[k][:60])
+        n = len(s)
+        if n > 320:
+            raise ValueError("a FASTQ read is longer than 320 bases")
+        sd = (k // 4) & 1 if paired else side
+        t = out[sd]
+        t["reads"] += 1
+        t["bases"] += n
+        t["len_hist"][n] += 1
+        if not n:
+            continue
+        c = _RS_COL[np.frombuffer(s, np.uint8)]
+        ch = np.frombuffer(ql, np.uint8).astype(np.int64)
+        v = np.minimum(np.clip(ch - base, 0, 127), 93)
+        t["clamped_low"] += int((ch < base).sum())
+        t["gc_hist"][(100 * int(((c == 1) | (c == 2)).sum())) // n] += 1
+        t["readqual_hist"][int(v.sum()) // n] += 1
+        cyc[sd].append(np.arange(n)); col[sd].append(c); val[sd].append(v)
+    for sd in (0, 1):
+        if cyc[sd]:
+            cc, bb, vv = np.concatenate(cyc[sd]), np.concatenate(col[sd]), np.concatenate(val[sd])
+            out[sd]["base"] += np.bincount(cc * 5 + bb, minlength=1600).reshape(320, 5)
+            out[sd]["qual"] += np.bincount(cc * 94 + vv, minlength=320 * 94).reshape(320, 94)
+    return out
+
+
+def read_stats_text(stats: dict, sample: str, phred64: bool | None = None, prepared: bool | None = None) -> bytes:
+    """The report file of `cli type --read-stats`, <out>/<sample>.readstats.tsv.  stats: {"raw": [side 0, side 1], "prepared": [...]}
+    as Engine.read_stats() returns it (its keys "phred_base" and "prepared_counted" stand in for phred64 / prepared when those are
+    None).  The format is the project's own and claims no other tool's bytes: integers only, tab-separated, LF line ends.
+      #metamlst-readstats<TAB>1                      format version
+      #sample<TAB><sample>
+      #phred_base<TAB>33 | 64
+      #stages<TAB>raw | raw,prepared                 the stages that were counted (prepared: only where a trim or an adapter ran)
+      #columns<TAB>table<TAB>stage<TAB>side<TAB>index<TAB>values
+    then, per counted stage (raw, prepared) and side (0; 1 only where it holds reads), rows `table stage side index values...`:
+      total    index 0, values reads, bases, clamped_low
+      len      index = length, value = reads of that length; non-zero rows only
+      base     index = cycle 0 .. longest read - 1, values A, C, G, T, other
+      qual     index = cycle 0 .. longest read - 1, values for Phred 0 .. the highest non-empty bin of that stage's and side's table
+      gc       index = GC percent 0 .. 100, value = reads; non-zero rows only
+      readqual index = mean Phred, value = reads; non-zero rows only"""
+    base = (64 if phred64 else 33) if phred64 is not None else int(stats.get("phred_base", 33))
+    with_prep = bool(stats.get("prepared_counted", False)) if prepared is None else bool(prepared)
+    stages = ["raw"] + (["prepared"] if with_prep else [])
+    out = ["#metamlst-readstats\t1", "#sample\t%s" % sample, "#phred_base\t%d" % base, "#stages\t%s" % ",".join(stages),
+           "#columns\ttable\tstage\tside\tindex\tvalues"]
+    for stage in stages:
+        for side in (0, 1):
+            t = stats[stage][side]
+            if side and not int(t["reads"]):
+                continue
+            key = "\t%s\t%d\t" % (stage, side)
+            out.append("total" + key + "0\t%d\t%d\t%d" % (int(t["reads"]), int(t["bases"]), int(t["clamped_low"])))
+            nz = np.flatnonzero(t["len_hist"])
+            out += ["len" + key + "%d\t%d" % (i, int(t["len_hist"][i])) for i in nz]
+            longest = int(nz[-1]) if len(nz) else 0
+            out += ["base" + key + "%d\t" % c + "\t".join(str(int(x)) for x in t["base"][c]) for c in range(longest)]
+            qn = np.flatnonzero(t["qual"].sum(axis=0))
+            top = int(qn[-1]) + 1 if len(qn) else 0
+            out += ["qual" + key + "%d\t" % c + "\t".join(str(int(x)) for x in t["qual"][c][:top]) for c in range(longest)]
+            out += ["gc" + key + "%d\t%d" % (i, int(t["gc_hist"][i])) for i in np.flatnonzero(t["gc_hist"])]
+            out += ["readqual" + key + "%d\t%d" % (i, int(t["readqual_hist"][i])) for i in np.flatnonzero(t["readqual_hist"])]
+    return ("\n".join(out) + "\n").encode()
+
+
+def phred_hint(stats: dict, phred64: bool | None = None) -> str | None:
+    """One sentence of advice on the Phred base from the raw tables of both sides, or None.  Under base 33: at least 1,000 bases
+    counted and no quality below Phred 31 (character '@') -- the file looks like Phred+64.  Under base 64: a quality character below
+    64 was seen (clamped_low) -- the file is not Phred+64.  The hint only advises; nothing applies it."""
+    base = (64 if phred64 else 33) if phred64 is not None else int(stats.get("phred_base", 33))
+    raw = stats["raw"]
+    bases = sum(int(t["bases"]) for t in raw)
+    if base == 33:
+        if bases >= 1000 and not sum(int(t["qual"][:, :31].sum()) for t in raw):
+            return ("read statistics: no quality character below '@' in %d bases -- the file looks like Phred+64 (Illumina 1.3 - 1.7): "
+                    "type it with --phred64" % bases)
+        return None
+    low = sum(int(t["clamped_low"]) for t in raw)
+    if low:
+        return ("read statistics: %d quality characters lie below '@' (64) -- the file does not look like Phred+64: "
+                "type it without --phred64" % low)
+    return None
+
+
 def _bgzf_block_size(buf, off: int) -> int:
     """Total size of the BGZF block that starts at buf[off], 0 if the header is incomplete, -1 if it is not BGZF."""
     if len(buf) - off < 18:
