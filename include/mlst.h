@@ -567,6 +567,46 @@ int mlst_set_read_stats_side(mlst_handle* h, int side);
 int mlst_read_stats_fetch(mlst_handle* h, int stage, int side, uint64_t* out, uint64_t cap);
 int mlst_read_stats_info(mlst_handle* h, uint64_t out[4]);
 
+/* ---- exact duplicate reads removed before the reads are aligned (off by default; csrc/read_dedup.h; `cli type --dedup`) -----------------
+ * mlst_set_read_dedup(h, 1): every read (every pair) of FASTQ text that repeats an earlier one of the sample is emptied on the device
+ *   before it is packed; the engine then behaves as if it had been given the deduplicated text (metamlst_amd.fastq.dedup_fastq states
+ *   the rule in Python and writes that text).  Off: nothing is queued, nothing is allocated, and the kernels that run are those that ran
+ *   before the switch existed.
+ * The rule:
+ *   1. Letters.  A read's letters are its sequence as the engine aligns it: A C G T in either case stand for themselves, every other
+ *      byte is N (the N bit of the packed rows).  The read's key is (length, folded letters); qualities and names play no part.
+ *   2. Unpaired submissions: read r is a duplicate if a read with a lower read index in the sample has the same key.  The first
+ *      occurrence is kept.
+ *   3. Paired submissions: the unit is the pair.  Pair j is a duplicate if an earlier pair has the same key for mate 1 AND the same key
+ *      for mate 2, in that order; swapped mates are not duplicates.  Both mates of a duplicate pair go, otherwise both stay.
+ *   4. A read of length 0 is neither a duplicate nor a first occurrence, nor is a pair whose mates are both empty.  A pair with one empty
+ *      mate takes part as it is.
+ *   5. A duplicate stays a read of length 0 (mlst_set_read_prep's rule 4): read indices, pairing and the names of mlst_set_read_names
+ *      are those of the file.  It holds no seed, leaves no candidate and appears in no export.
+ *   6. Only the same orientation counts: a reverse complement is not a duplicate (fastp's and FastUniq's rule).
+ *   7. It runs behind mlst_set_read_prep's steps and mlst_set_read_adapters' cut, on what they left: two reads that differ only in a
+ *      tail the quality trim removes are duplicates.  The tables of mlst_set_read_stats are counted in front of it and are what they are
+ *      without it.
+ *   On the device a unit is its 128-bit key (MLST_DEDUP_KEY of mlst_policy.h): the rule above holds unless two different units share
+ *   all 128 bits.  Two units that share the first 64 bits only are a clash: both are kept, the later one is counted in out[6].
+ * The keys live in a hash table on the device that belongs to the handle: 28 bytes per slot, MLST_DEDUP_SLOTS slots at first (a power
+ *   of two >= 64, default 2^22; read when the table is made), doubled and rehashed on the device whenever it would hold fewer than two
+ *   slots per unit submitted; 48 M reads end at 2^27 slots, 3.75 GB.  An allocation that fails is MLST_E_LIMIT with the bytes needed.
+ *   MLST_DEDUP_TAG_BITS (test switch, default 64, read when the table is made): only that many low bits of the first hash are used.
+ * Entries it applies to, the entries refused while it is on ("<entry>: duplicate removal is on (mlst_set_read_dedup) ...") and when the
+ *   switch may change: exactly as for mlst_set_read_prep, with which it combines, as it does with mlst_set_read_adapters,
+ *   mlst_set_read_stats, mlst_set_read_names and the exports.  mlst_reset_sample empties the table, zeroes the counters and keeps the
+ *   switch.  The result does not depend on how the text was cut into chunks; a paired chunk must hold whole pairs (every paired entry
+ *   sees to that; a paired mlst_submit_fastq_stream chunk cut behind a first mate is refused with MLST_E_INVALID).
+ * mlst_read_dedup_info: out[0] = reads seen, out[1] = units (reads or pairs) that took part, out[2] = duplicates (units removed),
+ *   out[3] = reads removed, out[4] = bases removed, out[5] = distinct keys, out[6] = clashes, out[7] = slots of the table,
+ *   out[8 + k], k = 0..7 = distinct keys that occur 1, 2, 3, 4, 5-9, 10-49, 50-499 and >= 500 times.  All zero with the switch off.  An
+ *   open BGZF piece is finished first.
+ * No host synchronisation is added per chunk; mlst_get_kernel_time 21 is the three launches of a chunk together. */
+int mlst_set_read_dedup(mlst_handle* h, int on);
+int mlst_get_read_dedup(mlst_handle* h, int* on);
+int mlst_read_dedup_info(mlst_handle* h, uint64_t out[16]);
+
 /* ---- bowtie2's MD:Z field in the text export (off by default; csrc/aln_text.h; `cli type --md`) --------------------------------------
  * mlst_set_export_md(h, 1): every record of mlst_alignments_text_* carries MD:Z:<text> between NM:i and YT:Z:UU, bowtie2's place;
  *   columns 1-11 and every other field are the bytes they are without it.  With the switch off the export writes what it wrote
@@ -855,7 +895,8 @@ int mlst_set_profiling(mlst_handle* h, int on);   /* 0 = off, 1 = events + sieve
  * 13 = k_fqt_count (a BAM piece: k_bamt_count) + k_fqt_scan + k_fqt_add and 14 = k_fqt_emit (k_bamt_emit) (long reads cut into windows,
  * csrc/fastq_tile.h, csrc/bam_tile.h; outside 6); 15 = the line table of a SAM chunk (k_fq_count, k_fq_scan, k_fq_lines, k_sam_flags), 16 =
  * k_sam_accumulate and 17 = k_sam_pileup (csrc/sam_dev.h; two entries of 15 per chunk); 18 = k_rp_qtrim (csrc/read_prep.h) and 19 = k_ra_cut
- * (csrc/read_adapt.h), each alone (inside 6); 20 = k_rs_count (csrc/read_stats.h; alone, inside 6); 9 = k_route, 10 =
+ * (csrc/read_adapt.h), each alone (inside 6); 20 = k_rs_count (csrc/read_stats.h; alone, inside 6); 21 = k_dd_insert + k_dd_sign + k_dd_mark
+ * (csrc/read_dedup.h; the three launches of a chunk together, inside 6); 9 = k_route, 10 =
  * k_route_probe and 11 = k_route_verify, the three kernels of the routed sieve (inside 0) (events bracket the launch on the engine's
  * stream, so with several engines on one GPU they include the time a kernel queues behind another stream's kernel);
  * 7 = the sieve's execution window measured inside the kernel (wall clock at the first workgroup's start and the last

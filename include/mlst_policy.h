@@ -67,6 +67,14 @@
                                        per allele.  The reference states nothing for reads its aligner handles and the packed score
                                        fields (MLST_MAX_READ_LEN) cannot hold: the policy is this engine's own, like --contigs */
 
+/* ---- duplicate reads (mlst_set_read_dedup) ---- */
+#define MLST_DEDUP_KEY        128   /* on the device a read (a pair) IS its 128-bit key: two independent 64-bit hashes of its length(s) and
+                                       its letters folded to A C G T N (both mates of a pair, in order).  The host rule
+                                       (fastq.dedup_fastq) compares the letters themselves; the two agree unless two different units of
+                                       one sample share all 128 bits (at 10^9 units the chance is ~10^-21), and then the later one is
+                                       removed as a duplicate.  Two units that share only the first 64 bits are both kept (a "clash",
+                                       counted).  The policy is this engine's own: the reference has no such step */
+
 /* ---- centre-star alignment of a locus' alleles (mlst_msa_align; merge --outseqformat A) ----
  * The policy is this engine's own: the reference pipes the sequences through MUSCLE (metamlst-merge.py:402-405) [NOT IN TREE], whose
  * gap placement differs between its own versions.  The rule is stated in metamlst_amd/msa.py and in include/mlst.h. */

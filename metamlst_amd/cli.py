@@ -151,6 +151,17 @@ def _type_parser(sub):
                         "and side, and a hint when the qualities look like the other Phred base.  One sample on one GPU: plain, .gz and "
                         "bgzip'd FASTQ, `a.fq,b.fq`, -2; refused with --alignments, --contigs, --long-reads, --long-bam-reads, a reads BAM, "
                         "a folder or several samples, and --gpus N.  The .nfo, the --log file and every export do not change")
+    p.add_argument("--dedup", dest="dedup", action="store_true",
+                   help="FASTQ input: remove exact duplicate reads before they are aligned, on the GPU (csrc/read_dedup.h; the rule: "
+                        "metamlst_amd.fastq.dedup_fastq).  A read whose letters (A, C, G, T in either case, everything else N) and length "
+                        "repeat an earlier read of the sample is emptied; with -2 the unit is the pair, and both mates must repeat, in "
+                        "order.  The first occurrence stays; a reverse complement is no duplicate; qualities and names play no part.  It "
+                        "runs behind --trim* / --adapter, on what they left.  A duplicate stays a read without a base (indices, pairing "
+                        "and --read-names are those of the file) and appears in no export.  The keys live in a table on the GPU (28 bytes "
+                        "per slot, at least two slots per read: 48 M reads end at 3.75 GB).  One sample on one GPU: plain, .gz and bgzip'd "
+                        "FASTQ, `a.fq,b.fq`, -2; refused with --alignments, --contigs, --long-reads, --long-bam-reads, a reads BAM, a "
+                        "folder or several samples, and --gpus N.  Unless --quiet, one line reports units, duplicates, bases removed and "
+                        "how often the distinct reads occur")
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -324,6 +335,17 @@ def run_type(a, argv=None) -> int:
             if on:
                 print("--read-stats: " + why)
                 return 1
+    if getattr(a, "dedup", False):      # (refused before any GPU use, each with its reason)
+        for on, why in ((a.alignments, "with --alignments the file holds alignments, not reads to compare (duplicate alignments are samtools markdup's)"),
+                        (a.contigs, "--contigs cuts assemblies into windows, and the windows of an assembly are not copies of a molecule"),
+                        (a.long_reads, "--long-reads cuts reads into windows, and the windows of a read would be compared, not the read"),
+                        (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and the windows of a read would be compared, not the read"),
+                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the reads of a BAM are not compared: FASTQ input only"),
+                        (many, "one table of keys per engine: several samples or a folder are typed without it (per-sample tables through the pipelined loop are the follow-up)"),
+                        (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "a rank of --gpus N sees only its byte range, and duplicates across ranks would be missed")):
+            if on:
+                print("duplicate removal (--dedup): " + why)
+                return 1
     if a.md and not (a.write_sam or a.write_sam_all):      # (with an export flag it is accepted and refused where that flag is: below)
         print("--md: it adds MD:Z to the records of an export: give --write-sam or --write-sam-all")
         return 1
@@ -394,6 +416,8 @@ def run_type(a, argv=None) -> int:
         eng.set_read_adapters(**adapters)
     if getattr(a, "read_stats", False):      # (likewise: counted where the text is parsed)
         eng.set_read_stats(True)
+    if getattr(a, "dedup", False):      # (likewise: compared where the text is parsed, behind the preparation)
+        eng.set_read_dedup(True)
     # the built host index is kept next to the database (as the reference keeps <idx>.1.bt2: metamlst-index.py:224-225) unless a
     # species filter made this index a one-off or MLST_INDEX_CACHE=0
     ref_cache = (a.database + ".mlstref") if (not a.filter and os.environ.get("MLST_INDEX_CACHE", "1") != "0") else ""
@@ -533,6 +557,8 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
         _say_read_adapters(eng.read_adapters_info(), eng.get_read_adapters()["adapters"], 1)
     if rc == 0 and getattr(a, "read_stats", False):
         _write_read_stats(a, eng)
+    if rc == 0 and not a.quiet and getattr(a, "dedup", False):
+        print(read_dedup_line(eng.read_dedup_info(), paired), flush=True)
     names, md = None, bool(getattr(a, "md", False))      # --md: MD:Z in both exports (write_sam on the host, the full export on the device)
     if rc == 0 and getattr(a, "read_names", False):      # the engine knows its switch: the text export needs no more than that
         names = eng.read_names()
@@ -597,6 +623,20 @@ def _adapters_of(a, say: bool = True):
             print("--adapter: %s" % e)
         return False
     return {"adapters": [x.decode() for x in ads], "min_overlap": 3 if mo is None else mo, "error_permille": permille}
+
+
+def read_dedup_line(info: dict, paired: bool = False) -> str:
+    """The line on what --dedup did (info: Engine.read_dedup_info() or fastq.dedup_fastq's counters): units seen, duplicates and their
+    share of the units to one decimal (in integers, rounded half up), bases removed, the eight levels, and the clashes only when there
+    are some"""
+    units, dups = int(info["units"]), int(info["duplicates"])
+    tenths = (1000 * dups + units // 2) // units if units else 0
+    lv = info["levels"]
+    line = ("duplicate removal: %d %s, %d duplicates (%d.%d %%), %d bases removed; distinct %d: x1 %d, x2 %d, x3 %d, x4 %d, x5-9 %d, x10-49 %d, x50-499 %d, x500+ %d"
+            % (units, "pairs" if paired else "reads", dups, tenths // 10, tenths % 10, int(info["bases_removed"]), int(info["distinct"]), *[int(v) for v in lv]))
+    if info.get("clashes"):
+        line += "; %d kept on a 64-bit clash" % int(info["clashes"])
+    return line
 
 
 def read_stats_lines(stats: dict) -> list:

@@ -3691,6 +3691,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "read_names.h"
 #include "read_prep.h"
 #include "read_adapt.h"
+#include "read_dedup.h"
 #include "read_stats.h"
 #include "aln_text.h"
 #include "reads_text.h"
@@ -3799,7 +3800,7 @@ struct mlst_handle {
     GraphSlot g_submit, g_typing; bool use_graphs = true;
     std::vector<EvPair> events;
     std::vector<hipEvent_t> ev_pool;
-    double k_ms[21] = {0}; u64 k_n[21] = {0};      // see mlst_get_kernel_time
+    double k_ms[22] = {0}; u64 k_n[22] = {0};      // see mlst_get_kernel_time
     double wall_khz = 100000.0;                  // wall_clock64 rate (hipDeviceAttributeWallClockRate)
     struct BamStream* bam = nullptr;             // BAM input (mlst_bam_open / mlst_submit_bam_bgzf), allocated by the first stream
     u32 bam_force_miss = 0; u64 bam_max_entries = 0;      // mlst_debug_bam_split, mlst_bam_set_capacity
@@ -3855,6 +3856,11 @@ struct mlst_handle {
     // tables on the device ([stage][side][RS_WORDS]) -- allocated by the first submission under the switch --, the launches per stage
     // since the last reset and the device's CU count (the grid is at most one workgroup per CU)
     struct { bool on = false; u32 side = 0; u64* d_tab = nullptr; u64 launches[2] = {0, 0}; int n_cu = 0; } rs;
+    // exact duplicates emptied before the reads are packed (mlst_set_read_dedup; csrc/read_dedup.h): the switch, the table of the sample's
+    // keys (one allocation: tag, chk, first, cnt), the counters on the device, slot and second hash per unit of a chunk -- all allocated by
+    // the first submission under the switch, which reads MLST_DEDUP_SLOTS / MLST_DEDUP_TAG_BITS --, the units and reads submitted so far
+    struct { bool on = false; DdTab tab = {nullptr, nullptr, nullptr, nullptr, 0, 0}; u8* d_mem = nullptr; DdCtr* d_ctr = nullptr;
+             u32* d_slot_of = nullptr; u64* d_key2 = nullptr; u64 cap_units = 0, units_seen = 0, reads = 0; } dd;
 };
 
 static std::string g_create_err;
@@ -3876,6 +3882,7 @@ static int rn_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_n
 static int rp_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_prep is on: an entry that does not prepare its reads is refused
 static int ra_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_adapters is on: an entry that does not cut its reads is refused
 static int rs_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_stats is on: an entry whose reads are not counted is refused
+static int dd_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_dedup is on: an entry whose reads are not compared is refused
 static void at_free(mlst_handle* h);      // the per-export tables of mlst_alignments_text_*
 static const char* bam_kind(const mlst_handle* h);      // "BAM" or "SAM": what the open stream of ready-made alignments takes
 template <typename T> static hipError_t dmalloc(T** p, u64 n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
@@ -4047,6 +4054,7 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     hipFree(h->d_cand); hipFree(h->d_in_bases); hipFree(h->d_in_quals); hipFree(h->d_in_off);
     hipFree(h->d_fq_slot[0]); hipFree(h->d_fq_slot[1]); hipFree(h->d_fq_nl[0]); hipFree(h->d_fq_nl[1]); hipFree(h->d_fq_blk); hipFree(h->d_fq_lines); hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); hipFree(h->d_fq_meta);
     hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta); hipFree(h->rp.d_ctr); hipFree(h->ra.d_ctr); hipFree(h->rs.d_tab);
+    hipFree(h->dd.d_mem); hipFree(h->dd.d_ctr); hipFree(h->dd.d_slot_of); hipFree(h->dd.d_key2);
     hipFree(h->fa.d_desc); hipFree(h->fa.d_meta); hipFree(h->fa.d_flat); hipFree(h->fa.d_kind); hipFree(h->fa.d_cseq); hipFree(h->fa.d_chdr); hipFree(h->fa.d_cstart); hipFree(h->fa.d_wcnt);
     if (h->fa.h_fa) hipHostFree(h->fa.h_fa);
     hipFree(h->tile.d_desc); hipFree(h->tile.d_meta); hipFree(h->tile.d_rlen); hipFree(h->tile.d_wex); hipFree(h->tile.d_gsum); hipFree(h->tile.d_soff); hipFree(h->tile.d_qoff);
@@ -4067,6 +4075,13 @@ static inline int base_code(u8 c) {
     switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; default: return 4; }
 }
 
+// an empty table of mlst_set_read_dedup: no tag, no copies, every first index the largest there is
+static int dd_clear(mlst_handle* h, const DdTab& T) {
+    HIPCHK(h, hipMemsetAsync(T.tag, 0, T.slots * 16, h->stream));      // (tag, then chk)
+    HIPCHK(h, hipMemsetAsync(T.first, 0xFF, T.slots * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.cnt, 0, T.slots * 4, h->stream));
+    return MLST_OK;
+}
 static int reset_sample_state(mlst_handle* h) {
     HIPCHK(h, hipMemsetAsync(h->d_stats, 0, h->stats_zero_bytes, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_stats + h->off_first, 0xFF, h->stats_bytes - h->off_first, h->stream));
@@ -4076,6 +4091,9 @@ static int reset_sample_state(mlst_handle* h) {
     if (h->ra.d_ctr) HIPCHK(h, hipMemsetAsync(h->ra.d_ctr, 0, sizeof(RaCtr), h->stream));      // mlst_set_read_adapters: likewise
     if (h->rs.d_tab) HIPCHK(h, hipMemsetAsync(h->rs.d_tab, 0, 4ull * RS_WORDS * 8, h->stream));      // mlst_set_read_stats: the tables are the sample's; the switch stays, the side is 0 again
     h->rs.side = 0; h->rs.launches[0] = h->rs.launches[1] = 0;
+    if (h->dd.d_mem) { int rc = dd_clear(h, h->dd.tab); if (rc) return rc; }      // mlst_set_read_dedup: the keys are the sample's; the switch and the table's size stay
+    if (h->dd.d_ctr) HIPCHK(h, hipMemsetAsync(h->dd.d_ctr, 0, sizeof(DdCtr), h->stream));
+    h->dd.units_seen = h->dd.reads = 0;
     h->reads_seen = 0; h->fq_carry_len = 0; h->max_wpr = 0;
     h->last_pack.n_reads = 0; h->last_pack.wpr = h->last_pack.qstride = 0;
     for (u64& x : h->tile.info) x = 0;
@@ -4692,6 +4710,7 @@ extern "C" int mlst_submit_packed_device(mlst_handle* h, const uint32_t* d_packe
     { int rc_ = rp_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
+    { int rc_ = dd_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     return submit_impl(h, d_packed, d_qrows, d_lens, n_reads, wpr, qstride, paired, 0);
 }
 static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* d_qrows, const uint16_t* d_lens,
@@ -4842,6 +4861,7 @@ extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, 
     { int rc_ = rp_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
+    { int rc_ = dd_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     hipSetDevice(h->device);
@@ -4861,6 +4881,7 @@ extern "C" int mlst_submit_reads(mlst_handle* h, const uint8_t* bases, const uin
     { int rc_ = rp_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
+    { int rc_ = dd_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (n_reads == 0) return MLST_OK;
@@ -4927,6 +4948,11 @@ static int rs_refuse(mlst_handle* h, const char* entry) {
     if (h && h->rs.on) return fail(h, MLST_E_INVALID, "%s: read statistics are on (mlst_set_read_stats) and only the FASTQ text and BGZF entries count their reads", entry);
     return MLST_OK;
 }
+// mlst_set_read_dedup (csrc/read_dedup.h): with the switch on, reads come from FASTQ text only, where they are compared
+static int dd_refuse(mlst_handle* h, const char* entry) {
+    if (h && h->dd.on) return fail(h, MLST_E_INVALID, "%s: duplicate removal is on (mlst_set_read_dedup) and only the FASTQ text and BGZF entries apply it", entry);
+    return MLST_OK;
+}
 // one launch of k_rs_count over the chunk's reads as offsets and lengths stand now: stage 0 in front of k_rp_qtrim (which rewrites the
 // offsets in place), stage 1 behind k_ra_cut.  At most one workgroup per CU, fewer for few reads (each flushes its LDS tables once); a
 // paired chunk takes an even number, a workgroup counting one side
@@ -4950,11 +4976,76 @@ static int rs_launch(mlst_handle* h, u64 n_reads, u32* d_flags, int paired, int 
 // front of the read-back of the flags, so that the longest length the host reads is the longest prepared one (no synchronisation added)
 // Behind them, mlst_set_read_adapters' cut (csrc/read_adapt.h): flags[0] is zeroed in front of either kernel, so the last one alone feeds what is read
 // mlst_set_read_stats: the raw tables are counted in front of the trims, the prepared ones behind the cut, only when either ran
+// mlst_set_read_dedup: the table, the counters and the per-unit scratch in front of a chunk of n_units units.  The table holds at least
+// two slots per unit submitted so far and in this chunk -- the host knows both numbers without a read-back; one that is too small is
+// replaced by the next power of two that is not, and k_dd_rehash moves the keys
+static int dd_ensure(mlst_handle* h, u64 n_units) {
+    auto& D = h->dd;
+    if (!D.d_ctr) { HIPCHK(h, dmalloc(&D.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(D.d_ctr, 0, sizeof(DdCtr), h->stream)); }
+    if (D.cap_units < n_units) {
+        hipFree(D.d_slot_of); hipFree(D.d_key2); D.d_slot_of = nullptr; D.d_key2 = nullptr; D.cap_units = 0;
+        HIPCHK(h, dmalloc(&D.d_slot_of, n_units)); HIPCHK(h, dmalloc(&D.d_key2, n_units)); D.cap_units = n_units;
+    }
+    u64 slots = D.tab.slots, tag_mask = D.tab.tag_mask;
+    if (!slots) {      // the first table: the two environment switches are read here
+        slots = 1ull << 22; tag_mask = ~0ull;
+        if (const char* e = getenv("MLST_DEDUP_SLOTS")) {
+            const long long v = atoll(e);
+            if (v < 64 || v > (1ll << 31) || (v & (v - 1))) return fail(h, MLST_E_INVALID, "MLST_DEDUP_SLOTS is %s: a power of two from 64 to 2^31 is taken", e);
+            slots = (u64)v;
+        }
+        if (const char* e = getenv("MLST_DEDUP_TAG_BITS")) {
+            const int v = atoi(e);
+            if (v < 0 || v > 64 || !(e[0] >= '0' && e[0] <= '9')) return fail(h, MLST_E_INVALID, "MLST_DEDUP_TAG_BITS is %s: 0 to 64 is taken", e);
+            tag_mask = v >= 64 ? ~0ull : (1ull << v) - 1;
+        }
+    }
+    const u64 need = 2 * (D.units_seen + n_units);
+    while (slots < need && slots < (1ull << 31)) slots <<= 1;
+    if (slots < need) return fail(h, MLST_E_LIMIT, "mlst_set_read_dedup: %llu units need more than 2^31 slots", (unsigned long long)(D.units_seen + n_units));
+    if (slots == D.tab.slots) return MLST_OK;
+    u8* mem = nullptr;
+    if (dmalloc(&mem, slots * 28) != hipSuccess) { (void)hipGetLastError(); return fail(h, MLST_E_LIMIT, "mlst_set_read_dedup: the table of %llu slots needs %llu bytes of device memory", (unsigned long long)slots, (unsigned long long)(slots * 28)); }
+    const DdTab T = {reinterpret_cast<u64*>(mem), reinterpret_cast<u64*>(mem + slots * 8), reinterpret_cast<u64*>(mem + slots * 16), reinterpret_cast<u32*>(mem + slots * 24), slots, tag_mask};
+    int rc = dd_clear(h, T);
+    if (!rc && D.d_mem) {
+        hipLaunchKernelGGL(k_dd_rehash, dim3(grid_for(D.tab.slots, 256)), dim3(256), 0, h->stream, D.tab, T, D.d_ctr);
+        const hipError_t e = hipStreamSynchronize(h->stream);      // (the old table is freed behind its last reader)
+        if (e != hipSuccess) rc = fail(h, MLST_E_HIP, "k_dd_rehash: %s", hipGetErrorString(e));
+    }
+    if (rc) { hipFree(mem); return rc; }
+    hipFree(D.d_mem); D.d_mem = mem; D.tab = T;
+    return MLST_OK;
+}
+// the three launches of mlst_set_read_dedup over a chunk's reads as their lengths stand now, behind the trims, the cut and the prepared
+// read statistics, in front of the read-back of the parser's flags.  flags[0] is zeroed once more: k_dd_mark alone feeds the longest
+// length the host reads.  Chunks are queued on h->stream one behind the other (each ends in a read-back), so the launches of
+// consecutive chunks run in read-index order -- for the pipelined BGZF entries too, whose other two streams only copy and inflate
+static int dd_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
+    auto& D = h->dd;
+    const u64 n_units = paired ? n_reads / 2 : n_reads;
+    if (paired && (n_reads & 1)) return fail(h, MLST_E_INVALID, "mlst_set_read_dedup: a paired chunk holds %llu records: the mates of a pair are compared within one chunk", (unsigned long long)n_reads);
+    if (!n_units) return MLST_OK;
+    int rc = dd_ensure(h, n_units); if (rc) return rc;
+    HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
+    {
+        Prof pf(h, 21);      // (mlst_get_kernel_time 21: k_dd_insert, k_dd_sign and k_dd_mark together)
+        const dim3 grid(grid_for(n_units, 256)), block(256);
+        hipLaunchKernelGGL(k_dd_insert, grid, block, 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, (const u16*)h->d_lens, n_units, paired ? 1u : 0u,
+                           D.units_seen, D.tab, D.d_slot_of, D.d_key2, (const u32*)d_flags, D.d_ctr);
+        hipLaunchKernelGGL(k_dd_sign, grid, block, 0, h->stream, n_units, D.units_seen, D.tab, (const u32*)D.d_slot_of, (const u64*)D.d_key2, (const u32*)d_flags, D.d_ctr);
+        hipLaunchKernelGGL(k_dd_mark, grid, block, 0, h->stream, h->d_lens, n_units, paired ? 1u : 0u, D.units_seen, D.tab, (const u32*)D.d_slot_of, (const u64*)D.d_key2,
+                           d_flags, D.d_ctr);
+    }
+    HIPCHK(h, hipGetLastError());
+    D.units_seen += n_units; D.reads += n_reads;
+    return MLST_OK;
+}
 static int rp_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
     const RpSet& P = h->rp.set;
     const bool trims = h->rp.on && (P.trim5 | P.trim3 | P.trim_qual);      // (the Phred base alone is k_pack_text's)
     if (h->rs.on) { int rc = rs_launch(h, n_reads, d_flags, paired, 0); if (rc) return rc; }
-    if (!trims && !h->ra.on) return MLST_OK;
+    if (!trims && !h->ra.on) return h->dd.on ? dd_apply(h, n_reads, d_flags, paired) : MLST_OK;      // (mlst_set_read_dedup alone still runs)
     if (trims && !h->rp.d_ctr) { HIPCHK(h, dmalloc(&h->rp.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->rp.d_ctr, 0, sizeof(RpCtr), h->stream)); }
     if (h->ra.on && !h->ra.d_ctr) { HIPCHK(h, dmalloc(&h->ra.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->ra.d_ctr, 0, sizeof(RaCtr), h->stream)); }
     HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
@@ -4971,8 +5062,8 @@ static int rp_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
         hipLaunchKernelGGL(k_ra_cut, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, h->d_lens, n_reads, h->ra.set,
                            d_flags, h->ra.d_ctr);
     }
-    if (h->rs.on) return rs_launch(h, n_reads, d_flags, paired, 1);
-    return MLST_OK;
+    if (h->rs.on) { int rc = rs_launch(h, n_reads, d_flags, paired, 1); if (rc) return rc; }
+    return h->dd.on ? dd_apply(h, n_reads, d_flags, paired) : MLST_OK;      // mlst_set_read_dedup: behind the prepared tables, which stay what they are
 }
 // the counters of the name arena; an arena that was too small is reported here (the next entry that looks)
 static int rn_fetch(mlst_handle* h, RnCtr* c) {
@@ -5054,6 +5145,7 @@ static int fastq_pipeline(mlst_handle* h, u64 n_bytes, int paired, bool whole, u
         if (flags[1] & 4) return fq_tile_submit(h, n_bytes, n_lines, n_reads, tslot, n_reads_out);      // a record to cut: csrc/fastq_tile.h
         if (flags[0] > h->tile.info[3]) h->tile.info[3] = flags[0];      // (no record is longer than the tile: the chunk goes on as without the switch)
     }
+    if (flags[1] & 8) return fail(h, MLST_E_HIP, "mlst_set_read_dedup: a probe ran through the whole table");      // (k_dd_mark hands DdCtr::err on)
     if (flags[1] & 2) return fail(h, MLST_E_LIMIT, "a FASTQ read is longer than %d bases", MLST_MAX_READ_LEN);
     if (flags[1] & 1) return fail(h, MLST_E_INVALID, "malformed FASTQ: a record does not start with '@' or its sequence and quality lengths differ");
     h->rn.src.lines1 = h->d_fq_lines; h->rn.src.lines2 = nullptr; h->rn.src.pair_k = pair_k;
@@ -5083,7 +5175,7 @@ static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, i
     if (!h->rn.on) HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
     if (n_reads_out) *n_reads_out = n_reads;
     h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
-    if (!h->rn.on && (h->rp.on || h->ra.on || h->rs.on)) return submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);      // (the public entry refuses under mlst_set_read_prep / mlst_set_read_adapters)
+    if (!h->rn.on && (h->rp.on || h->ra.on || h->rs.on || h->dd.on)) return submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);      // (the public entry refuses under mlst_set_read_prep / mlst_set_read_adapters)
     if (!h->rn.on) return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired);
     // mlst_set_read_names: the text outlives pass 1 of its chunk -- the names of the reads it retained are copied out of the header
     // lines (csrc/read_names.h), behind the submission and outside its captured graph, and only then is the slot released
@@ -5242,6 +5334,7 @@ extern "C" int mlst_submit_packed_host(mlst_handle* h, const uint32_t* packed, c
     { int rc_ = rp_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
+    { int rc_ = dd_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (!packed || !qrows || !lens) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -5747,6 +5840,7 @@ static int bzp_finish_impl(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
         HIPCHK(h, hipMemcpyAsync(back, h->d_pr_meta + 1, 24, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         memcpy(flags, &back[0], 8); cut[0] = back[1]; cut[1] = back[2];
+        if (flags[1] & 8) return fail(h, MLST_E_HIP, "mlst_set_read_dedup: a probe ran through the whole table");
         if (flags[1] & 2) return fail(h, MLST_E_LIMIT, "a FASTQ read is longer than %d bases", MLST_MAX_READ_LEN);
         if (flags[1] & 1) return fail(h, MLST_E_INVALID, "malformed FASTQ: a record does not start with '@' or its sequence and quality lengths differ");
     }
@@ -6573,6 +6667,7 @@ extern "C" int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip
     { int rc_ = rp_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
+    { int rc_ = dd_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6620,6 +6715,7 @@ extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n
     { int rc_ = rp_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = ra_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
+    { int rc_ = dd_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6793,6 +6889,7 @@ extern "C" int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t 
     if (read_len) { int rc_ = rp_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window is cut from the record as it stands)
     if (read_len) { int rc_ = ra_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
     if (read_len) { int rc_ = rs_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
+    if (read_len) { int rc_ = dd_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
     // (a reads stream took its tile when it was opened: include/mlst.h gives one message for every stream of reads)
     if (bam_is_open(h) && h->bam->reads) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (the reads stream of a BAM: its last chunk was not marked final)");
@@ -6962,6 +7059,38 @@ extern "C" int mlst_read_stats_info(mlst_handle* h, uint64_t out[4]) {
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     const bool live = h->rs.on && h->rs.d_tab;
     out[0] = live ? h->rs.launches[0] : 0; out[1] = live ? h->rs.launches[1] : 0; out[2] = h->rs.d_tab ? 4ull * RS_WORDS * 8 : 0; out[3] = 0;
+    return MLST_OK;
+}
+// exact duplicates emptied before the reads are packed (include/mlst.h; csrc/read_dedup.h): the switch's life cycle is mlst_set_read_prep's
+extern "C" int mlst_set_read_dedup(mlst_handle* h, int on) {
+    if (!h) return MLST_E_INVALID;
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
+    if ((on != 0) != h->dd.on && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_dedup changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
+    if (on && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_dedup: mlst_set_read_tiling is on and the windows of a read would be compared, not the read");
+    h->dd.on = on != 0;
+    return MLST_OK;
+}
+extern "C" int mlst_get_read_dedup(mlst_handle* h, int* on) {
+    if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
+    *on = h->dd.on ? 1 : 0;
+    return MLST_OK;
+}
+extern "C" int mlst_read_dedup_info(mlst_handle* h, uint64_t out[16]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    hipSetDevice(h->device);
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
+    for (int k = 0; k < 16; k++) out[k] = 0;
+    if (!h->dd.on || !h->dd.d_ctr || !h->dd.d_mem) return MLST_OK;
+    DdCtr c; memset(&c, 0, sizeof c);
+    HIPCHK(h, hipMemsetAsync(h->dd.d_ctr->levels, 0, sizeof c.levels, h->stream));      // (counted anew by every call)
+    hipLaunchKernelGGL(k_dd_levels, dim3(grid_for(h->dd.tab.slots, 256, 4096)), dim3(256), 0, h->stream, h->dd.tab, h->dd.d_ctr);
+    HIPCHK(h, hipMemcpyAsync(&c, h->dd.d_ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (c.err) return fail(h, MLST_E_HIP, "mlst_set_read_dedup: a probe ran through the whole table");
+    out[0] = h->dd.reads; out[1] = c.units; out[2] = c.dups; out[3] = c.reads_removed; out[4] = c.bases_removed; out[5] = c.distinct; out[6] = c.clashes;
+    out[7] = h->dd.tab.slots;
+    for (int k = 0; k < 8; k++) out[8 + k] = c.levels[k];
     return MLST_OK;
 }
 // MD:Z in the text export (include/mlst.h): no part of the sample's state; mlst_alignments_text_open reads it
@@ -8004,13 +8133,13 @@ extern "C" int mlst_get_items(mlst_handle* h, mlst_item* out, uint64_t cap, uint
 
 extern "C" int mlst_set_profiling(mlst_handle* h, int on) { if (!h) return MLST_E_INVALID; drain_events(h); h->profiling = on == 1; h->window = on != 0; return MLST_OK; }
 extern "C" int mlst_get_kernel_time(mlst_handle* h, int which, double* total_ms, uint64_t* launches) {
-    if (!h || which < 0 || which >= 21) return MLST_E_INVALID;
+    if (!h || which < 0 || which >= 22) return MLST_E_INVALID;
     hipSetDevice(h->device); drain_events(h);
     if (total_ms) *total_ms = h->k_ms[which];
     if (launches) *launches = h->k_n[which];
     return MLST_OK;
 }
-extern "C" int mlst_reset_kernel_time(mlst_handle* h) { if (!h) return MLST_E_INVALID; drain_events(h); for (int i = 0; i < 21; i++) { h->k_ms[i] = 0; h->k_n[i] = 0; } return MLST_OK; }
+extern "C" int mlst_reset_kernel_time(mlst_handle* h) { if (!h) return MLST_E_INVALID; drain_events(h); for (int i = 0; i < 22; i++) { h->k_ms[i] = 0; h->k_n[i] = 0; } return MLST_OK; }
 extern "C" int mlst_get_index_bytes(mlst_handle* h, uint64_t out[4]) {
     if (!h || !out) return MLST_E_INVALID;
     out[0] = h->bytes_arena + h->bytes_hap; out[1] = h->bytes_sieve; out[2] = h->bytes_table; out[3] = (u64)(h->bitmap_fill * 1e6); return MLST_OK;

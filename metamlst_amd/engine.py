@@ -179,6 +179,9 @@ def load_library(path: str | None = None):
         "mlst_set_read_stats_side": (C.c_int, [H, C.c_int]),
         "mlst_read_stats_fetch": (C.c_int, [H, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint64]),
         "mlst_read_stats_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "mlst_set_read_dedup": (C.c_int, [H, C.c_int]),
+        "mlst_get_read_dedup": (C.c_int, [H, C.POINTER(C.c_int)]),
+        "mlst_read_dedup_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_set_export_md": (C.c_int, [H, C.c_int]),
         "mlst_get_export_md": (C.c_int, [H, C.POINTER(C.c_int)]),
         "mlst_read_names_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
@@ -931,6 +934,29 @@ class Engine:
         out = (C.c_uint64 * 4)()
         self._check(self.lib.mlst_read_stats_info(self._h, out), "mlst_read_stats_info")
         return {"raw_launches": int(out[0]), "prepared_launches": int(out[1]), "table_bytes": int(out[2])}
+
+    def set_read_dedup(self, on: bool = True) -> None:
+        """Empty every read (in a paired submission: every pair) of FASTQ text that repeats an earlier one of the sample, on the GPU
+        before it is packed (mlst_set_read_dedup; off by default; the rule: fastq.dedup_fastq), behind set_read_prep's steps and
+        set_read_adapters' cut.  The engine then behaves as if it had been given the deduplicated text.  FASTQ text and BGZF entries
+        only -- every other way of adding reads is refused while it is on; may change only while the sample holds no reads and no
+        stream is open.  reset_sample empties the table of keys and keeps the switch."""
+        self._check(self.lib.mlst_set_read_dedup(self._h, 1 if on else 0), "mlst_set_read_dedup")
+
+    def get_read_dedup(self) -> bool:
+        on = C.c_int()
+        self._check(self.lib.mlst_get_read_dedup(self._h, C.byref(on)), "mlst_get_read_dedup")
+        return bool(on.value)
+
+    def read_dedup_info(self) -> dict:
+        """Since the last reset_sample, fastq.dedup_fastq's counters -- reads, units (reads or pairs that took part), duplicates,
+        reads_removed, bases_removed, distinct, levels (eight: keys that occur 1, 2, 3, 4, 5-9, 10-49, 50-499, >= 500 times) -- and
+        clashes (units kept because only the first 64 bits of their key met another's) and slots (of the table on the device).  All
+        zero with the switch off."""
+        out = (C.c_uint64 * 16)()
+        self._check(self.lib.mlst_read_dedup_info(self._h, out), "mlst_read_dedup_info")
+        return {"reads": int(out[0]), "units": int(out[1]), "duplicates": int(out[2]), "reads_removed": int(out[3]), "bases_removed": int(out[4]),
+                "distinct": int(out[5]), "clashes": int(out[6]), "slots": int(out[7]), "levels": [int(out[8 + k]) for k in range(8)]}
 
     def set_export_md(self, on: bool = True) -> None:
         """export_sam_text / write_sam_all write bowtie2's MD:Z field between NM:i and YT:Z, formatted on the GPU (mlst_set_export_md; off

@@ -858,6 +858,69 @@ def trim_adapters(text: bytes, adapters, min_overlap: int = 3, error_permille: i
     return b"".join(out), info
 
 
+DEDUP_LEVELS = (1, 2, 3, 4, 5, 10, 50, 500)      # the lower edges of the eight levels: keys that occur 1, 2, 3, 4, 5-9, 10-49, 50-499, >= 500 times
+_DD_FOLD = bytes(c if c in b"ACGT" else (c & 0xDF if (c & 0xDF) in b"ACGT" else 78) for c in range(256))      # a letter as the engine aligns it (78: 'N')
+
+
+def dedup_level(count: int) -> int:
+    """The level (0..7) of a key that occurs `count` >= 1 times"""
+    return sum(count >= e for e in DEDUP_LEVELS) - 1
+
+
+def dedup_fastq(text: bytes, paired: bool = False) -> tuple[bytes, dict]:
+    """The FASTQ text the engine behaves as if it had been given under Engine.set_read_dedup(), and the counters of
+    Engine.read_dedup_info().  This is the rule mlst_set_read_dedup applies on the device (csrc/read_dedup.h) -- there on 128-bit
+    hashes of the keys (MLST_DEDUP_KEY of include/mlst_policy.h), here on the letters themselves; it serves the tests and whoever
+    wants the deduplicated file -- the command never calls it.
+      1. A read's letters are its sequence line as the engine aligns it: A, C, G, T in either case stand for themselves, every other
+         byte is N (pack_group's N bit, _RS_COL's folding).  Its key is (length, folded letters); qualities and names play no part.
+      2. Unpaired: a read is a duplicate if an earlier read of the text has the same key.  The first occurrence is kept.
+      3. paired (records 2j and 2j + 1): pair j is a duplicate if an earlier pair has the same key for mate 1 AND for mate 2, in that
+         order (swapped mates are not duplicates); both mates of a duplicate pair go, otherwise both stay.
+      4. A read of length 0 -- a pair whose mates are both empty -- is neither a duplicate nor a first occurrence; a pair with one
+         empty mate takes part as it is.
+      5. A duplicate stays a record: header and '+' line untouched, sequence and quality lines empty, line ends LF.
+      6. Only the same orientation counts: a reverse complement is no duplicate.
+      7. Behind the preparation: dedup_fastq(trim_adapters(prep_fastq(text, ...)[0], ...)[0], paired).
+    Counters: reads (records seen), units (reads or pairs that took part), duplicates (units removed), reads_removed, bases_removed,
+    distinct (keys), levels (eight: the distinct keys that occur 1, 2, 3, 4, 5-9, 10-49, 50-499 and >= 500 times)."""
+    lines = bytes(text).split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    if len(lines) % 4:
+        raise ValueError("FASTQ text holds %d lines: not a whole number of 4-line records" % len(lines))
+    if paired and len(lines) % 8:
+        raise ValueError("paired FASTQ text holds %d records: not whole pairs" % (len(lines) // 4))
+    recs = []
+    for k in range(0, len(lines), 4):
+        h, s, p, ql = (x[:-1] if x.endswith(b"\r") else x for x in lines[k:k + 4])
+        if len(s) != len(ql):
+            raise ValueError("FASTQ record with different sequence and quality lengths: %r" % h[:60])
+        recs.append([h, s, p, ql])
+    info = {"reads": len(recs), "units": 0, "duplicates": 0, "reads_removed": 0, "bases_removed": 0, "distinct": 0, "levels": [0] * 8}
+    step = 2 if paired else 1
+    seen = {}
+    for j in range(0, len(recs), step):
+        unit = recs[j:j + step]
+        key = tuple(r[1].translate(_DD_FOLD) for r in unit)
+        if not any(key):
+            continue
+        info["units"] += 1
+        if key in seen:
+            seen[key] += 1
+            info["duplicates"] += 1
+            for r in unit:
+                info["reads_removed"] += 1
+                info["bases_removed"] += len(r[1])
+                r[1] = r[3] = b""
+        else:
+            seen[key] = 1
+    info["distinct"] = len(seen)
+    for c in seen.values():
+        info["levels"][dedup_level(c)] += 1
+    return b"".join(b"%s\n%s\n%s\n%s\n" % tuple(r) for r in recs), info
+
+
 # the table block of mlst_read_stats_fetch in 64-bit words (MLST_RS_* of include/mlst.h): reads, bases, clamped_low, padding, then
 RS_LEN, RS_BASE, RS_QUAL, RS_GC, RS_READQUAL, RS_WORDS = 4, 325, 1925, 32005, 32106, 32200
 _RS_COL = np.full(256, 4, np.int64)      # letter -> column of base[c]: A, C, G, T in either case, 4 = every other byte (pack_group's N bit)
