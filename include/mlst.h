@@ -607,6 +607,52 @@ int mlst_set_read_dedup(mlst_handle* h, int on);
 int mlst_get_read_dedup(mlst_handle* h, int* on);
 int mlst_read_dedup_info(mlst_handle* h, uint64_t out[16]);
 
+/* ---- adapter read-through trimmed from the overlap of the mates (off by default; csrc/read_overlap.h; `cli type -2 MATES --pair-overlap`) --
+ * mlst_set_read_pair_overlap(h, 1, min_overlap, max_mismatches, error_permille): when the insert is shorter than the reads, both mates
+ *   run through it into the adapter.  The mates overlap as reverse complements, so the overlap says where the insert ends: both mates
+ *   of a paired FASTQ submission are cut there on the device before they are packed, and no adapter sequence is needed.  The engine then
+ *   behaves as if it had been given the cut text (metamlst_amd.fastq.pair_overlap / trim_pair_overlap state the rule in Python and write
+ *   that text).  Off: nothing is queued, nothing is allocated, and the kernels that run are those that ran before the switch existed.
+ *   MLST_E_INVALID for min_overlap outside 8..320, max_mismatches outside 0..64, error_permille outside 0..500 (fastp's defaults:
+ *   30, 5, 200).  The rule is modelled on fastp's overlap analysis (no indels); it is the project's own and claims none of fastp's bytes.
+ * The rule, per pair (mate 1 of n1 letters, mate 2 of n2):
+ *   1. Letters are folded as mlst_set_read_dedup folds them: A C G T in either case stand for themselves, every other byte is N.  c2 is
+ *      the reverse complement of mate 2; the complement of N is N.
+ *   2. A candidate is an offset o: letter j of c2 lies on letter o + j of mate 1, -(n2 - min_overlap) <= o <= n1 - min_overlap.  Its
+ *      overlap is positions max(0, o) .. min(n1, o + n2) - 1 of mate 1, L of them.  A candidate with L < min_overlap is none: a mate
+ *      shorter than min_overlap has no candidate.
+ *   3. A position matches if both letters are one of ACGT and equal; an N on either side is a mismatch.  mism = L - matches.
+ *   4. A candidate is valid if mism <= max_mismatches and mism <= (L * error_permille) / 1000, in integers.
+ *   5. The valid candidate with the most matches is chosen; among equals the smallest o.
+ *   6. The insert then ends at I = o + n2 + trim5 in the coordinates of either prepared mate, trim5 being mlst_set_read_prep's (both
+ *      mates lost that many bases in front).  Mate 1 keeps min(n1, I) bases and qualities, mate 2 min(n2, I).  A pair without a
+ *      candidate stays as it is, and so does one whose I cuts neither mate: mates that overlap in their middles.
+ *   7. A mate left without a base stays a read of length 0 (mlst_set_read_prep's rule 4).
+ *   8. It runs behind mlst_set_read_prep's steps and mlst_set_read_adapters' cut and in front of mlst_set_read_dedup; the prepared tables
+ *      of mlst_set_read_stats are counted behind it (also when it is the only step that ran).
+ *   Limits: an insert shorter than min_overlap is not seen (that is mlst_set_read_adapters' job); two mates of one low-complexity repeat
+ *   can overlap at a wrong offset.  Not done: correcting mismatching bases inside the overlap, merging the mates into one read.
+ * Entries it applies to: the paired forms of the FASTQ entries -- mlst_submit_fastq and mlst_submit_fastq_stream with paired,
+ *   mlst_submit_fastq_pair, mlst_submit_fastq_bgzf with paired, mlst_submit_fastq_bgzf_pair.  While it is on every other way of adding
+ *   reads is MLST_E_INVALID with a reason: the entries mlst_set_read_dedup refuses ("<entry>: mate overlap trimming is on
+ *   (mlst_set_read_pair_overlap) ..."), mlst_set_read_tiling, an unpaired FASTQ submission, and a paired chunk with an odd number of
+ *   records (a paired mlst_submit_fastq_stream chunk cut behind a first mate; a BGZF piece that ends behind a first mate keeps
+ *   that record for the next piece instead).  When the switch and its setting may change: exactly as
+ *   for mlst_set_read_prep.  mlst_reset_sample zeroes the counters and keeps the switch and its setting.  The result does not depend on
+ *   how the text was cut into chunks.
+ * mlst_get_read_pair_overlap: the switch and the setting (the three pointers may be NULL).
+ * mlst_read_pair_overlap_info: out[0] = pairs seen, out[1] = overlapping pairs (those with a chosen candidate), out[2] = pairs of which
+ *   a mate was cut, out[3] = reads cut, out[4] = bases removed, out[5] = mates of length >= 1 left without a base, out[6..7] = 0.
+ * mlst_read_pair_overlap_hist: MLST_PO_HIST words; word k = overlapping pairs with min(o + n2 + 2 * trim5, MLST_PO_HIST - 1) == k, the
+ *   fragment length in the file's coordinates, each overlapping pair counted once.  cap < MLST_PO_HIST is MLST_E_INVALID.
+ *   Both are all zero with the switch off; an open BGZF piece is finished first.
+ * No host synchronisation is added per chunk; mlst_get_kernel_time 22 is k_po_cut alone. */
+#define MLST_PO_HIST 1024
+int mlst_set_read_pair_overlap(mlst_handle* h, int on, uint32_t min_overlap, uint32_t max_mismatches, uint32_t error_permille);
+int mlst_get_read_pair_overlap(mlst_handle* h, int* on, uint32_t* min_overlap, uint32_t* max_mismatches, uint32_t* error_permille);
+int mlst_read_pair_overlap_info(mlst_handle* h, uint64_t out[8]);
+int mlst_read_pair_overlap_hist(mlst_handle* h, uint64_t* out, uint64_t cap);
+
 /* ---- bowtie2's MD:Z field in the text export (off by default; csrc/aln_text.h; `cli type --md`) --------------------------------------
  * mlst_set_export_md(h, 1): every record of mlst_alignments_text_* carries MD:Z:<text> between NM:i and YT:Z:UU, bowtie2's place;
  *   columns 1-11 and every other field are the bytes they are without it.  With the switch off the export writes what it wrote
@@ -896,7 +942,7 @@ int mlst_set_profiling(mlst_handle* h, int on);   /* 0 = off, 1 = events + sieve
  * csrc/fastq_tile.h, csrc/bam_tile.h; outside 6); 15 = the line table of a SAM chunk (k_fq_count, k_fq_scan, k_fq_lines, k_sam_flags), 16 =
  * k_sam_accumulate and 17 = k_sam_pileup (csrc/sam_dev.h; two entries of 15 per chunk); 18 = k_rp_qtrim (csrc/read_prep.h) and 19 = k_ra_cut
  * (csrc/read_adapt.h), each alone (inside 6); 20 = k_rs_count (csrc/read_stats.h; alone, inside 6); 21 = k_dd_insert + k_dd_sign + k_dd_mark
- * (csrc/read_dedup.h; the three launches of a chunk together, inside 6); 9 = k_route, 10 =
+ * (csrc/read_dedup.h; the three launches of a chunk together, inside 6); 22 = k_po_cut (csrc/read_overlap.h; alone, inside 6); 9 = k_route, 10 =
  * k_route_probe and 11 = k_route_verify, the three kernels of the routed sieve (inside 0) (events bracket the launch on the engine's
  * stream, so with several engines on one GPU they include the time a kernel queues behind another stream's kernel);
  * 7 = the sieve's execution window measured inside the kernel (wall clock at the first workgroup's start and the last

@@ -162,6 +162,24 @@ def _type_parser(sub):
                         "FASTQ, `a.fq,b.fq`, -2; refused with --alignments, --contigs, --long-reads, --long-bam-reads, a reads BAM, a "
                         "folder or several samples, and --gpus N.  Unless --quiet, one line reports units, duplicates, bases removed and "
                         "how often the distinct reads occur")
+    p.add_argument("--pair-overlap", dest="pair_overlap", action="store_true",
+                   help="-2 MATES: trim adapter read-through from both mates of every pair before they are aligned, on the GPU "
+                        "(csrc/read_overlap.h; the rule: metamlst_amd.fastq.pair_overlap / trim_pair_overlap, modelled on fastp's overlap "
+                        "analysis without indels; it is the project's own and claims none of fastp's bytes).  When the insert is shorter "
+                        "than the reads, both mates run through it into the adapter; the mates overlap as reverse complements, and the "
+                        "overlap says where the insert ends, so no adapter sequence is needed and a tail of one base is found.  It runs "
+                        "behind --trim* / --adapter and in front of --dedup; with --read-stats the prepared stage shows the cut reads.  An "
+                        "insert shorter than the minimum overlap is not seen (that is --adapter's job), and two mates of one "
+                        "low-complexity repeat can overlap at a wrong offset.  One sample on one GPU with -2: plain, .gz and bgzip'd mates "
+                        "whose records share their names; refused without -2, with --alignments, --contigs, --long-reads, "
+                        "--long-bam-reads, a reads BAM, a folder or several samples, and --gpus N.  Unless --quiet, one line reports pairs, "
+                        "overlapping pairs, pairs cut, bases removed and the median insert of the overlapping pairs")
+    p.add_argument("--pair-overlap-min", dest="pair_overlap_min", default=None, type=int, metavar="N",
+                   help="--pair-overlap: the mates must lie on each other over at least N bases (8 to 320, default 30)")
+    p.add_argument("--pair-overlap-diff", dest="pair_overlap_diff", default=None, type=int, metavar="N",
+                   help="--pair-overlap: at most N letters of the overlap may differ (0 to 64, default 5)")
+    p.add_argument("--pair-overlap-rate", dest="pair_overlap_rate", default=None, type=float, metavar="X",
+                   help="--pair-overlap: and at most floor(X * overlap) of them (0 to 0.5, default 0.2; kept as round(1000 * X) permille)")
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -346,6 +364,29 @@ def run_type(a, argv=None) -> int:
             if on:
                 print("duplicate removal (--dedup): " + why)
                 return 1
+    pair_overlap = _pair_overlap_of(a)
+    if pair_overlap is not None:      # (refused before any GPU use, each with its reason)
+        if pair_overlap is False:
+            return 1
+        for on, why in ((a.alignments, "with --alignments the file holds alignments, not mates to lay on each other"),
+                        (a.contigs, "--contigs cuts assemblies into windows, and a window has no mate"),
+                        (a.long_reads, "--long-reads cuts unpaired reads into windows, and a window has no mate"),
+                        (a.long_bam_reads, "--long-bam-reads cuts unpaired reads into windows, and a window has no mate"),
+                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the mates of a BAM are taken as they are stored: FASTQ input with -2 only"),
+                        (many, "several samples or a folder are typed without it (the rule is per pair: summing the counters of the samples is the follow-up)"),
+                        (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "one GPU: the counters of the ranks of --gpus N are not summed yet (the follow-up)"),
+                        (not a.mates, "it lays the mates of a pair on each other: give the second file with -2"),
+                        (bool(a.mates) and len(samples[0]) > 1, "it takes one file of first mates and one of second mates (-2), not `a.fq,b.fq`")):
+            if on:
+                print("--pair-overlap: " + why)
+                return 1
+        try:
+            if not mates_share_names(samples[0][0], a.mates):
+                print("--pair-overlap: the records of %s and %s do not share their names, so the files go in as two unpaired texts and no read has a mate" % (samples[0][0], a.mates))
+                return 1
+        except OSError as e:
+            print("--pair-overlap: %s" % e)
+            return 1
     if a.md and not (a.write_sam or a.write_sam_all):      # (with an export flag it is accepted and refused where that flag is: below)
         print("--md: it adds MD:Z to the records of an export: give --write-sam or --write-sam-all")
         return 1
@@ -418,6 +459,8 @@ def run_type(a, argv=None) -> int:
         eng.set_read_stats(True)
     if getattr(a, "dedup", False):      # (likewise: compared where the text is parsed, behind the preparation)
         eng.set_read_dedup(True)
+    if pair_overlap:      # (likewise: the mates are laid on each other where the text is parsed, behind the cut)
+        eng.set_read_pair_overlap(True, **pair_overlap)
     # the built host index is kept next to the database (as the reference keeps <idx>.1.bt2: metamlst-index.py:224-225) unless a
     # species filter made this index a one-off or MLST_INDEX_CACHE=0
     ref_cache = (a.database + ".mlstref") if (not a.filter and os.environ.get("MLST_INDEX_CACHE", "1") != "0") else ""
@@ -555,6 +598,8 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
         _say_read_prep(eng.read_prep_info(), 1)
     if rc == 0 and not a.quiet and _adapters_of(a, say=False):
         _say_read_adapters(eng.read_adapters_info(), eng.get_read_adapters()["adapters"], 1)
+    if rc == 0 and not a.quiet and _pair_overlap_of(a, say=False):
+        print(read_pair_overlap_line(eng.read_pair_overlap_info()), flush=True)
     if rc == 0 and getattr(a, "read_stats", False):
         _write_read_stats(a, eng)
     if rc == 0 and not a.quiet and getattr(a, "dedup", False):
@@ -623,6 +668,44 @@ def _adapters_of(a, say: bool = True):
             print("--adapter: %s" % e)
         return False
     return {"adapters": [x.decode() for x in ads], "min_overlap": 3 if mo is None else mo, "error_permille": permille}
+
+
+def _pair_overlap_of(a, say: bool = True):
+    """--pair-overlap, --pair-overlap-min, --pair-overlap-diff, --pair-overlap-rate -> the arguments of Engine.set_read_pair_overlap, None
+    when --pair-overlap is not given, False (said) when a flag is out of range or given without --pair-overlap"""
+    from .fastq import check_pair_overlap
+    mo, mm, er = getattr(a, "pair_overlap_min", None), getattr(a, "pair_overlap_diff", None), getattr(a, "pair_overlap_rate", None)
+    if not getattr(a, "pair_overlap", False):
+        for flag, v in (("--pair-overlap-min", mo), ("--pair-overlap-diff", mm), ("--pair-overlap-rate", er)):
+            if v is not None:
+                if say:
+                    print(flag + " belongs to --pair-overlap: give the switch it applies to")
+                return False
+        return None
+    try:
+        if er is not None and not 0 <= er <= 0.5:
+            raise ValueError("--pair-overlap-rate takes a number from 0 to 0.5, not %r" % er)
+        out = {"min_overlap": 30 if mo is None else mo, "max_mismatches": 5 if mm is None else mm, "error_permille": 200 if er is None else int(round(1000 * er))}
+        check_pair_overlap(**out)
+    except ValueError as e:
+        if say:
+            print("--pair-overlap: %s" % e)
+        return False
+    return out
+
+
+def read_pair_overlap_line(info: dict) -> str:
+    """The line on what --pair-overlap did (info: Engine.read_pair_overlap_info() or fastq.trim_pair_overlap's counters): pairs,
+    overlapping pairs and their share of the pairs to one decimal (in integers, rounded half up), pairs cut, bases removed, reads left
+    without a base, and the median insert of the overlapping pairs (fastq.pair_overlap_median; left out when no pair overlaps)"""
+    from .fastq import pair_overlap_median
+    pairs, ov = int(info["pairs"]), int(info["overlapping"])
+    tenths = (1000 * ov + pairs // 2) // pairs if pairs else 0
+    line = ("mate overlap trimming: %d pairs, %d overlapping (%d.%d %%), %d pairs cut (%d reads), %d bases removed, %d reads left without a base"
+            % (pairs, ov, tenths // 10, tenths % 10, int(info["trimmed_pairs"]), int(info["reads_trimmed"]), int(info["bases_removed"]), int(info["emptied"])))
+    if ov:
+        line += "; median insert of the overlapping pairs %d" % pair_overlap_median(info["insert_hist"])
+    return line
 
 
 def read_dedup_line(info: dict, paired: bool = False) -> str:

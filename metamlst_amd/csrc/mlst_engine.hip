@@ -3692,6 +3692,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "read_prep.h"
 #include "read_adapt.h"
 #include "read_dedup.h"
+#include "read_overlap.h"
 #include "read_stats.h"
 #include "aln_text.h"
 #include "reads_text.h"
@@ -3800,7 +3801,7 @@ struct mlst_handle {
     GraphSlot g_submit, g_typing; bool use_graphs = true;
     std::vector<EvPair> events;
     std::vector<hipEvent_t> ev_pool;
-    double k_ms[22] = {0}; u64 k_n[22] = {0};      // see mlst_get_kernel_time
+    double k_ms[23] = {0}; u64 k_n[23] = {0};      // see mlst_get_kernel_time
     double wall_khz = 100000.0;                  // wall_clock64 rate (hipDeviceAttributeWallClockRate)
     struct BamStream* bam = nullptr;             // BAM input (mlst_bam_open / mlst_submit_bam_bgzf), allocated by the first stream
     u32 bam_force_miss = 0; u64 bam_max_entries = 0;      // mlst_debug_bam_split, mlst_bam_set_capacity
@@ -3861,6 +3862,10 @@ struct mlst_handle {
     // the first submission under the switch, which reads MLST_DEDUP_SLOTS / MLST_DEDUP_TAG_BITS --, the units and reads submitted so far
     struct { bool on = false; DdTab tab = {nullptr, nullptr, nullptr, nullptr, 0, 0}; u8* d_mem = nullptr; DdCtr* d_ctr = nullptr;
              u32* d_slot_of = nullptr; u64* d_key2 = nullptr; u64 cap_units = 0, units_seen = 0, reads = 0; } dd;
+    // adapter read-through cut from the overlap of the mates before the reads are packed (mlst_set_read_pair_overlap; csrc/read_overlap.h):
+    // the switch, the setting (trim5 is filled in per chunk from mlst_set_read_prep's), the counters and the insert histogram on the
+    // device -- allocated by the first submission under the switch --, the pairs submitted so far and the device's CU count
+    struct { bool on = false; PoSet set = {30, 5, 200, 0}; PoCtr* d_ctr = nullptr; u64 pairs = 0; int n_cu = 0; } po;
 };
 
 static std::string g_create_err;
@@ -3883,6 +3888,7 @@ static int rp_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_p
 static int ra_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_adapters is on: an entry that does not cut its reads is refused
 static int rs_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_stats is on: an entry whose reads are not counted is refused
 static int dd_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_dedup is on: an entry whose reads are not compared is refused
+static int po_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_pair_overlap is on: an entry that does not hand over pairs of FASTQ text is refused
 static void at_free(mlst_handle* h);      // the per-export tables of mlst_alignments_text_*
 static const char* bam_kind(const mlst_handle* h);      // "BAM" or "SAM": what the open stream of ready-made alignments takes
 template <typename T> static hipError_t dmalloc(T** p, u64 n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
@@ -4053,7 +4059,7 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     if (h->copy_stream) hipStreamDestroy(h->copy_stream);
     hipFree(h->d_cand); hipFree(h->d_in_bases); hipFree(h->d_in_quals); hipFree(h->d_in_off);
     hipFree(h->d_fq_slot[0]); hipFree(h->d_fq_slot[1]); hipFree(h->d_fq_nl[0]); hipFree(h->d_fq_nl[1]); hipFree(h->d_fq_blk); hipFree(h->d_fq_lines); hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); hipFree(h->d_fq_meta);
-    hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta); hipFree(h->rp.d_ctr); hipFree(h->ra.d_ctr); hipFree(h->rs.d_tab);
+    hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta); hipFree(h->rp.d_ctr); hipFree(h->ra.d_ctr); hipFree(h->rs.d_tab); hipFree(h->po.d_ctr);
     hipFree(h->dd.d_mem); hipFree(h->dd.d_ctr); hipFree(h->dd.d_slot_of); hipFree(h->dd.d_key2);
     hipFree(h->fa.d_desc); hipFree(h->fa.d_meta); hipFree(h->fa.d_flat); hipFree(h->fa.d_kind); hipFree(h->fa.d_cseq); hipFree(h->fa.d_chdr); hipFree(h->fa.d_cstart); hipFree(h->fa.d_wcnt);
     if (h->fa.h_fa) hipHostFree(h->fa.h_fa);
@@ -4093,6 +4099,8 @@ static int reset_sample_state(mlst_handle* h) {
     h->rs.side = 0; h->rs.launches[0] = h->rs.launches[1] = 0;
     if (h->dd.d_mem) { int rc = dd_clear(h, h->dd.tab); if (rc) return rc; }      // mlst_set_read_dedup: the keys are the sample's; the switch and the table's size stay
     if (h->dd.d_ctr) HIPCHK(h, hipMemsetAsync(h->dd.d_ctr, 0, sizeof(DdCtr), h->stream));
+    if (h->po.d_ctr) HIPCHK(h, hipMemsetAsync(h->po.d_ctr, 0, sizeof(PoCtr), h->stream));      // mlst_set_read_pair_overlap: the counters are the sample's; the switch and its setting stay
+    h->po.pairs = 0;
     h->dd.units_seen = h->dd.reads = 0;
     h->reads_seen = 0; h->fq_carry_len = 0; h->max_wpr = 0;
     h->last_pack.n_reads = 0; h->last_pack.wpr = h->last_pack.qstride = 0;
@@ -4711,6 +4719,7 @@ extern "C" int mlst_submit_packed_device(mlst_handle* h, const uint32_t* d_packe
     { int rc_ = ra_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     { int rc_ = dd_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
+    { int rc_ = po_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     return submit_impl(h, d_packed, d_qrows, d_lens, n_reads, wpr, qstride, paired, 0);
 }
 static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* d_qrows, const uint16_t* d_lens,
@@ -4862,6 +4871,7 @@ extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, 
     { int rc_ = ra_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     { int rc_ = dd_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
+    { int rc_ = po_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     hipSetDevice(h->device);
@@ -4882,6 +4892,7 @@ extern "C" int mlst_submit_reads(mlst_handle* h, const uint8_t* bases, const uin
     { int rc_ = ra_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     { int rc_ = dd_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
+    { int rc_ = po_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (n_reads == 0) return MLST_OK;
@@ -4951,6 +4962,11 @@ static int rs_refuse(mlst_handle* h, const char* entry) {
 // mlst_set_read_dedup (csrc/read_dedup.h): with the switch on, reads come from FASTQ text only, where they are compared
 static int dd_refuse(mlst_handle* h, const char* entry) {
     if (h && h->dd.on) return fail(h, MLST_E_INVALID, "%s: duplicate removal is on (mlst_set_read_dedup) and only the FASTQ text and BGZF entries apply it", entry);
+    return MLST_OK;
+}
+// mlst_set_read_pair_overlap (csrc/read_overlap.h): with the switch on, reads come as pairs of FASTQ text only, where the mates are laid on each other
+static int po_refuse(mlst_handle* h, const char* entry) {
+    if (h && h->po.on) return fail(h, MLST_E_INVALID, "%s: mate overlap trimming is on (mlst_set_read_pair_overlap) and only the paired FASTQ text and BGZF entries apply it", entry);
     return MLST_OK;
 }
 // one launch of k_rs_count over the chunk's reads as offsets and lengths stand now: stage 0 in front of k_rp_qtrim (which rewrites the
@@ -5041,10 +5057,38 @@ static int dd_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
     D.units_seen += n_units; D.reads += n_reads;
     return MLST_OK;
 }
+// mlst_set_read_pair_overlap's launch over a chunk's pairs as their lengths stand now, behind the trims and the adapter cut, in front of the
+// prepared read statistics and the duplicate removal.  flags[0] is zeroed once more: k_po_cut alone feeds the longest length it leaves.
+// At most three workgroups of eight waves per CU (what its registers let a CU hold; each flushes its histogram in LDS once), fewer for few pairs
+static int po_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
+    auto& O = h->po;
+    if (!paired) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: an unpaired FASTQ submission: mate overlap trimming is on and takes pairs (the paired entries; `-2` with mates that share their names)");
+    if (n_reads & 1) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: a paired chunk holds %llu records: the mates of a pair are laid on each other within one chunk", (unsigned long long)n_reads);
+    const u64 n_pairs = n_reads / 2;
+    if (!n_pairs) return MLST_OK;
+    if (!O.d_ctr) { HIPCHK(h, dmalloc(&O.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(O.d_ctr, 0, sizeof(PoCtr), h->stream)); }
+    if (!O.n_cu) { HIPCHK(h, hipDeviceGetAttribute(&O.n_cu, hipDeviceAttributeMultiprocessorCount, h->device)); if (O.n_cu < 1) O.n_cu = 1; }
+    PoSet S = O.set;
+    S.trim5 = h->rp.on ? h->rp.set.trim5 : 0u;
+    HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
+    {
+        Prof pf(h, 22);      // (mlst_get_kernel_time 22: k_po_cut alone)
+        const u32 grid = (u32)std::min<u64>((n_pairs + PO_WAVES - 1) / PO_WAVES, 3ull * (u64)O.n_cu);
+        hipLaunchKernelGGL(k_po_cut, dim3(grid), dim3(64 * PO_WAVES), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, h->d_lens, n_pairs, S, d_flags, O.d_ctr);
+    }
+    HIPCHK(h, hipGetLastError());
+    O.pairs += n_pairs;
+    return MLST_OK;
+}
 static int rp_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
     const RpSet& P = h->rp.set;
     const bool trims = h->rp.on && (P.trim5 | P.trim3 | P.trim_qual);      // (the Phred base alone is k_pack_text's)
     if (h->rs.on) { int rc = rs_launch(h, n_reads, d_flags, paired, 0); if (rc) return rc; }
+    if (h->po.on && !trims && !h->ra.on) {      // mlst_set_read_pair_overlap alone: the prepared tables are counted behind it all the same
+        int rc = po_apply(h, n_reads, d_flags, paired); if (rc) return rc;
+        if (h->rs.on) { rc = rs_launch(h, n_reads, d_flags, paired, 1); if (rc) return rc; }
+        return h->dd.on ? dd_apply(h, n_reads, d_flags, paired) : MLST_OK;
+    }
     if (!trims && !h->ra.on) return h->dd.on ? dd_apply(h, n_reads, d_flags, paired) : MLST_OK;      // (mlst_set_read_dedup alone still runs)
     if (trims && !h->rp.d_ctr) { HIPCHK(h, dmalloc(&h->rp.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->rp.d_ctr, 0, sizeof(RpCtr), h->stream)); }
     if (h->ra.on && !h->ra.d_ctr) { HIPCHK(h, dmalloc(&h->ra.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->ra.d_ctr, 0, sizeof(RaCtr), h->stream)); }
@@ -5062,6 +5106,7 @@ static int rp_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
         hipLaunchKernelGGL(k_ra_cut, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, h->d_lens, n_reads, h->ra.set,
                            d_flags, h->ra.d_ctr);
     }
+    if (h->po.on) { int rc = po_apply(h, n_reads, d_flags, paired); if (rc) return rc; }      // mlst_set_read_pair_overlap: behind the cut, in front of the prepared tables
     if (h->rs.on) { int rc = rs_launch(h, n_reads, d_flags, paired, 1); if (rc) return rc; }
     return h->dd.on ? dd_apply(h, n_reads, d_flags, paired) : MLST_OK;      // mlst_set_read_dedup: behind the prepared tables, which stay what they are
 }
@@ -5082,8 +5127,10 @@ static int fq_tile_submit(mlst_handle* h, u64 n_bytes, u64 n_lines, u64 n_recs, 
 // tslot: the text slot the chunk sits in (-1: the current one); skip: bytes of filler in front of the first line (see k_fq_lines).
 // ext_blk (optional): the newline counts per FQ_BLOCK bytes come with the text (the inflate counted them while writing it) except for
 // the first count_bytes bytes (a multiple of FQ_BLOCK: the filler and the partial record in front of an inflated piece).
+// pair_carry (the BGZF entries, whose pieces end where their blocks end): under mlst_set_read_pair_overlap a paired piece that is not the
+// last and holds an odd number of records keeps its last record, a first mate, with the partial one for the next piece.
 static int fastq_pipeline(mlst_handle* h, u64 n_bytes, int paired, bool whole, uint64_t* n_reads_out, u64 pair_boundary = 0, int tslot = -1, u64 skip = 0,
-                          u32* ext_blk = nullptr, u64 count_bytes = 0) {
+                          u32* ext_blk = nullptr, u64 count_bytes = 0, bool pair_carry = false) {
     if (tslot < 0) tslot = h->fq_slot;
     const u64 n_blocks = (n_bytes + FQ_BLOCK - 1) / FQ_BLOCK;
     if (!ext_blk && h->cap_fq_blk < n_blocks) { hipFree(h->d_fq_blk); h->d_fq_blk = nullptr; HIPCHK(h, dmalloc(&h->d_fq_blk, n_blocks + 1)); h->cap_fq_blk = n_blocks; }
@@ -5098,7 +5145,8 @@ static int fastq_pipeline(mlst_handle* h, u64 n_bytes, int paired, bool whole, u
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (n_lines >= (1ull << 32)) return fail(h, MLST_E_LIMIT, "more than 2^32 lines in one FASTQ chunk");
     if (whole && n_lines % 4 != 0) return fail(h, MLST_E_INVALID, "FASTQ chunk holds %llu lines: not a whole number of 4-line records", (unsigned long long)n_lines);
-    const u64 n_reads = n_lines / 4;
+    u64 n_reads = n_lines / 4;
+    if (!whole && pair_carry && paired && h->po.on && (n_reads & 1)) n_reads--;
     if (h->cap_fq_lines < n_lines + 2) { hipFree(h->d_fq_lines); h->d_fq_lines = nullptr; HIPCHK(h, dmalloc(&h->d_fq_lines, n_lines + 2)); h->cap_fq_lines = n_lines + 2; }
     hipLaunchKernelGGL(k_fq_lines, dim3((u32)n_blocks), dim3(256), 0, h->stream, h->d_fq_text, (u64)n_bytes, blk, h->d_fq_lines, skip);
     h->fq_carry_len = 0;
@@ -5175,7 +5223,7 @@ static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, i
     if (!h->rn.on) HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
     if (n_reads_out) *n_reads_out = n_reads;
     h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
-    if (!h->rn.on && (h->rp.on || h->ra.on || h->rs.on || h->dd.on)) return submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);      // (the public entry refuses under mlst_set_read_prep / mlst_set_read_adapters)
+    if (!h->rn.on && (h->rp.on || h->ra.on || h->rs.on || h->dd.on || h->po.on)) return submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);      // (the public entry refuses under mlst_set_read_prep / mlst_set_read_adapters)
     if (!h->rn.on) return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired);
     // mlst_set_read_names: the text outlives pass 1 of its chunk -- the names of the reads it retained are copied out of the header
     // lines (csrc/read_names.h), behind the submission and outside its captured graph, and only then is the slot released
@@ -5335,6 +5383,7 @@ extern "C" int mlst_submit_packed_host(mlst_handle* h, const uint32_t* packed, c
     { int rc_ = ra_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     { int rc_ = dd_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
+    { int rc_ = po_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (!packed || !qrows || !lens) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -5547,7 +5596,7 @@ static int bz_finish(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
     if (skip) HIPCHK(h, hipMemsetAsync(slot + base, 'X', skip, h->stream));
     h->d_fq_text = slot + base;
     u32* counts = h->bz_pend.counted ? h->d_fq_nl[h->bz_pend.tslot] + base / FQ_BLOCK : nullptr;
-    return fastq_pipeline(h, skip + carry + h->bz_pend.text_bytes, h->bz_pend.paired, whole, n_reads_out, 0, h->bz_pend.tslot, skip, counts, FQ_HEAD - base);
+    return fastq_pipeline(h, skip + carry + h->bz_pend.text_bytes, h->bz_pend.paired, whole, n_reads_out, 0, h->bz_pend.tslot, skip, counts, FQ_HEAD - base, true);
 }
 // a piece that is still open is finished (its trailing partial record stays in the carry, as after any non-final chunk)
 static int bz_flush(mlst_handle* h) {
@@ -5757,7 +5806,7 @@ extern "C" int mlst_submit_fastq_bgzf(mlst_handle* h, const uint8_t* data, uint6
         HIPCHK(h, hipStreamSynchronize(h->stream));      // also: blks / data may be released by the caller after this
         if (err[0]) return bz_fail(h, err, err[0] - 1, " of the chunk");
     }
-    return fastq_pipeline(h, text_bytes, paired, final_chunk != 0, n_reads_out);
+    return fastq_pipeline(h, text_bytes, paired, final_chunk != 0, n_reads_out, 0, -1, 0, nullptr, 0, true);
 }
 
 // ---- bgzip'd mate files (mlst_submit_fastq_bgzf_pair).  A call's blocks of BOTH files go into one block list and one inflate
@@ -6668,6 +6717,7 @@ extern "C" int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip
     { int rc_ = ra_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = dd_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
+    { int rc_ = po_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6716,6 +6766,7 @@ extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n
     { int rc_ = ra_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = rs_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = dd_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
+    { int rc_ = po_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6890,6 +6941,7 @@ extern "C" int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t 
     if (read_len) { int rc_ = ra_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
     if (read_len) { int rc_ = rs_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
     if (read_len) { int rc_ = dd_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
+    if (read_len) { int rc_ = po_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window has no mate)
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
     // (a reads stream took its tile when it was opened: include/mlst.h gives one message for every stream of reads)
     if (bam_is_open(h) && h->bam->reads) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (the reads stream of a BAM: its last chunk was not marked final)");
@@ -7092,6 +7144,58 @@ extern "C" int mlst_read_dedup_info(mlst_handle* h, uint64_t out[16]) {
     out[7] = h->dd.tab.slots;
     for (int k = 0; k < 8; k++) out[8 + k] = c.levels[k];
     return MLST_OK;
+}
+// adapter read-through cut from the overlap of the mates (include/mlst.h; csrc/read_overlap.h): the switch's life cycle is mlst_set_read_prep's
+extern "C" int mlst_set_read_pair_overlap(mlst_handle* h, int on, uint32_t min_overlap, uint32_t max_mismatches, uint32_t error_permille) {
+    if (!h) return MLST_E_INVALID;
+    if (on) {
+        if (min_overlap < 8 || min_overlap > PO_MAX_LEN) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: min_overlap %u is outside 8..%d", min_overlap, PO_MAX_LEN);
+        if (max_mismatches > 64) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: max_mismatches %u is outside 0..64", max_mismatches);
+        if (error_permille > 500) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: error_permille %u is outside 0..500", error_permille);
+    }
+    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
+    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
+    const bool same = (on != 0) == h->po.on && (!on || (min_overlap == h->po.set.min_overlap && max_mismatches == h->po.set.max_mism && error_permille == h->po.set.permille));
+    if (!same && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_pair_overlap changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
+    if (on && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: mlst_set_read_tiling is on and takes unpaired text, whose windows have no mate");
+    h->po.on = on != 0;
+    if (on) { h->po.set.min_overlap = min_overlap; h->po.set.max_mism = max_mismatches; h->po.set.permille = error_permille; }
+    return MLST_OK;
+}
+extern "C" int mlst_get_read_pair_overlap(mlst_handle* h, int* on, uint32_t* min_overlap, uint32_t* max_mismatches, uint32_t* error_permille) {
+    if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
+    *on = h->po.on ? 1 : 0;
+    if (min_overlap) *min_overlap = h->po.set.min_overlap;
+    if (max_mismatches) *max_mismatches = h->po.set.max_mism;
+    if (error_permille) *error_permille = h->po.set.permille;
+    return MLST_OK;
+}
+// the counters and the histogram of the device, all zero with the switch off or before the first pair
+static int po_fetch(mlst_handle* h, PoCtr* c) {
+    memset(c, 0, sizeof *c);
+    hipSetDevice(h->device);
+    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
+    if (!h->po.on || !h->po.d_ctr) return MLST_OK;
+    HIPCHK(h, hipMemcpyAsync(c, h->po.d_ctr, sizeof *c, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MLST_OK;
+}
+extern "C" int mlst_read_pair_overlap_info(mlst_handle* h, uint64_t out[8]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    PoCtr* const pc = new PoCtr;
+    int rc = po_fetch(h, pc);
+    if (!rc) { out[0] = h->po.on ? h->po.pairs : 0; out[1] = pc->overlapping; out[2] = pc->trimmed_pairs; out[3] = pc->reads_trimmed; out[4] = pc->bases_removed; out[5] = pc->emptied; out[6] = 0; out[7] = 0; }
+    delete pc;
+    return rc;
+}
+extern "C" int mlst_read_pair_overlap_hist(mlst_handle* h, uint64_t* out, uint64_t cap) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    if (cap < PO_HIST) return fail(h, MLST_E_INVALID, "mlst_read_pair_overlap_hist: the buffer holds %llu words, %d are needed", (unsigned long long)cap, PO_HIST);
+    PoCtr* const pc = new PoCtr;
+    int rc = po_fetch(h, pc);
+    if (!rc) memcpy(out, pc->hist, sizeof pc->hist);
+    delete pc;
+    return rc;
 }
 // MD:Z in the text export (include/mlst.h): no part of the sample's state; mlst_alignments_text_open reads it
 extern "C" int mlst_set_export_md(mlst_handle* h, int on) {
@@ -8133,13 +8237,13 @@ extern "C" int mlst_get_items(mlst_handle* h, mlst_item* out, uint64_t cap, uint
 
 extern "C" int mlst_set_profiling(mlst_handle* h, int on) { if (!h) return MLST_E_INVALID; drain_events(h); h->profiling = on == 1; h->window = on != 0; return MLST_OK; }
 extern "C" int mlst_get_kernel_time(mlst_handle* h, int which, double* total_ms, uint64_t* launches) {
-    if (!h || which < 0 || which >= 22) return MLST_E_INVALID;
+    if (!h || which < 0 || which >= 23) return MLST_E_INVALID;
     hipSetDevice(h->device); drain_events(h);
     if (total_ms) *total_ms = h->k_ms[which];
     if (launches) *launches = h->k_n[which];
     return MLST_OK;
 }
-extern "C" int mlst_reset_kernel_time(mlst_handle* h) { if (!h) return MLST_E_INVALID; drain_events(h); for (int i = 0; i < 22; i++) { h->k_ms[i] = 0; h->k_n[i] = 0; } return MLST_OK; }
+extern "C" int mlst_reset_kernel_time(mlst_handle* h) { if (!h) return MLST_E_INVALID; drain_events(h); for (int i = 0; i < 23; i++) { h->k_ms[i] = 0; h->k_n[i] = 0; } return MLST_OK; }
 extern "C" int mlst_get_index_bytes(mlst_handle* h, uint64_t out[4]) {
     if (!h || !out) return MLST_E_INVALID;
     out[0] = h->bytes_arena + h->bytes_hap; out[1] = h->bytes_sieve; out[2] = h->bytes_table; out[3] = (u64)(h->bitmap_fill * 1e6); return MLST_OK;

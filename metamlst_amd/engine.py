@@ -182,6 +182,10 @@ def load_library(path: str | None = None):
         "mlst_set_read_dedup": (C.c_int, [H, C.c_int]),
         "mlst_get_read_dedup": (C.c_int, [H, C.POINTER(C.c_int)]),
         "mlst_read_dedup_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "mlst_set_read_pair_overlap": (C.c_int, [H, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "mlst_get_read_pair_overlap": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "mlst_read_pair_overlap_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "mlst_read_pair_overlap_hist": (C.c_int, [H, C.POINTER(C.c_uint64), C.c_uint64]),
         "mlst_set_export_md": (C.c_int, [H, C.c_int]),
         "mlst_get_export_md": (C.c_int, [H, C.POINTER(C.c_int)]),
         "mlst_read_names_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
@@ -957,6 +961,31 @@ class Engine:
         self._check(self.lib.mlst_read_dedup_info(self._h, out), "mlst_read_dedup_info")
         return {"reads": int(out[0]), "units": int(out[1]), "duplicates": int(out[2]), "reads_removed": int(out[3]), "bases_removed": int(out[4]),
                 "distinct": int(out[5]), "clashes": int(out[6]), "slots": int(out[7]), "levels": [int(out[8 + k]) for k in range(8)]}
+
+    def set_read_pair_overlap(self, on: bool = True, min_overlap: int = 30, max_mismatches: int = 5, error_permille: int = 200) -> None:
+        """Cut adapter read-through from both mates of every pair of FASTQ text where the overlap of the mates says the insert ends, on
+        the GPU before the reads are packed (mlst_set_read_pair_overlap; off by default; the rule: fastq.pair_overlap /
+        fastq.trim_pair_overlap), behind set_read_prep's steps and set_read_adapters' cut, in front of set_read_dedup.  The engine then
+        behaves as if it had been given the cut text.  Paired FASTQ text and BGZF entries only -- every other way of adding reads is
+        refused while it is on; may change only while the sample holds no reads and no stream is open.  reset_sample zeroes the
+        counters and keeps the switch."""
+        self._check(self.lib.mlst_set_read_pair_overlap(self._h, 1 if on else 0, int(min_overlap), int(max_mismatches), int(error_permille)), "mlst_set_read_pair_overlap")
+
+    def get_read_pair_overlap(self) -> dict:
+        on, mo, mm, pm = C.c_int(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._check(self.lib.mlst_get_read_pair_overlap(self._h, C.byref(on), C.byref(mo), C.byref(mm), C.byref(pm)), "mlst_get_read_pair_overlap")
+        return {"on": bool(on.value), "min_overlap": int(mo.value), "max_mismatches": int(mm.value), "error_permille": int(pm.value)}
+
+    def read_pair_overlap_info(self) -> dict:
+        """Since the last reset_sample, fastq.trim_pair_overlap's counters -- pairs, overlapping, trimmed_pairs, reads_trimmed,
+        bases_removed, emptied -- and insert_hist (1,024 bins: the fragment length of every overlapping pair in the file's
+        coordinates, the last bin holding the longer ones).  All zero with the switch off."""
+        out = (C.c_uint64 * 8)()
+        self._check(self.lib.mlst_read_pair_overlap_info(self._h, out), "mlst_read_pair_overlap_info")
+        hist = (C.c_uint64 * 1024)()
+        self._check(self.lib.mlst_read_pair_overlap_hist(self._h, hist, 1024), "mlst_read_pair_overlap_hist")
+        return {"pairs": int(out[0]), "overlapping": int(out[1]), "trimmed_pairs": int(out[2]), "reads_trimmed": int(out[3]), "bases_removed": int(out[4]),
+                "emptied": int(out[5]), "insert_hist": [int(v) for v in hist]}
 
     def set_export_md(self, on: bool = True) -> None:
         """export_sam_text / write_sam_all write bowtie2's MD:Z field between NM:i and YT:Z, formatted on the GPU (mlst_set_export_md; off

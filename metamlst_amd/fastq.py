@@ -858,6 +858,117 @@ def trim_adapters(text: bytes, adapters, min_overlap: int = 3, error_permille: i
     return b"".join(out), info
 
 
+_PO_COMP = bytes({65: 84, 67: 71, 71: 67, 84: 65}.get(c, 78) for c in range(256))      # the complement of a folded letter (N stays N)
+
+
+def check_pair_overlap(min_overlap: int = 30, max_mismatches: int = 5, error_permille: int = 200) -> None:
+    """ValueError for a setting mlst_set_read_pair_overlap refuses: min_overlap outside 8..320, max_mismatches outside 0..64,
+    error_permille outside 0..500"""
+    for name, v, lo, hi in (("min_overlap", min_overlap, 8, 320), ("max_mismatches", max_mismatches, 0, 64), ("error_permille", error_permille, 0, 500)):
+        if int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError("%s %r is outside %d..%d" % (name, v, lo, hi))
+
+
+def pair_overlap(seq1: bytes, seq2: bytes, min_overlap: int = 30, max_mismatches: int = 5, error_permille: int = 200):
+    """Where the reverse complement of mate 2 lies on mate 1: (o, matches), or None when the mates do not overlap.  The rule is the
+    project's own, modelled on fastp's overlap analysis (no indels); it does not claim fastp's bytes.
+      * Letters are folded as dedup_fastq folds them: A C G T in either case stand for themselves, every other byte is N.  c2 is the
+        reverse complement of mate 2 (the complement of N is N).
+      * A candidate is an offset o: letter j of c2 lies on letter o + j of mate 1, -(n2 - min_overlap) <= o <= n1 - min_overlap.  Its
+        overlap is positions max(0, o) .. min(n1, o + n2) - 1 of mate 1, L of them; a candidate with L < min_overlap is none (so a mate
+        shorter than min_overlap has no candidate).
+      * A position matches if both letters are one of ACGT and equal: an N on either side is a mismatch.  mism = L - matches.
+      * The candidate is valid if mism <= max_mismatches and mism <= (L * error_permille) // 1000 (integers).
+      * The valid candidate with the most matches is chosen; among equals the smallest o.
+    Limits: an insert shorter than min_overlap is not seen (that is adapter_cut's job), and two mates of one low-complexity repeat
+    can overlap at a wrong offset."""
+    check_pair_overlap(min_overlap, max_mismatches, error_permille)
+    s1 = np.frombuffer(bytes(seq1).translate(_DD_FOLD), np.uint8)
+    c2 = np.frombuffer(bytes(seq2).translate(_DD_FOLD).translate(_PO_COMP)[::-1], np.uint8)
+    n1, n2 = len(s1), len(c2)
+    if n1 < min_overlap or n2 < min_overlap:
+        return None
+    o = np.arange(-(n2 - min_overlap), n1 - min_overlap + 1)
+    full = np.zeros(n1 + n2 - 1, np.int64)                   # matches per offset -(n2 - 1) .. n1 - 1
+    for letter in b"ACGT":
+        full += np.correlate((s1 == letter).astype(np.int64), (c2 == letter).astype(np.int64), "full")
+    matches = full[o + (n2 - 1)]
+    L = np.minimum(n1, o + n2) - np.maximum(0, o)
+    mism = L - matches
+    valid = (L >= min_overlap) & (mism <= max_mismatches) & (mism <= (L * error_permille) // 1000)
+    if not valid.any():
+        return None
+    k = int(np.where(valid, matches, -1).argmax())           # the most matches, the smallest o among equals
+    return int(o[k]), int(matches[k])
+
+
+def trim_pair_overlap(text: bytes, min_overlap: int = 30, max_mismatches: int = 5, error_permille: int = 200, trim5: int = 0) -> tuple[bytes, dict]:
+    """The interleaved paired FASTQ text (records 2j, 2j + 1) the engine behaves as if it had been given under
+    Engine.set_read_pair_overlap(min_overlap, max_mismatches, error_permille), and the counters of Engine.read_pair_overlap_info().
+    This is the rule mlst_set_read_pair_overlap applies on the device (csrc/read_overlap.h, pair_overlap per pair); it serves the tests
+    and whoever wants the cut file -- the command never calls it.  When the insert is shorter than the reads, both mates run through it
+    into the adapter; the overlap of the mates says where the insert ends, and no adapter sequence is needed.
+      * For a pair with a chosen candidate (o, matches) the insert ends at I = o + n2 + trim5 in the coordinates of either prepared mate
+        (trim5: the --trim5 in force, which took that many bases from the front of both mates).  Mate 1 keeps min(n1, I) letters, mate 2
+        min(n2, I); sequence and quality lines are both cut.  Header and '+' line untouched, line ends LF.
+      * A pair without a candidate stays as it is, and so does one whose I cuts neither mate (mates that overlap in their middles).
+      * A mate left without a base stays a record with two empty lines (rule 4 of prep_fastq).
+      * Behind prep_fastq and trim_adapters, in front of dedup_fastq.
+    Counters: pairs, overlapping (pairs with a candidate), trimmed_pairs, reads_trimmed, bases_removed, emptied (mates of length >= 1
+    left without a base) and insert_hist (1,024 bins, indexed by min(o + n2 + 2 * trim5, 1023): the fragment length in the file's
+    coordinates; each overlapping pair is counted once).
+    Limits: pair_overlap's.  Not done here: correcting mismatching bases inside the overlap, merging the mates into one read."""
+    check_pair_overlap(min_overlap, max_mismatches, error_permille)
+    if trim5 < 0:
+        raise ValueError("trim5 must not be negative")
+    lines = bytes(text).split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    if len(lines) % 4:
+        raise ValueError("FASTQ text holds %d lines: not a whole number of 4-line records" % len(lines))
+    if len(lines) % 8:
+        raise ValueError("paired FASTQ text holds %d records: not whole pairs" % (len(lines) // 4))
+    out = []
+    info = {"pairs": 0, "overlapping": 0, "trimmed_pairs": 0, "reads_trimmed": 0, "bases_removed": 0, "emptied": 0, "insert_hist": [0] * 1024}
+    for k in range(0, len(lines), 8):
+        pair = []
+        for m in (0, 4):
+            h, s, p, ql = (x[:-1] if x.endswith(b"\r") else x for x in lines[k + m:k + m + 4])
+            if len(s) != len(ql):
+                raise ValueError("FASTQ record with different sequence and quality lengths: %r" % h[:60])
+            pair.append([h, s, p, ql])
+        info["pairs"] += 1
+        hit = pair_overlap(pair[0][1], pair[1][1], min_overlap, max_mismatches, error_permille)
+        if hit is not None:
+            n2 = len(pair[1][1])
+            info["overlapping"] += 1
+            info["insert_hist"][min(hit[0] + n2 + 2 * trim5, 1023)] += 1
+            end = hit[0] + n2 + trim5
+            cut = 0
+            for r in pair:
+                n = len(r[1])
+                if end < n:
+                    cut += 1
+                    info["bases_removed"] += n - end
+                    info["emptied"] += end == 0
+                    r[1], r[3] = r[1][:end], r[3][:end]
+            info["reads_trimmed"] += cut
+            info["trimmed_pairs"] += cut > 0
+        out += [b"%s\n%s\n%s\n%s\n" % tuple(r) for r in pair]
+    return b"".join(out), info
+
+
+def pair_overlap_median(hist) -> int:
+    """The median insert of insert_hist (the lower median; 0 for an empty histogram)"""
+    total = sum(int(v) for v in hist)
+    seen = 0
+    for k, v in enumerate(hist):
+        seen += int(v)
+        if total and 2 * seen >= total:
+            return k
+    return 0
+
+
 DEDUP_LEVELS = (1, 2, 3, 4, 5, 10, 50, 500)      # the lower edges of the eight levels: keys that occur 1, 2, 3, 4, 5-9, 10-49, 50-499, >= 500 times
 _DD_FOLD = bytes(c if c in b"ACGT" else (c & 0xDF if (c & 0xDF) in b"ACGT" else 78) for c in range(256))      # a letter as the engine aligns it (78: 'N')
 
