@@ -305,81 +305,75 @@ def run_type(a, argv=None) -> int:
         return 1
     many = len(samples) > 1
     if a.read_names:      # (refused before any GPU use, each with its reason)
-        for on, why in ((a.alignments, "with --alignments the file is the input, and its records carry their names already"),
-                        (many, "it names the reads of one sample's export: several samples or a folder are typed without exports"),
-                        (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "the exports take one GPU, so do the names (not --gpus N)"),
-                        (a.contigs, "--contigs cuts assemblies into windows, and a window has no name"),
-                        (a.long_reads, "--long-reads cuts reads into windows, and a window has no name"),
-                        (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and a window has no name"),
-                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the names of a reads BAM are not carried to the exports: FASTQ input only"),
-                        (not (a.write_sam or a.write_sam_all or a.write_reads), "it names the reads of an export: give --write-sam or --write-sam-all")):
-            if on:
-                print("--read-names: " + why)
-                return 1
+        if _refused("--read-names: ", (
+                (a.alignments, "with --alignments the file is the input, and its records carry their names already"),
+                (many, "it names the reads of one sample's export: several samples or a folder are typed without exports"),
+                (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "the exports take one GPU, so do the names (not --gpus N)"),
+                (a.contigs, "--contigs cuts assemblies into windows, and a window has no name"),
+                (a.long_reads, "--long-reads cuts reads into windows, and a window has no name"),
+                (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and a window has no name"),
+                (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the names of a reads BAM are not carried to the exports: FASTQ input only"),
+                (not (a.write_sam or a.write_sam_all or a.write_reads), "it names the reads of an export: give --write-sam or --write-sam-all"))):
+            return 1
     read_prep = _read_prep_of(a)
     if read_prep is not None:      # (refused before any GPU use, each with its reason)
         if read_prep is False:
             return 1
-        for on, why in ((a.alignments, "with --alignments the records are what they are: the file holds alignments, not reads to prepare"),
-                        (a.contigs, "--contigs cuts assemblies into windows, and a window is cut from the sequence as it stands"),
-                        (a.long_reads, "--long-reads cuts reads into windows, and a window is cut from the record as it stands"),
-                        (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and a window is cut from the record as it stands"),
-                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp),
-                         "a reads BAM stores raw Phred and its own strand, and its reads are not prepared: FASTQ input only")):
-            if on:
-                print("read preparation (--trim5, --trim3, --trim-qual, --phred64): " + why)
-                return 1
+        if _refused("read preparation (--trim5, --trim3, --trim-qual, --phred64): ", (
+                (a.alignments, "with --alignments the records are what they are: the file holds alignments, not reads to prepare"),
+                (a.contigs, "--contigs cuts assemblies into windows, and a window is cut from the sequence as it stands"),
+                (a.long_reads, "--long-reads cuts reads into windows, and a window is cut from the record as it stands"),
+                (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and a window is cut from the record as it stands"),
+                (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp),
+                 "a reads BAM stores raw Phred and its own strand, and its reads are not prepared: FASTQ input only"))):
+            return 1
     adapters = _adapters_of(a)
     if adapters is not None:      # (refused before any GPU use, each with its reason)
         if adapters is False:
             return 1
-        for on, why in ((a.alignments, "with --alignments the records are what they are: the file holds alignments, not reads to cut"),
-                        (a.contigs, "--contigs cuts assemblies into windows, and an assembly carries no adapter"),
-                        (a.long_reads, "--long-reads cuts reads into windows, and a window is cut from the record as it stands"),
-                        (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and a window is cut from the record as it stands"),
-                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp),
-                         "the reads of a BAM are taken as they are stored: FASTQ input only")):
-            if on:
-                print("--adapter: " + why)
-                return 1
+        if _refused("--adapter: ", (
+                (a.alignments, "with --alignments the records are what they are: the file holds alignments, not reads to cut"),
+                (a.contigs, "--contigs cuts assemblies into windows, and an assembly carries no adapter"),
+                (a.long_reads, "--long-reads cuts reads into windows, and a window is cut from the record as it stands"),
+                (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and a window is cut from the record as it stands"),
+                (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp),
+                 "the reads of a BAM are taken as they are stored: FASTQ input only"))):
+            return 1
     if getattr(a, "read_stats", False):      # (refused before any GPU use, each with its reason)
-        for on, why in ((a.alignments, "with --alignments the file holds alignments, not the reads of a FASTQ file"),
-                        (a.contigs, "--contigs cuts assemblies into windows, and an assembly has neither cycles nor qualities"),
-                        (a.long_reads, "--long-reads cuts reads into windows, and the tables hold the 320 cycles of a short read"),
-                        (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and the tables hold the 320 cycles of a short read"),
-                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the reads of a BAM are not counted: FASTQ input only"),
-                        (many, "it reports one sample: several samples or a folder are typed without it"),
-                        (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "the tables are one GPU's: a rank of --gpus N counts its own share of the reads only")):
-            if on:
-                print("--read-stats: " + why)
-                return 1
+        if _refused("--read-stats: ", (
+                (a.alignments, "with --alignments the file holds alignments, not the reads of a FASTQ file"),
+                (a.contigs, "--contigs cuts assemblies into windows, and an assembly has neither cycles nor qualities"),
+                (a.long_reads, "--long-reads cuts reads into windows, and the tables hold the 320 cycles of a short read"),
+                (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and the tables hold the 320 cycles of a short read"),
+                (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the reads of a BAM are not counted: FASTQ input only"),
+                (many, "it reports one sample: several samples or a folder are typed without it"),
+                (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "the tables are one GPU's: a rank of --gpus N counts its own share of the reads only"))):
+            return 1
     if getattr(a, "dedup", False):      # (refused before any GPU use, each with its reason)
-        for on, why in ((a.alignments, "with --alignments the file holds alignments, not reads to compare (duplicate alignments are samtools markdup's)"),
-                        (a.contigs, "--contigs cuts assemblies into windows, and the windows of an assembly are not copies of a molecule"),
-                        (a.long_reads, "--long-reads cuts reads into windows, and the windows of a read would be compared, not the read"),
-                        (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and the windows of a read would be compared, not the read"),
-                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the reads of a BAM are not compared: FASTQ input only"),
-                        (many, "one table of keys per engine: several samples or a folder are typed without it (per-sample tables through the pipelined loop are the follow-up)"),
-                        (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "a rank of --gpus N sees only its byte range, and duplicates across ranks would be missed")):
-            if on:
-                print("duplicate removal (--dedup): " + why)
-                return 1
+        if _refused("duplicate removal (--dedup): ", (
+                (a.alignments, "with --alignments the file holds alignments, not reads to compare (duplicate alignments are samtools markdup's)"),
+                (a.contigs, "--contigs cuts assemblies into windows, and the windows of an assembly are not copies of a molecule"),
+                (a.long_reads, "--long-reads cuts reads into windows, and the windows of a read would be compared, not the read"),
+                (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and the windows of a read would be compared, not the read"),
+                (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the reads of a BAM are not compared: FASTQ input only"),
+                (many, "one table of keys per engine: several samples or a folder are typed without it (per-sample tables through the pipelined loop are the follow-up)"),
+                (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "a rank of --gpus N sees only its byte range, and duplicates across ranks would be missed"))):
+            return 1
     pair_overlap = _pair_overlap_of(a)
     if pair_overlap is not None:      # (refused before any GPU use, each with its reason)
         if pair_overlap is False:
             return 1
-        for on, why in ((a.alignments, "with --alignments the file holds alignments, not mates to lay on each other"),
-                        (a.contigs, "--contigs cuts assemblies into windows, and a window has no mate"),
-                        (a.long_reads, "--long-reads cuts unpaired reads into windows, and a window has no mate"),
-                        (a.long_bam_reads, "--long-bam-reads cuts unpaired reads into windows, and a window has no mate"),
-                        (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the mates of a BAM are taken as they are stored: FASTQ input with -2 only"),
-                        (many, "several samples or a folder are typed without it (the rule is per pair: summing the counters of the samples is the follow-up)"),
-                        (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "one GPU: the counters of the ranks of --gpus N are not summed yet (the follow-up)"),
-                        (not a.mates, "it lays the mates of a pair on each other: give the second file with -2"),
-                        (bool(a.mates) and len(samples[0]) > 1, "it takes one file of first mates and one of second mates (-2), not `a.fq,b.fq`")):
-            if on:
-                print("--pair-overlap: " + why)
-                return 1
+        if _refused("--pair-overlap: ", (
+                (a.alignments, "with --alignments the file holds alignments, not mates to lay on each other"),
+                (a.contigs, "--contigs cuts assemblies into windows, and a window has no mate"),
+                (a.long_reads, "--long-reads cuts unpaired reads into windows, and a window has no mate"),
+                (a.long_bam_reads, "--long-bam-reads cuts unpaired reads into windows, and a window has no mate"),
+                (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp), "the mates of a BAM are taken as they are stored: FASTQ input with -2 only"),
+                (many, "several samples or a folder are typed without it (the rule is per pair: summing the counters of the samples is the follow-up)"),
+                (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1, "one GPU: the counters of the ranks of --gpus N are not summed yet (the follow-up)"),
+                (not a.mates, "it lays the mates of a pair on each other: give the second file with -2"),
+                (bool(a.mates) and len(samples[0]) > 1, "it takes one file of first mates and one of second mates (-2), not `a.fq,b.fq`"))):
+            return 1
         try:
             if not mates_share_names(samples[0][0], a.mates):
                 print("--pair-overlap: the records of %s and %s do not share their names, so the files go in as two unpaired texts and no read has a mate" % (samples[0][0], a.mates))
@@ -451,16 +445,7 @@ def run_type(a, argv=None) -> int:
         eng.set_read_tiling(*(long_reads or long_bam))
     if a.read_names:      # (FASTQ input only: text, host-inflated .gz and BGZF all reach the device as text, where the names are kept)
         eng.set_read_names(True)
-    if read_prep:      # (the same entries: the reads are prepared where the text is parsed; before a rank's first read index base)
-        eng.set_read_prep(**read_prep)
-    if adapters:       # (likewise)
-        eng.set_read_adapters(**adapters)
-    if getattr(a, "read_stats", False):      # (likewise: counted where the text is parsed)
-        eng.set_read_stats(True)
-    if getattr(a, "dedup", False):      # (likewise: compared where the text is parsed, behind the preparation)
-        eng.set_read_dedup(True)
-    if pair_overlap:      # (likewise: the mates are laid on each other where the text is parsed, behind the cut)
-        eng.set_read_pair_overlap(True, **pair_overlap)
+    _apply_read_chain(eng, a, read_prep, adapters, pair_overlap)      # (the same entries; before a rank's first read index base)
     # the built host index is kept next to the database (as the reference keeps <idx>.1.bt2: metamlst-index.py:224-225) unless a
     # species filter made this index a one-off or MLST_INDEX_CACHE=0
     ref_cache = (a.database + ".mlstref") if (not a.filter and os.environ.get("MLST_INDEX_CACHE", "1") != "0") else ""
@@ -482,10 +467,7 @@ def run_type(a, argv=None) -> int:
             e2.set_bgzf_verify(a.verify_crc)
             if long_reads or long_bam:
                 e2.set_read_tiling(*(long_reads or long_bam))
-            if read_prep:
-                e2.set_read_prep(**read_prep)
-            if adapters:
-                e2.set_read_adapters(**adapters)
+            _apply_read_chain(e2, a, read_prep, adapters, pair_overlap)      # (the switches refused for several samples are off)
             if a.depth_cap:
                 e2.set_depth_cap(a.depth_cap)
             engines.append(e2)
@@ -623,6 +605,30 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
         if not a.quiet:
             print("--write-reads: %d reads with an alignment written" % n_written)
     return rc
+
+
+def _refused(prefix: str, rows) -> bool:
+    """says the first reason of rows ((holds, sentence), ...) that holds, behind prefix"""
+    for on, why in rows:
+        if on:
+            print(prefix + why)
+            return True
+    return False
+
+
+def _apply_read_chain(eng, a, read_prep, adapters, pair_overlap) -> None:
+    """The switches of the read chain as the command was given them: the reads are prepared, cut, counted and compared
+    where the FASTQ text is parsed"""
+    if read_prep:
+        eng.set_read_prep(**read_prep)
+    if adapters:
+        eng.set_read_adapters(**adapters)
+    if getattr(a, "read_stats", False):
+        eng.set_read_stats(True)
+    if getattr(a, "dedup", False):
+        eng.set_read_dedup(True)
+    if pair_overlap:
+        eng.set_read_pair_overlap(True, **pair_overlap)
 
 
 def _read_prep_of(a):

@@ -3883,12 +3883,8 @@ static void bz_free(mlst_handle* h);
 static int bam_flush(mlst_handle* h);     // BAM input: the piece in flight is finished (its errors are this call's)
 static void bam_drop(mlst_handle* h, bool release);      // the BAM stream is closed and forgotten (release: its buffers too)
 static bool bam_is_open(const mlst_handle* h);
-static int rn_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_names is on: an entry that carries no names is refused
-static int rp_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_prep is on: an entry that does not prepare its reads is refused
-static int ra_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_adapters is on: an entry that does not cut its reads is refused
-static int rs_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_stats is on: an entry whose reads are not counted is refused
-static int dd_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_dedup is on: an entry whose reads are not compared is refused
-static int po_refuse(mlst_handle* h, const char* entry);      // mlst_set_read_pair_overlap is on: an entry that does not hand over pairs of FASTQ text is refused
+static int chain_reset(mlst_handle* h);      // the read chain (csrc/read_chain.h, included behind grid_for): a new sample
+static void chain_free(mlst_handle* h);      // ... and the end of the handle
 static void at_free(mlst_handle* h);      // the per-export tables of mlst_alignments_text_*
 static const char* bam_kind(const mlst_handle* h);      // "BAM" or "SAM": what the open stream of ready-made alignments takes
 template <typename T> static hipError_t dmalloc(T** p, u64 n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
@@ -4059,8 +4055,7 @@ extern "C" void mlst_destroy(mlst_handle* h) {
     if (h->copy_stream) hipStreamDestroy(h->copy_stream);
     hipFree(h->d_cand); hipFree(h->d_in_bases); hipFree(h->d_in_quals); hipFree(h->d_in_off);
     hipFree(h->d_fq_slot[0]); hipFree(h->d_fq_slot[1]); hipFree(h->d_fq_nl[0]); hipFree(h->d_fq_nl[1]); hipFree(h->d_fq_blk); hipFree(h->d_fq_lines); hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); hipFree(h->d_fq_meta);
-    hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta); hipFree(h->rp.d_ctr); hipFree(h->ra.d_ctr); hipFree(h->rs.d_tab); hipFree(h->po.d_ctr);
-    hipFree(h->dd.d_mem); hipFree(h->dd.d_ctr); hipFree(h->dd.d_slot_of); hipFree(h->dd.d_key2);
+    hipFree(h->d_pc[0]); hipFree(h->d_pc[1]); hipFree(h->d_pr_meta); chain_free(h);
     hipFree(h->fa.d_desc); hipFree(h->fa.d_meta); hipFree(h->fa.d_flat); hipFree(h->fa.d_kind); hipFree(h->fa.d_cseq); hipFree(h->fa.d_chdr); hipFree(h->fa.d_cstart); hipFree(h->fa.d_wcnt);
     if (h->fa.h_fa) hipHostFree(h->fa.h_fa);
     hipFree(h->tile.d_desc); hipFree(h->tile.d_meta); hipFree(h->tile.d_rlen); hipFree(h->tile.d_wex); hipFree(h->tile.d_gsum); hipFree(h->tile.d_soff); hipFree(h->tile.d_qoff);
@@ -4092,16 +4087,7 @@ static int reset_sample_state(mlst_handle* h) {
     HIPCHK(h, hipMemsetAsync(h->d_stats, 0, h->stats_zero_bytes, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_stats + h->off_first, 0xFF, h->stats_bytes - h->off_first, h->stream));
     if (h->d_acc64 && h->n_alleles) HIPCHK(h, hipMemsetAsync(h->d_acc64, 0, (u64)h->n_alleles * 8, h->stream));      // (zero after every complete submission already: k_accumulate; this is for one that was cut short)
-    if (h->rn.d_ctr) HIPCHK(h, hipMemsetAsync(h->rn.d_ctr, 0, sizeof(RnCtr), h->stream));      // the name arena is empty; the switch stays
-    if (h->rp.d_ctr) HIPCHK(h, hipMemsetAsync(h->rp.d_ctr, 0, sizeof(RpCtr), h->stream));      // mlst_set_read_prep: the counters are the sample's; the setting stays
-    if (h->ra.d_ctr) HIPCHK(h, hipMemsetAsync(h->ra.d_ctr, 0, sizeof(RaCtr), h->stream));      // mlst_set_read_adapters: likewise
-    if (h->rs.d_tab) HIPCHK(h, hipMemsetAsync(h->rs.d_tab, 0, 4ull * RS_WORDS * 8, h->stream));      // mlst_set_read_stats: the tables are the sample's; the switch stays, the side is 0 again
-    h->rs.side = 0; h->rs.launches[0] = h->rs.launches[1] = 0;
-    if (h->dd.d_mem) { int rc = dd_clear(h, h->dd.tab); if (rc) return rc; }      // mlst_set_read_dedup: the keys are the sample's; the switch and the table's size stay
-    if (h->dd.d_ctr) HIPCHK(h, hipMemsetAsync(h->dd.d_ctr, 0, sizeof(DdCtr), h->stream));
-    if (h->po.d_ctr) HIPCHK(h, hipMemsetAsync(h->po.d_ctr, 0, sizeof(PoCtr), h->stream));      // mlst_set_read_pair_overlap: the counters are the sample's; the switch and its setting stay
-    h->po.pairs = 0;
-    h->dd.units_seen = h->dd.reads = 0;
+    { int rc = chain_reset(h); if (rc) return rc; }
     h->reads_seen = 0; h->fq_carry_len = 0; h->max_wpr = 0;
     h->last_pack.n_reads = 0; h->last_pack.wpr = h->last_pack.qstride = 0;
     for (u64& x : h->tile.info) x = 0;
@@ -4640,6 +4626,7 @@ extern "C" int mlst_reset_sample(mlst_handle* h) {
 static int grid_for(u64 n_units, int per_block, int cap = 2048) {
     u64 g = (n_units + per_block - 1) / per_block; if (g < 1) g = 1; if (g > (u64)cap) g = cap; return (int)g;
 }
+#include "read_chain.h"      // the read-preparation stages of the FASTQ path strung together: host code only
 static void zero_words(mlst_handle* h, void* p, u64 n_words) {
     if (!n_words) return;
     hipLaunchKernelGGL(k_zero, dim3(grid_for((n_words + 255) / 256, 1, 1024)), dim3(256), 0, h->stream, (u32*)p, n_words);
@@ -4714,12 +4701,7 @@ static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* 
                        uint64_t n_reads, uint32_t wpr, uint32_t qstride, int paired, int phase);
 extern "C" int mlst_submit_packed_device(mlst_handle* h, const uint32_t* d_packed, const uint8_t* d_qrows, const uint16_t* d_lens,
                                          uint64_t n_reads, uint32_t wpr, uint32_t qstride, int paired) {
-    { int rc_ = rn_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
-    { int rc_ = rp_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
-    { int rc_ = ra_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
-    { int rc_ = rs_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
-    { int rc_ = dd_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
-    { int rc_ = po_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
+    { int rc_ = chain_refuse(h, "mlst_submit_packed_device"); if (rc_) return rc_; }
     return submit_impl(h, d_packed, d_qrows, d_lens, n_reads, wpr, qstride, paired, 0);
 }
 static int submit_impl(mlst_handle* h, const uint32_t* d_packed, const uint8_t* d_qrows, const uint16_t* d_lens,
@@ -4866,12 +4848,7 @@ static int h2d_overlapped(mlst_handle* h, void* d_dst, const void* src, u64 n, h
 extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, const uint8_t* d_quals, const uint64_t* d_off,
                                         uint64_t n_reads, uint32_t max_len, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
-    { int rc_ = rn_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
-    { int rc_ = rp_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
-    { int rc_ = ra_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
-    { int rc_ = rs_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
-    { int rc_ = dd_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
-    { int rc_ = po_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
+    { int rc_ = chain_refuse(h, "mlst_submit_reads_device"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     hipSetDevice(h->device);
@@ -4887,12 +4864,7 @@ extern "C" int mlst_submit_reads_device(mlst_handle* h, const uint8_t* d_bases, 
 extern "C" int mlst_submit_reads(mlst_handle* h, const uint8_t* bases, const uint8_t* quals, const uint64_t* off,
                                  uint64_t n_reads, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
-    { int rc_ = rn_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
-    { int rc_ = rp_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
-    { int rc_ = ra_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
-    { int rc_ = rs_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
-    { int rc_ = dd_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
-    { int rc_ = po_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
+    { int rc_ = chain_refuse(h, "mlst_submit_reads"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (n_reads == 0) return MLST_OK;
@@ -4930,193 +4902,18 @@ static int next_text_slot(mlst_handle* h, u64 bytes) {
 }
 
 static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, int paired, uint64_t* n_reads_out);
-// mlst_set_read_names: the name arena, allocated by the first submission under the switch (csrc/read_names.h)
-static int rn_ensure(mlst_handle* h) {
-    auto& N = h->rn;
-    if (N.d_ctr) return MLST_OK;
-    HIPCHK(h, dmalloc(&N.d_ctr, (u64)1)); HIPCHK(h, dmalloc(&N.d_bytes, N.want_bytes)); N.cap_bytes = N.want_bytes;
-    HIPCHK(h, dmalloc(&N.d_off, h->E.cap_ret)); HIPCHK(h, dmalloc(&N.d_len, h->E.cap_ret));
-    HIPCHK(h, hipMemsetAsync(N.d_ctr, 0, sizeof(RnCtr), h->stream));
+// the tail the text parsers share (fastq_pipeline, bzp_finish_impl): sequence and quality offsets for n_reads reads, grown as needed
+static int ensure_fq_reads(mlst_handle* h, u64 n_reads) {
+    if (h->cap_fq_reads >= n_reads) return MLST_OK;
+    hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); h->d_fq_soff = h->d_fq_qoff = nullptr; h->cap_fq_reads = 0;
+    HIPCHK(h, dmalloc(&h->d_fq_soff, n_reads)); HIPCHK(h, dmalloc(&h->d_fq_qoff, n_reads)); h->cap_fq_reads = n_reads;
     return MLST_OK;
 }
-// with the switch on, reads come from FASTQ text only: every other way of adding reads is refused
-static int rn_refuse(mlst_handle* h, const char* entry) {
-    if (h && h->rn.on) return fail(h, MLST_E_INVALID, "%s: read names are on (mlst_set_read_names) and only the FASTQ text and BGZF entries carry names", entry);
-    return MLST_OK;
-}
-// mlst_set_read_prep (csrc/read_prep.h): with the switch on, reads come from FASTQ text only, where they are prepared
-static int rp_refuse(mlst_handle* h, const char* entry) {
-    if (h && h->rp.on) return fail(h, MLST_E_INVALID, "%s: read preparation is on (mlst_set_read_prep) and only the FASTQ text and BGZF entries apply it", entry);
-    return MLST_OK;
-}
-// mlst_set_read_adapters (csrc/read_adapt.h): likewise
-static int ra_refuse(mlst_handle* h, const char* entry) {
-    if (h && h->ra.on) return fail(h, MLST_E_INVALID, "%s: adapter removal is on (mlst_set_read_adapters) and only the FASTQ text and BGZF entries apply it", entry);
-    return MLST_OK;
-}
-// mlst_set_read_stats (csrc/read_stats.h): with the switch on, reads come from FASTQ text only, where they are counted
-static int rs_refuse(mlst_handle* h, const char* entry) {
-    if (h && h->rs.on) return fail(h, MLST_E_INVALID, "%s: read statistics are on (mlst_set_read_stats) and only the FASTQ text and BGZF entries count their reads", entry);
-    return MLST_OK;
-}
-// mlst_set_read_dedup (csrc/read_dedup.h): with the switch on, reads come from FASTQ text only, where they are compared
-static int dd_refuse(mlst_handle* h, const char* entry) {
-    if (h && h->dd.on) return fail(h, MLST_E_INVALID, "%s: duplicate removal is on (mlst_set_read_dedup) and only the FASTQ text and BGZF entries apply it", entry);
-    return MLST_OK;
-}
-// mlst_set_read_pair_overlap (csrc/read_overlap.h): with the switch on, reads come as pairs of FASTQ text only, where the mates are laid on each other
-static int po_refuse(mlst_handle* h, const char* entry) {
-    if (h && h->po.on) return fail(h, MLST_E_INVALID, "%s: mate overlap trimming is on (mlst_set_read_pair_overlap) and only the paired FASTQ text and BGZF entries apply it", entry);
-    return MLST_OK;
-}
-// one launch of k_rs_count over the chunk's reads as offsets and lengths stand now: stage 0 in front of k_rp_qtrim (which rewrites the
-// offsets in place), stage 1 behind k_ra_cut.  At most one workgroup per CU, fewer for few reads (each flushes its LDS tables once); a
-// paired chunk takes an even number, a workgroup counting one side
-static int rs_launch(mlst_handle* h, u64 n_reads, u32* d_flags, int paired, int stage) {
-    auto& S = h->rs;
-    if (!S.d_tab) { HIPCHK(h, dmalloc(&S.d_tab, 4ull * RS_WORDS)); HIPCHK(h, hipMemsetAsync(S.d_tab, 0, 4ull * RS_WORDS * 8, h->stream)); }
-    if (!S.n_cu) { HIPCHK(h, hipDeviceGetAttribute(&S.n_cu, hipDeviceAttributeMultiprocessorCount, h->device)); if (S.n_cu < 2) S.n_cu = 2; }
-    u64 want = (n_reads + RS_WG_READS - 1) / RS_WG_READS; if (want < 1) want = 1;
-    u32 grid = (u32)std::min<u64>(want, (u64)S.n_cu);
-    if (paired) { grid = (grid + 1) & ~1u; if (grid > (u32)S.n_cu) grid -= 2; if (grid < 2) grid = 2; }
-    u64* const tab = S.d_tab + (u64)stage * 2 * RS_WORDS;
-    Prof pf(h, 20);      // (mlst_get_kernel_time 20: k_rs_count alone)
-    if (h->rp.set.phred_base == 64) hipLaunchKernelGGL(k_rs_count<64>, dim3(grid), dim3(1024), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, (const u64*)h->d_fq_qoff,
-                                                       (const u16*)h->d_lens, n_reads, paired ? 1u : 0u, S.side, stage == 0 ? 1u : 0u, (const u32*)d_flags, tab);
-    else hipLaunchKernelGGL(k_rs_count<33>, dim3(grid), dim3(1024), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, (const u64*)h->d_fq_qoff,
-                            (const u16*)h->d_lens, n_reads, paired ? 1u : 0u, S.side, stage == 0 ? 1u : 0u, (const u32*)d_flags, tab);
-    S.launches[stage]++;
-    return MLST_OK;
-}
-// the parser has left offsets and lengths of n_reads reads of h->d_fq_text and the longest length in flags[0]: the trims, queued in
-// front of the read-back of the flags, so that the longest length the host reads is the longest prepared one (no synchronisation added)
-// Behind them, mlst_set_read_adapters' cut (csrc/read_adapt.h): flags[0] is zeroed in front of either kernel, so the last one alone feeds what is read
-// mlst_set_read_stats: the raw tables are counted in front of the trims, the prepared ones behind the cut, only when either ran
-// mlst_set_read_dedup: the table, the counters and the per-unit scratch in front of a chunk of n_units units.  The table holds at least
-// two slots per unit submitted so far and in this chunk -- the host knows both numbers without a read-back; one that is too small is
-// replaced by the next power of two that is not, and k_dd_rehash moves the keys
-static int dd_ensure(mlst_handle* h, u64 n_units) {
-    auto& D = h->dd;
-    if (!D.d_ctr) { HIPCHK(h, dmalloc(&D.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(D.d_ctr, 0, sizeof(DdCtr), h->stream)); }
-    if (D.cap_units < n_units) {
-        hipFree(D.d_slot_of); hipFree(D.d_key2); D.d_slot_of = nullptr; D.d_key2 = nullptr; D.cap_units = 0;
-        HIPCHK(h, dmalloc(&D.d_slot_of, n_units)); HIPCHK(h, dmalloc(&D.d_key2, n_units)); D.cap_units = n_units;
-    }
-    u64 slots = D.tab.slots, tag_mask = D.tab.tag_mask;
-    if (!slots) {      // the first table: the two environment switches are read here
-        slots = 1ull << 22; tag_mask = ~0ull;
-        if (const char* e = getenv("MLST_DEDUP_SLOTS")) {
-            const long long v = atoll(e);
-            if (v < 64 || v > (1ll << 31) || (v & (v - 1))) return fail(h, MLST_E_INVALID, "MLST_DEDUP_SLOTS is %s: a power of two from 64 to 2^31 is taken", e);
-            slots = (u64)v;
-        }
-        if (const char* e = getenv("MLST_DEDUP_TAG_BITS")) {
-            const int v = atoi(e);
-            if (v < 0 || v > 64 || !(e[0] >= '0' && e[0] <= '9')) return fail(h, MLST_E_INVALID, "MLST_DEDUP_TAG_BITS is %s: 0 to 64 is taken", e);
-            tag_mask = v >= 64 ? ~0ull : (1ull << v) - 1;
-        }
-    }
-    const u64 need = 2 * (D.units_seen + n_units);
-    while (slots < need && slots < (1ull << 31)) slots <<= 1;
-    if (slots < need) return fail(h, MLST_E_LIMIT, "mlst_set_read_dedup: %llu units need more than 2^31 slots", (unsigned long long)(D.units_seen + n_units));
-    if (slots == D.tab.slots) return MLST_OK;
-    u8* mem = nullptr;
-    if (dmalloc(&mem, slots * 28) != hipSuccess) { (void)hipGetLastError(); return fail(h, MLST_E_LIMIT, "mlst_set_read_dedup: the table of %llu slots needs %llu bytes of device memory", (unsigned long long)slots, (unsigned long long)(slots * 28)); }
-    const DdTab T = {reinterpret_cast<u64*>(mem), reinterpret_cast<u64*>(mem + slots * 8), reinterpret_cast<u64*>(mem + slots * 16), reinterpret_cast<u32*>(mem + slots * 24), slots, tag_mask};
-    int rc = dd_clear(h, T);
-    if (!rc && D.d_mem) {
-        hipLaunchKernelGGL(k_dd_rehash, dim3(grid_for(D.tab.slots, 256)), dim3(256), 0, h->stream, D.tab, T, D.d_ctr);
-        const hipError_t e = hipStreamSynchronize(h->stream);      // (the old table is freed behind its last reader)
-        if (e != hipSuccess) rc = fail(h, MLST_E_HIP, "k_dd_rehash: %s", hipGetErrorString(e));
-    }
-    if (rc) { hipFree(mem); return rc; }
-    hipFree(D.d_mem); D.d_mem = mem; D.tab = T;
-    return MLST_OK;
-}
-// the three launches of mlst_set_read_dedup over a chunk's reads as their lengths stand now, behind the trims, the cut and the prepared
-// read statistics, in front of the read-back of the parser's flags.  flags[0] is zeroed once more: k_dd_mark alone feeds the longest
-// length the host reads.  Chunks are queued on h->stream one behind the other (each ends in a read-back), so the launches of
-// consecutive chunks run in read-index order -- for the pipelined BGZF entries too, whose other two streams only copy and inflate
-static int dd_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
-    auto& D = h->dd;
-    const u64 n_units = paired ? n_reads / 2 : n_reads;
-    if (paired && (n_reads & 1)) return fail(h, MLST_E_INVALID, "mlst_set_read_dedup: a paired chunk holds %llu records: the mates of a pair are compared within one chunk", (unsigned long long)n_reads);
-    if (!n_units) return MLST_OK;
-    int rc = dd_ensure(h, n_units); if (rc) return rc;
-    HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
-    {
-        Prof pf(h, 21);      // (mlst_get_kernel_time 21: k_dd_insert, k_dd_sign and k_dd_mark together)
-        const dim3 grid(grid_for(n_units, 256)), block(256);
-        hipLaunchKernelGGL(k_dd_insert, grid, block, 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, (const u16*)h->d_lens, n_units, paired ? 1u : 0u,
-                           D.units_seen, D.tab, D.d_slot_of, D.d_key2, (const u32*)d_flags, D.d_ctr);
-        hipLaunchKernelGGL(k_dd_sign, grid, block, 0, h->stream, n_units, D.units_seen, D.tab, (const u32*)D.d_slot_of, (const u64*)D.d_key2, (const u32*)d_flags, D.d_ctr);
-        hipLaunchKernelGGL(k_dd_mark, grid, block, 0, h->stream, h->d_lens, n_units, paired ? 1u : 0u, D.units_seen, D.tab, (const u32*)D.d_slot_of, (const u64*)D.d_key2,
-                           d_flags, D.d_ctr);
-    }
-    HIPCHK(h, hipGetLastError());
-    D.units_seen += n_units; D.reads += n_reads;
-    return MLST_OK;
-}
-// mlst_set_read_pair_overlap's launch over a chunk's pairs as their lengths stand now, behind the trims and the adapter cut, in front of the
-// prepared read statistics and the duplicate removal.  flags[0] is zeroed once more: k_po_cut alone feeds the longest length it leaves.
-// At most three workgroups of eight waves per CU (what its registers let a CU hold; each flushes its histogram in LDS once), fewer for few pairs
-static int po_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
-    auto& O = h->po;
-    if (!paired) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: an unpaired FASTQ submission: mate overlap trimming is on and takes pairs (the paired entries; `-2` with mates that share their names)");
-    if (n_reads & 1) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: a paired chunk holds %llu records: the mates of a pair are laid on each other within one chunk", (unsigned long long)n_reads);
-    const u64 n_pairs = n_reads / 2;
-    if (!n_pairs) return MLST_OK;
-    if (!O.d_ctr) { HIPCHK(h, dmalloc(&O.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(O.d_ctr, 0, sizeof(PoCtr), h->stream)); }
-    if (!O.n_cu) { HIPCHK(h, hipDeviceGetAttribute(&O.n_cu, hipDeviceAttributeMultiprocessorCount, h->device)); if (O.n_cu < 1) O.n_cu = 1; }
-    PoSet S = O.set;
-    S.trim5 = h->rp.on ? h->rp.set.trim5 : 0u;
-    HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
-    {
-        Prof pf(h, 22);      // (mlst_get_kernel_time 22: k_po_cut alone)
-        const u32 grid = (u32)std::min<u64>((n_pairs + PO_WAVES - 1) / PO_WAVES, 3ull * (u64)O.n_cu);
-        hipLaunchKernelGGL(k_po_cut, dim3(grid), dim3(64 * PO_WAVES), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, h->d_lens, n_pairs, S, d_flags, O.d_ctr);
-    }
-    HIPCHK(h, hipGetLastError());
-    O.pairs += n_pairs;
-    return MLST_OK;
-}
-static int rp_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
-    const RpSet& P = h->rp.set;
-    const bool trims = h->rp.on && (P.trim5 | P.trim3 | P.trim_qual);      // (the Phred base alone is k_pack_text's)
-    if (h->rs.on) { int rc = rs_launch(h, n_reads, d_flags, paired, 0); if (rc) return rc; }
-    if (h->po.on && !trims && !h->ra.on) {      // mlst_set_read_pair_overlap alone: the prepared tables are counted behind it all the same
-        int rc = po_apply(h, n_reads, d_flags, paired); if (rc) return rc;
-        if (h->rs.on) { rc = rs_launch(h, n_reads, d_flags, paired, 1); if (rc) return rc; }
-        return h->dd.on ? dd_apply(h, n_reads, d_flags, paired) : MLST_OK;
-    }
-    if (!trims && !h->ra.on) return h->dd.on ? dd_apply(h, n_reads, d_flags, paired) : MLST_OK;      // (mlst_set_read_dedup alone still runs)
-    if (trims && !h->rp.d_ctr) { HIPCHK(h, dmalloc(&h->rp.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->rp.d_ctr, 0, sizeof(RpCtr), h->stream)); }
-    if (h->ra.on && !h->ra.d_ctr) { HIPCHK(h, dmalloc(&h->ra.d_ctr, (u64)1)); HIPCHK(h, hipMemsetAsync(h->ra.d_ctr, 0, sizeof(RaCtr), h->stream)); }
-    HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
-    if (trims) {
-        Prof pf(h, 18);      // (mlst_get_kernel_time 18: k_rp_qtrim alone)
-        hipLaunchKernelGGL(k_rp_qtrim, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, h->d_fq_soff, h->d_fq_qoff, h->d_lens, n_reads, P,
-                           d_flags, h->rp.d_ctr);
-    }
-    // k_rp_qtrim has fed the longest PREPARED length, and an atomicMax with the shorter cut lengths would leave it standing: zeroed again,
-    // so that the longest length the host reads is that of the prepared, cut text
-    if (trims && h->ra.on) HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
-    if (h->ra.on) {
-        Prof pf(h, 19);      // (mlst_get_kernel_time 19: k_ra_cut alone)
-        hipLaunchKernelGGL(k_ra_cut, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, h->d_lens, n_reads, h->ra.set,
-                           d_flags, h->ra.d_ctr);
-    }
-    if (h->po.on) { int rc = po_apply(h, n_reads, d_flags, paired); if (rc) return rc; }      // mlst_set_read_pair_overlap: behind the cut, in front of the prepared tables
-    if (h->rs.on) { int rc = rs_launch(h, n_reads, d_flags, paired, 1); if (rc) return rc; }
-    return h->dd.on ? dd_apply(h, n_reads, d_flags, paired) : MLST_OK;      // mlst_set_read_dedup: behind the prepared tables, which stay what they are
-}
-// the counters of the name arena; an arena that was too small is reported here (the next entry that looks)
-static int rn_fetch(mlst_handle* h, RnCtr* c) {
-    memset(c, 0, sizeof *c);
-    if (!h->rn.d_ctr) return MLST_OK;
-    HIPCHK(h, hipMemcpyAsync(c, h->rn.d_ctr, sizeof *c, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (c->err) return fail(h, MLST_E_LIMIT, "the read names need %llu bytes and the arena holds %llu: raise MLST_NAMES_BYTES", (unsigned long long)c->bytes, (unsigned long long)h->rn.cap_bytes);
+// ... and what the record kernels and the read chain left in flags[1]
+static int fq_flags_fail(mlst_handle* h, const u32 flags[2]) {
+    if (flags[1] & 8) return fail(h, MLST_E_HIP, "mlst_set_read_dedup: a probe ran through the whole table");      // (k_dd_mark hands DdCtr::err on)
+    if (flags[1] & 2) return fail(h, MLST_E_LIMIT, "a FASTQ read is longer than %d bases", MLST_MAX_READ_LEN);
+    if (flags[1] & 1) return fail(h, MLST_E_INVALID, "malformed FASTQ: a record does not start with '@' or its sequence and quality lengths differ");
     return MLST_OK;
 }
 static int fq_tile_submit(mlst_handle* h, u64 n_bytes, u64 n_lines, u64 n_recs, int tslot, uint64_t* n_reads_out);
@@ -5174,17 +4971,16 @@ static int fastq_pipeline(mlst_handle* h, u64 n_bytes, int paired, bool whole, u
         if (second != pair_boundary) return fail(h, MLST_E_INVALID, "mate files hold different numbers of records (record %llu starts at byte %llu, the second file at %llu)",
                                                  (unsigned long long)pair_k, (unsigned long long)second, (unsigned long long)pair_boundary);
     }
-    if (h->cap_fq_reads < n_reads) { hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); h->d_fq_soff = h->d_fq_qoff = nullptr;
-                                     HIPCHK(h, dmalloc(&h->d_fq_soff, n_reads)); HIPCHK(h, dmalloc(&h->d_fq_qoff, n_reads)); h->cap_fq_reads = n_reads; }
+    int rc = ensure_fq_reads(h, n_reads); if (rc) return rc;
     // lengths are needed before the packed buffers can be sized: worst-case row width first, then the real one
-    int rc = ensure_pack_buffers(h, n_reads, 2, 8); if (rc) return rc;
+    rc = ensure_pack_buffers(h, n_reads, 2, 8); if (rc) return rc;
     u32* d_flags = reinterpret_cast<u32*>(h->d_fq_meta + 1);
     const bool tile = h->tile.read_len && !paired && !pair_boundary;      // mlst_set_read_tiling: unpaired text only
     if (tile) hipLaunchKernelGGL(k_fq_records<true>, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, h->d_fq_text, (u64)n_bytes, h->d_fq_lines, n_lines, n_reads,
                                  h->d_fq_soff, h->d_fq_qoff, h->d_lens, d_flags, pair_k, h->tile.read_len);
     else hipLaunchKernelGGL(k_fq_records<false>, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, h->d_fq_text, (u64)n_bytes, h->d_fq_lines, n_lines, n_reads,
                             h->d_fq_soff, h->d_fq_qoff, h->d_lens, d_flags, pair_k, 0u);
-    rc = rp_apply(h, n_reads, d_flags, paired || pair_boundary); if (rc) return rc;      // mlst_set_read_prep (never with a tile)
+    rc = chain_apply(h, n_reads, d_flags, paired || pair_boundary); if (rc) return rc;      // the read chain (never with a tile)
     u32 flags[2] = {0, 0};
     HIPCHK(h, hipMemcpyAsync(flags, d_flags, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -5193,9 +4989,7 @@ static int fastq_pipeline(mlst_handle* h, u64 n_bytes, int paired, bool whole, u
         if (flags[1] & 4) return fq_tile_submit(h, n_bytes, n_lines, n_reads, tslot, n_reads_out);      // a record to cut: csrc/fastq_tile.h
         if (flags[0] > h->tile.info[3]) h->tile.info[3] = flags[0];      // (no record is longer than the tile: the chunk goes on as without the switch)
     }
-    if (flags[1] & 8) return fail(h, MLST_E_HIP, "mlst_set_read_dedup: a probe ran through the whole table");      // (k_dd_mark hands DdCtr::err on)
-    if (flags[1] & 2) return fail(h, MLST_E_LIMIT, "a FASTQ read is longer than %d bases", MLST_MAX_READ_LEN);
-    if (flags[1] & 1) return fail(h, MLST_E_INVALID, "malformed FASTQ: a record does not start with '@' or its sequence and quality lengths differ");
+    rc = fq_flags_fail(h, flags); if (rc) return rc;
     h->rn.src.lines1 = h->d_fq_lines; h->rn.src.lines2 = nullptr; h->rn.src.pair_k = pair_k;
     return fq_pack_submit(h, n_reads, flags[0], tslot, paired, n_reads_out);
 }
@@ -5223,8 +5017,7 @@ static int fq_pack_submit(mlst_handle* h, u64 n_reads, u32 max_len, int tslot, i
     if (!h->rn.on) HIPCHK(h, hipEventRecord(h->ev_packed[tslot], h->stream));      // the text buffer may be overwritten from here on
     if (n_reads_out) *n_reads_out = n_reads;
     h->last_pack.n_reads = n_reads; h->last_pack.wpr = wpr; h->last_pack.qstride = qstride;
-    if (!h->rn.on && (h->rp.on || h->ra.on || h->rs.on || h->dd.on || h->po.on)) return submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);      // (the public entry refuses under mlst_set_read_prep / mlst_set_read_adapters)
-    if (!h->rn.on) return mlst_submit_packed_device(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired);
+    if (!h->rn.on) return submit_impl(h, h->d_packed, h->d_qrows, h->d_lens, n_reads, wpr, qstride, paired, 0);      // (not the public entry: it refuses under the read chain)
     // mlst_set_read_names: the text outlives pass 1 of its chunk -- the names of the reads it retained are copied out of the header
     // lines (csrc/read_names.h), behind the submission and outside its captured graph, and only then is the slot released
     const u64 read_base = h->reads_seen;
@@ -5378,12 +5171,7 @@ extern "C" int mlst_pack_fastq_host(const uint8_t* text, uint64_t n_bytes, uint3
 extern "C" int mlst_submit_packed_host(mlst_handle* h, const uint32_t* packed, const uint8_t* qrows, const uint16_t* lens, uint64_t n_reads,
                                        uint32_t wpr, uint32_t qstride, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
-    { int rc_ = rn_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
-    { int rc_ = rp_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
-    { int rc_ = ra_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
-    { int rc_ = rs_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
-    { int rc_ = dd_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
-    { int rc_ = po_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
+    { int rc_ = chain_refuse(h, "mlst_submit_packed_host"); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (!packed || !qrows || !lens) return fail(h, MLST_E_INVALID, "NULL argument");
@@ -5879,19 +5667,16 @@ static int bzp_finish_impl(mlst_handle* h, bool whole, uint64_t* n_reads_out) {
         hipLaunchKernelGGL(k_fq_pair_lines, dim3((ce[0] - a[0]) + (ce[1] - a[1])), dim3(256), 0, h->stream, (const u8*)slot, a[0], ce[0] - a[0], e[0] + 1, a[1], e[1] + 1,
                            (const u32*)(nl + a[0]), lines1, s[0], lines2, s[1], (u64)n1 + 1, nn[1] + 1);
         const u64 n_reads = 2 * k;
-        if (h->cap_fq_reads < n_reads) { hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); h->d_fq_soff = h->d_fq_qoff = nullptr;
-                                         HIPCHK(h, dmalloc(&h->d_fq_soff, n_reads)); HIPCHK(h, dmalloc(&h->d_fq_qoff, n_reads)); h->cap_fq_reads = n_reads; }
-        int rc = ensure_pack_buffers(h, n_reads, 2, 8); if (rc) return rc;
+        int rc = ensure_fq_reads(h, n_reads); if (rc) return rc;
+        rc = ensure_pack_buffers(h, n_reads, 2, 8); if (rc) return rc;
         hipLaunchKernelGGL(k_fq_pair_records, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)slot, (const u64*)lines1, (const u64*)lines2, k,
                            h->d_fq_soff, h->d_fq_qoff, h->d_lens, reinterpret_cast<u32*>(h->d_pr_meta + 1), h->d_pr_meta + 2);
-        rc = rp_apply(h, n_reads, reinterpret_cast<u32*>(h->d_pr_meta + 1), 1); if (rc) return rc;      // mlst_set_read_prep
+        rc = chain_apply(h, n_reads, reinterpret_cast<u32*>(h->d_pr_meta + 1), 1); if (rc) return rc;      // the read chain
         u64 back[3] = {0, 0, 0};      // flags, then the two cuts
         HIPCHK(h, hipMemcpyAsync(back, h->d_pr_meta + 1, 24, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         memcpy(flags, &back[0], 8); cut[0] = back[1]; cut[1] = back[2];
-        if (flags[1] & 8) return fail(h, MLST_E_HIP, "mlst_set_read_dedup: a probe ran through the whole table");
-        if (flags[1] & 2) return fail(h, MLST_E_LIMIT, "a FASTQ read is longer than %d bases", MLST_MAX_READ_LEN);
-        if (flags[1] & 1) return fail(h, MLST_E_INVALID, "malformed FASTQ: a record does not start with '@' or its sequence and quality lengths differ");
+        rc = fq_flags_fail(h, flags); if (rc) return rc;
     }
     for (int r = 0; r < 2; r++) {      // the text behind record k waits for the next piece of its file
         if (cut[r] < s[r] || cut[r] > e[r] + 1) return fail(h, MLST_E_HIP, "FASTQ line table inconsistent");
@@ -6712,12 +6497,7 @@ static int bamr_tile_submit(mlst_handle* h, BamSlot& S, const u32* rd_rec, const
 
 extern "C" int mlst_bam_reads_open(mlst_handle* h, uint32_t n_ref, uint32_t skip_bytes, int paired) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
-    { int rc_ = rn_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
-    { int rc_ = rp_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
-    { int rc_ = ra_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
-    { int rc_ = rs_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
-    { int rc_ = dd_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
-    { int rc_ = po_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
+    { int rc_ = chain_refuse(h, "mlst_bam_reads_open"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6761,12 +6541,7 @@ extern "C" int mlst_bam_reads_info(mlst_handle* h, uint64_t out[4]) {
 extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n_bytes, uint32_t read_len, uint32_t stride, uint32_t min_len,
                                  uint64_t* n_contigs_out, uint64_t* n_reads_out) {
     if (!h || !h->have_state) return fail(h, MLST_E_INVALID, "no reference loaded");
-    { int rc_ = rn_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
-    { int rc_ = rp_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
-    { int rc_ = ra_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
-    { int rc_ = rs_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
-    { int rc_ = dd_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
-    { int rc_ = po_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
+    { int rc_ = chain_refuse(h, "mlst_submit_fasta"); if (rc_) return rc_; }
     { int rc_ = bz_flush(h); if (rc_) return rc_; }
     if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
@@ -6852,8 +6627,7 @@ extern "C" int mlst_submit_fasta(mlst_handle* h, const uint8_t* text, uint64_t n
     const u64 n_reads = m.n_reads;
     if (n_reads == 0) return MLST_OK;
     if (n_reads >= (1ull << 32)) return fail(h, MLST_E_LIMIT, "more than 2^32 reads from one FASTA chunk");
-    if (h->cap_fq_reads < n_reads) { hipFree(h->d_fq_soff); hipFree(h->d_fq_qoff); h->d_fq_soff = h->d_fq_qoff = nullptr; h->cap_fq_reads = 0;
-                                     HIPCHK(h, dmalloc(&h->d_fq_soff, n_reads)); HIPCHK(h, dmalloc(&h->d_fq_qoff, n_reads)); h->cap_fq_reads = n_reads; }
+    { int rc = ensure_fq_reads(h, n_reads); if (rc) return rc; }
     u32 wpr = (m.max_len + 15) / 16; if (wpr < 2) wpr = 2; wpr = (wpr + 1) & ~1u;
     u32 qstride = (m.max_len + 7) & ~7u; if (qstride < 8) qstride = 8;
     { int rc = ensure_pack_buffers(h, n_reads, wpr, qstride); if (rc) return rc; }
@@ -6936,12 +6710,7 @@ extern "C" int mlst_set_read_tiling(mlst_handle* h, uint32_t read_len, uint32_t 
     if (!h) return MLST_E_INVALID;
     if ((read_len == 0) != (stride == 0)) return fail(h, MLST_E_INVALID, "read_len and stride must both be positive (or both 0: no tiling)");
     if (read_len > (u32)MLST_MAX_READ_LEN) return fail(h, MLST_E_LIMIT, "read_len %u exceeds %d bases", read_len, MLST_MAX_READ_LEN);
-    if (read_len) { int rc_ = rn_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window has no name)
-    if (read_len) { int rc_ = rp_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window is cut from the record as it stands)
-    if (read_len) { int rc_ = ra_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
-    if (read_len) { int rc_ = rs_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
-    if (read_len) { int rc_ = dd_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }
-    if (read_len) { int rc_ = po_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window has no mate)
+    if (read_len) { int rc_ = chain_refuse(h, "mlst_set_read_tiling"); if (rc_) return rc_; }      // (a window has no name and no mate, and is cut from the record as it stands)
     if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
     // (a reads stream took its tile when it was opened: include/mlst.h gives one message for every stream of reads)
     if (bam_is_open(h) && h->bam->reads) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (the reads stream of a BAM: its last chunk was not marked final)");
@@ -6961,242 +6730,6 @@ extern "C" int mlst_get_read_tiling_info(mlst_handle* h, uint64_t out[4]) {
     return MLST_OK;
 }
 
-// the retained reads' names (include/mlst.h; csrc/read_names.h): the switch may change only while the sample holds no reads and no stream
-// is open -- a read submitted without the switch has no name to give
-extern "C" int mlst_set_read_names(mlst_handle* h, int on) {
-    if (!h) return MLST_E_INVALID;
-    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
-    if ((on != 0) != h->rn.on && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_names changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
-    if (on && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_tiling is on: a window has no name");
-    h->rn.on = on != 0;
-    return MLST_OK;
-}
-// reads prepared before they are packed (include/mlst.h; csrc/read_prep.h): like the names, the setting may change only while the sample
-// holds no reads and no stream is open -- one sample is prepared one way
-extern "C" int mlst_set_read_prep(mlst_handle* h, const mlst_read_prep* p) {
-    if (!h) return MLST_E_INVALID;
-    const RpSet want = p ? RpSet{p->trim5, p->trim3, p->trim_qual, p->phred_base} : RpSet{0, 0, 0, 33};
-    if (want.phred_base != 33 && want.phred_base != 64) return fail(h, MLST_E_INVALID, "mlst_set_read_prep: phred_base is %u, not 33 or 64", want.phred_base);
-    if (want.trim_qual > 93) return fail(h, MLST_E_INVALID, "mlst_set_read_prep: trim_qual %u exceeds 93", want.trim_qual);
-    if (want.trim5 > 65535 || want.trim3 > 65535) return fail(h, MLST_E_INVALID, "mlst_set_read_prep: a trim exceeds 65535 bases");
-    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
-    const RpSet& cur = h->rp.set;
-    const bool same = want.trim5 == cur.trim5 && want.trim3 == cur.trim3 && want.trim_qual == cur.trim_qual && want.phred_base == cur.phred_base;
-    if (!same && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_prep changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
-    const bool on = (want.trim5 | want.trim3 | want.trim_qual) != 0 || want.phred_base != 33;
-    if (on && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_prep: mlst_set_read_tiling is on and a window is cut from the record as it stands");
-    h->rp.set = want; h->rp.on = on;
-    return MLST_OK;
-}
-extern "C" int mlst_get_read_prep(mlst_handle* h, mlst_read_prep* out) {
-    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
-    out->trim5 = h->rp.set.trim5; out->trim3 = h->rp.set.trim3; out->trim_qual = h->rp.set.trim_qual; out->phred_base = h->rp.set.phred_base;
-    return MLST_OK;
-}
-extern "C" int mlst_read_prep_info(mlst_handle* h, uint64_t out[4]) {
-    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
-    hipSetDevice(h->device);
-    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
-    RpCtr c; memset(&c, 0, sizeof c);
-    if (h->rp.on && h->rp.d_ctr) {
-        HIPCHK(h, hipMemcpyAsync(&c, h->rp.d_ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    out[0] = c.shortened; out[1] = c.removed; out[2] = c.emptied; out[3] = 0;
-    return MLST_OK;
-}
-// 3' adapters removed before the reads are packed (include/mlst.h; csrc/read_adapt.h): the life cycle is mlst_set_read_prep's
-extern "C" int mlst_set_read_adapters(mlst_handle* h, const char* adapters, uint32_t min_overlap, uint32_t error_permille) {
-    if (!h) return MLST_E_INVALID;
-    RaSet want = {}; std::string text;
-    if (adapters && *adapters) {
-        if (min_overlap < 1 || min_overlap > RA_MAX_LEN) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: min_overlap %u is outside 1..%d", min_overlap, RA_MAX_LEN);
-        if (error_permille > 500) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: error_permille %u exceeds 500", error_permille);
-        want.permille = error_permille; want.min_overlap = min_overlap;
-        for (const char* c = adapters;; c++) {      // letter by letter; ',' or the end closes an adapter
-            if (want.K >= RA_MAX_ADAPTERS) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: more than %d adapters", RA_MAX_ADAPTERS);
-            RaAd& A = want.ad[want.K];
-            if (*c == ',' || !*c) {
-                if (!A.m) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: adapter %u is empty", want.K + 1);
-                if (!(A.care[0] | A.care[1])) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: adapter %u holds only N", want.K + 1);
-                A.mo = min_overlap < A.m ? min_overlap : A.m;
-                want.K++;
-                if (!*c) break;
-                text.push_back(',');
-                continue;
-            }
-            const char up = (char)(*c & 0xDF);
-            const char* at = (up && !(*c & 0x80)) ? strchr("ACGTN", up) : nullptr;
-            if (!at) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: adapter %u holds a letter outside ACGTN (byte 0x%02x)", want.K + 1, (unsigned)(unsigned char)*c);
-            if (A.m >= RA_MAX_LEN) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: adapter %u is longer than %d letters", want.K + 1, RA_MAX_LEN);
-            const u32 w = A.m >> 5, sh = 2 * (A.m & 31);
-            if (up == 'N') A.anyn[w] |= 1ull << sh;
-            else { A.code[w] |= (u64)(at - "ACGTN") << sh; A.care[w] |= 1ull << sh; }
-            A.m++;
-            text.push_back(up);
-        }
-    }
-    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
-    const bool same = text == h->ra.text && want.permille == h->ra.set.permille && want.min_overlap == h->ra.set.min_overlap;
-    if (!same && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_adapters changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
-    if (want.K && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_adapters: mlst_set_read_tiling is on and a window is cut from the record as it stands");
-    h->ra.set = want; h->ra.text = text; h->ra.on = want.K != 0;
-    return MLST_OK;
-}
-extern "C" int mlst_get_read_adapters(mlst_handle* h, char* adapters, uint64_t cap, uint32_t* min_overlap, uint32_t* error_permille) {
-    if (!h) return MLST_E_INVALID;
-    if (adapters) {
-        if (cap < h->ra.text.size() + 1) return fail(h, MLST_E_INVALID, "mlst_get_read_adapters: the buffer holds %llu bytes, %llu are needed", (unsigned long long)cap, (unsigned long long)(h->ra.text.size() + 1));
-        memcpy(adapters, h->ra.text.c_str(), h->ra.text.size() + 1);
-    }
-    if (min_overlap) *min_overlap = h->ra.set.min_overlap;
-    if (error_permille) *error_permille = h->ra.set.permille;
-    return MLST_OK;
-}
-extern "C" int mlst_get_read_adapters_info(mlst_handle* h, uint64_t out[12]) {
-    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
-    hipSetDevice(h->device);
-    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
-    RaCtr c; memset(&c, 0, sizeof c);
-    if (h->ra.on && h->ra.d_ctr) {
-        HIPCHK(h, hipMemcpyAsync(&c, h->ra.d_ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    out[0] = c.trimmed; out[1] = c.removed; out[2] = c.emptied; out[3] = h->ra.set.K;
-    for (int k = 0; k < RA_MAX_ADAPTERS; k++) out[4 + k] = c.per_adapter[k];
-    return MLST_OK;
-}
-// per-cycle read statistics (include/mlst.h; csrc/read_stats.h): the switch's life cycle is mlst_set_read_prep's
-extern "C" int mlst_set_read_stats(mlst_handle* h, int on) {
-    if (!h) return MLST_E_INVALID;
-    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
-    if ((on != 0) != h->rs.on && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_stats changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
-    if (on && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_stats: mlst_set_read_tiling is on and the windows of a read would be counted, not the read");
-    h->rs.on = on != 0;
-    return MLST_OK;
-}
-extern "C" int mlst_get_read_stats(mlst_handle* h, int* on) {
-    if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
-    *on = h->rs.on ? 1 : 0;
-    return MLST_OK;
-}
-extern "C" int mlst_set_read_stats_side(mlst_handle* h, int side) {
-    if (!h) return MLST_E_INVALID;
-    if (side != 0 && side != 1) return fail(h, MLST_E_INVALID, "mlst_set_read_stats_side: side is %d, not 0 or 1", side);
-    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
-    h->rs.side = (u32)side;
-    return MLST_OK;
-}
-extern "C" int mlst_read_stats_fetch(mlst_handle* h, int stage, int side, uint64_t* out, uint64_t cap) {
-    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
-    if ((stage != 0 && stage != 1) || (side != 0 && side != 1)) return fail(h, MLST_E_INVALID, "mlst_read_stats_fetch: stage %d, side %d: each is 0 or 1", stage, side);
-    if (cap < RS_WORDS) return fail(h, MLST_E_INVALID, "mlst_read_stats_fetch: the buffer holds %llu words, %d are needed", (unsigned long long)cap, RS_WORDS);
-    hipSetDevice(h->device);
-    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
-    memset(out, 0, (size_t)RS_WORDS * 8);
-    if (!h->rs.on || !h->rs.d_tab) return MLST_OK;
-    if (stage == 1 && !h->rs.launches[1]) stage = 0;      // neither a trim nor an adapter ran: the prepared read is the raw one
-    HIPCHK(h, hipMemcpyAsync(out, h->rs.d_tab + ((u64)stage * 2 + (u64)side) * RS_WORDS, (size_t)RS_WORDS * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MLST_OK;
-}
-extern "C" int mlst_read_stats_info(mlst_handle* h, uint64_t out[4]) {
-    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
-    hipSetDevice(h->device);
-    { int rc_ = bz_flush(h); if (rc_) return rc_; }
-    const bool live = h->rs.on && h->rs.d_tab;
-    out[0] = live ? h->rs.launches[0] : 0; out[1] = live ? h->rs.launches[1] : 0; out[2] = h->rs.d_tab ? 4ull * RS_WORDS * 8 : 0; out[3] = 0;
-    return MLST_OK;
-}
-// exact duplicates emptied before the reads are packed (include/mlst.h; csrc/read_dedup.h): the switch's life cycle is mlst_set_read_prep's
-extern "C" int mlst_set_read_dedup(mlst_handle* h, int on) {
-    if (!h) return MLST_E_INVALID;
-    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
-    if ((on != 0) != h->dd.on && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_dedup changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
-    if (on && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_dedup: mlst_set_read_tiling is on and the windows of a read would be compared, not the read");
-    h->dd.on = on != 0;
-    return MLST_OK;
-}
-extern "C" int mlst_get_read_dedup(mlst_handle* h, int* on) {
-    if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
-    *on = h->dd.on ? 1 : 0;
-    return MLST_OK;
-}
-extern "C" int mlst_read_dedup_info(mlst_handle* h, uint64_t out[16]) {
-    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
-    hipSetDevice(h->device);
-    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
-    for (int k = 0; k < 16; k++) out[k] = 0;
-    if (!h->dd.on || !h->dd.d_ctr || !h->dd.d_mem) return MLST_OK;
-    DdCtr c; memset(&c, 0, sizeof c);
-    HIPCHK(h, hipMemsetAsync(h->dd.d_ctr->levels, 0, sizeof c.levels, h->stream));      // (counted anew by every call)
-    hipLaunchKernelGGL(k_dd_levels, dim3(grid_for(h->dd.tab.slots, 256, 4096)), dim3(256), 0, h->stream, h->dd.tab, h->dd.d_ctr);
-    HIPCHK(h, hipMemcpyAsync(&c, h->dd.d_ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (c.err) return fail(h, MLST_E_HIP, "mlst_set_read_dedup: a probe ran through the whole table");
-    out[0] = h->dd.reads; out[1] = c.units; out[2] = c.dups; out[3] = c.reads_removed; out[4] = c.bases_removed; out[5] = c.distinct; out[6] = c.clashes;
-    out[7] = h->dd.tab.slots;
-    for (int k = 0; k < 8; k++) out[8 + k] = c.levels[k];
-    return MLST_OK;
-}
-// adapter read-through cut from the overlap of the mates (include/mlst.h; csrc/read_overlap.h): the switch's life cycle is mlst_set_read_prep's
-extern "C" int mlst_set_read_pair_overlap(mlst_handle* h, int on, uint32_t min_overlap, uint32_t max_mismatches, uint32_t error_permille) {
-    if (!h) return MLST_E_INVALID;
-    if (on) {
-        if (min_overlap < 8 || min_overlap > PO_MAX_LEN) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: min_overlap %u is outside 8..%d", min_overlap, PO_MAX_LEN);
-        if (max_mismatches > 64) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: max_mismatches %u is outside 0..64", max_mismatches);
-        if (error_permille > 500) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: error_permille %u is outside 0..500", error_permille);
-    }
-    if (h->bz_pend.on || h->bzp.on || h->pair_open || h->fq_carry_len) return fail(h, MLST_E_INVALID, "a FASTQ stream is open (its last chunk was not marked final)");
-    if (bam_is_open(h)) return fail(h, MLST_E_INVALID, "a %s stream is open (its last chunk was not marked final)", bam_kind(h));
-    const bool same = (on != 0) == h->po.on && (!on || (min_overlap == h->po.set.min_overlap && max_mismatches == h->po.set.max_mism && error_permille == h->po.set.permille));
-    if (!same && h->reads_seen) return fail(h, MLST_E_INVALID, "the sample holds reads: mlst_set_read_pair_overlap changes only before the first submission or behind mlst_reset_sample (a read index base counts as reads)");
-    if (on && h->tile.read_len) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: mlst_set_read_tiling is on and takes unpaired text, whose windows have no mate");
-    h->po.on = on != 0;
-    if (on) { h->po.set.min_overlap = min_overlap; h->po.set.max_mism = max_mismatches; h->po.set.permille = error_permille; }
-    return MLST_OK;
-}
-extern "C" int mlst_get_read_pair_overlap(mlst_handle* h, int* on, uint32_t* min_overlap, uint32_t* max_mismatches, uint32_t* error_permille) {
-    if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
-    *on = h->po.on ? 1 : 0;
-    if (min_overlap) *min_overlap = h->po.set.min_overlap;
-    if (max_mismatches) *max_mismatches = h->po.set.max_mism;
-    if (error_permille) *error_permille = h->po.set.permille;
-    return MLST_OK;
-}
-// the counters and the histogram of the device, all zero with the switch off or before the first pair
-static int po_fetch(mlst_handle* h, PoCtr* c) {
-    memset(c, 0, sizeof *c);
-    hipSetDevice(h->device);
-    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
-    if (!h->po.on || !h->po.d_ctr) return MLST_OK;
-    HIPCHK(h, hipMemcpyAsync(c, h->po.d_ctr, sizeof *c, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MLST_OK;
-}
-extern "C" int mlst_read_pair_overlap_info(mlst_handle* h, uint64_t out[8]) {
-    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
-    PoCtr* const pc = new PoCtr;
-    int rc = po_fetch(h, pc);
-    if (!rc) { out[0] = h->po.on ? h->po.pairs : 0; out[1] = pc->overlapping; out[2] = pc->trimmed_pairs; out[3] = pc->reads_trimmed; out[4] = pc->bases_removed; out[5] = pc->emptied; out[6] = 0; out[7] = 0; }
-    delete pc;
-    return rc;
-}
-extern "C" int mlst_read_pair_overlap_hist(mlst_handle* h, uint64_t* out, uint64_t cap) {
-    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
-    if (cap < PO_HIST) return fail(h, MLST_E_INVALID, "mlst_read_pair_overlap_hist: the buffer holds %llu words, %d are needed", (unsigned long long)cap, PO_HIST);
-    PoCtr* const pc = new PoCtr;
-    int rc = po_fetch(h, pc);
-    if (!rc) memcpy(out, pc->hist, sizeof pc->hist);
-    delete pc;
-    return rc;
-}
 // MD:Z in the text export (include/mlst.h): no part of the sample's state; mlst_alignments_text_open reads it
 extern "C" int mlst_set_export_md(mlst_handle* h, int on) {
     if (!h) return MLST_E_INVALID;
@@ -7207,40 +6740,6 @@ extern "C" int mlst_set_export_md(mlst_handle* h, int on) {
 extern "C" int mlst_get_export_md(mlst_handle* h, int* on) {
     if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
     *on = h->at.md ? 1 : 0;
-    return MLST_OK;
-}
-extern "C" int mlst_get_read_names(mlst_handle* h, int* on) {
-    if (!h || !on) return fail(h, MLST_E_INVALID, "NULL argument");
-    *on = h->rn.on ? 1 : 0;
-    return MLST_OK;
-}
-extern "C" int mlst_read_names_info(mlst_handle* h, uint64_t out[4]) {
-    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
-    hipSetDevice(h->device);
-    { int rc_ = bz_flush(h); if (rc_) return rc_; }      // (a BGZF piece in flight is part of the sample)
-    RnCtr c; { int rc_ = rn_fetch(h, &c); if (rc_) return rc_; }
-    out[0] = c.done - c.fallbacks; out[1] = c.bytes; out[2] = c.fallbacks; out[3] = c.longest;
-    return MLST_OK;
-}
-extern "C" int mlst_read_names_fetch(mlst_handle* h, uint64_t* read_index, uint64_t* off, uint8_t* bytes) {
-    if (!h || !read_index || !off || !bytes) return fail(h, MLST_E_INVALID, "NULL argument");
-    hipSetDevice(h->device);
-    { int rc_ = bz_flush(h); if (rc_) return rc_; }
-    RnCtr c; { int rc_ = rn_fetch(h, &c); if (rc_) return rc_; }
-    off[0] = 0;
-    if (!c.done) return MLST_OK;
-    std::vector<u64> ridx(c.done), noff(c.done); std::vector<u16> nlen(c.done); std::vector<u8> arena(c.bytes ? c.bytes : 1);
-    HIPCHK(h, hipMemcpyAsync(ridx.data(), h->E.ret_ridx, c.done * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(noff.data(), h->rn.d_off, c.done * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(nlen.data(), h->rn.d_len, c.done * 2, hipMemcpyDeviceToHost, h->stream));
-    if (c.bytes) HIPCHK(h, hipMemcpyAsync(arena.data(), h->rn.d_bytes, c.bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    u64 n = 0, at = 0;
-    for (u64 s = 0; s < c.done; s++) {      // the slots with a name, in slot order
-        if (!nlen[s]) continue;
-        if (noff[s] + nlen[s] > c.bytes) return fail(h, MLST_E_HIP, "name arena inconsistent at slot %llu", (unsigned long long)s);
-        read_index[n] = ridx[s]; memcpy(bytes + at, arena.data() + noff[s], nlen[s]); at += nlen[s]; off[++n] = at;
-    }
     return MLST_OK;
 }
 
