@@ -704,7 +704,12 @@ __global__ __launch_bounds__(NW * 64) void k_route(const u32* __restrict__ packe
     constexpr int NT = WPR - 1;
     constexpr int QN = NW / 4;                    // thread slices of 256: slice q holds the runs of waves 4q .. 4q+3
     constexpr u32 TILE = NW * 64u;
-    constexpr u32 SCAP = TILE * NT + (NW == 16 ? 1024u : 768u);       // + dummy entries of empty runs (typically ~5 %)
+    // + dummy entries of empty runs.  A tile has NW * 256 (owner, wave) runs and at most TILE * NT seeds, NT / 4 per run: about
+    // NW * 256 * exp(-NT / 4) runs stay empty.  Rows of 8 words and more: ~5 % of the entries, 1,024 (768) words hold them twice
+    // over.  Narrow rows (reads up to 96 bases) leave most runs empty -- 3,190, 1,935 and 1,173 of 4,096 for 2, 4 and 6 words -- and
+    // with the room of the wide rows every full tile of such reads overflowed and became candidates outright
+    // (tests/test_gpu_sieve_words.py): every run for NT = 1, a quarter more than expected for NT = 3 and 5.
+    constexpr u32 SCAP = TILE * NT + (NT >= 7 ? (NW == 16 ? 1024u : 768u) : NT == 5 ? NW * 104u : NT == 3 ? NW * 160u : NW * 256u);
     constexpr u32 CW = 16;                        // entries per 64-byte chunk: what leaves for a region is whole, aligned chunks
     constexpr int OPW = RT_OWNERS / NW;           // owners whose segments a wave writes out
     // WO: up to three words of padding in front of every owner's segment (and in front of the first).  The room for them is
@@ -4666,8 +4671,11 @@ static int ensure_route_buffers(mlst_handle* h, u64 n_reads, u32 wpr, u64 n_read
     // tiles are handed out dynamically: a workgroup may take up to half as many again as its even share (the spread seen
     // is +-20 %); the capacities below (list of tiles, regions) are sized for that and a workgroup stops asking at the bound
     u64 tiles_max = (n_tiles + prod - 1) / prod * 3 / 2 + 8;
-    // expected entries per (owner, tile): tile * seeds / 256 + dummies (~10 % of nw) + ~2 of padding; 25 % and a constant on top
-    u64 cap = (u64)((double)tiles_max * ((double)tile / 256.0 * (wpr - 1) + 0.15 * nw + 2.0) * 1.25) + 256; cap = (cap + 31) & ~31ull;      // regions start on 128-byte boundaries, whole 64-byte chunks are written
+    // expected entries per (owner, tile): tile * seeds / 256 + dummies + ~2 of padding; 25 % and a constant on top.  Dummies: a run of
+    // (wpr - 1) / 4 seeds on average is empty with probability exp(-(wpr - 1) / 4) -- ~10 % of the owner's nw runs for rows of 10 words
+    // (0.15 stays the floor: rows of 10 words and more are sized as before), most of them for the narrow rows of short reads (see k_route's SCAP)
+    const double empty_runs = std::max(0.15, std::exp(-(double)(wpr - 1) / 4.0));
+    u64 cap = (u64)((double)tiles_max * ((double)tile / 256.0 * (wpr - 1) + empty_runs * nw + 2.0) * 1.25) + 256; cap = (cap + 31) & ~31ull;      // regions start on 128-byte boundaries, whole 64-byte chunks are written
     // A layout that is large enough stays (round 5): the capacities are upper bounds, and a submission of fewer reads than the one
     // before -- the pieces of a bgzip'd file differ in size -- used to re-allocate (a device-wide synchronisation) for its smaller one.
     if (h->rt_prod == prod && h->rt_nw == nw && h->rt_cap >= cap && h->rt_tiles_max >= tiles_max) { cap = h->rt_cap; tiles_max = h->rt_tiles_max; }
