@@ -653,6 +653,49 @@ int mlst_get_read_pair_overlap(mlst_handle* h, int* on, uint32_t* min_overlap, u
 int mlst_read_pair_overlap_info(mlst_handle* h, uint64_t out[8]);
 int mlst_read_pair_overlap_hist(mlst_handle* h, uint64_t* out, uint64_t cap);
 
+/* ---- poly-G / poly-X tails trimmed and reads filtered (off by default; csrc/read_filter.h; `cli type --trim-poly-g / --trim-poly-x /
+ * --min-length / --max-n / --low-complexity / --min-mean-qual`) ------------------------------------------------------------------------
+ * mlst_set_read_filter(h, &f): two-colour machines (NovaSeq, NextSeq) call G where a cluster gives no signal, so reads of short inserts
+ *   and of dying clusters end in a run of G of high quality that neither the quality trim nor the adapter cut sees; and a read that the
+ *   trims left very short, that holds many Ns, that is one repeated letter pair or whose qualities are low is better not aligned at
+ *   all.  Both are done on the device before the reads are packed, and the engine then behaves as if it had been given the filtered text
+ *   (metamlst_amd.fastq.poly_tail / read_fails / filter_fastq state the rule in Python and write that text).  NULL or a struct with
+ *   everything off (poly_mask 0, min_length 0, max_n MLST_RF_NO_LIMIT, complexity_pct 0, mean_qual 0) switches the stage off: nothing
+ *   is queued, nothing is allocated, and the kernels that run are those that ran before the switch existed.  MLST_E_INVALID, with a
+ *   sentence that names the field and its range, for poly_mask outside 0..15, poly_min outside 1..320 (looked at only with a poly_mask),
+ *   min_length outside 0..320, complexity_pct outside 0..100, mean_qual outside 0..93 (every max_n is taken).
+ *   The rule is modelled on fastp's --trim_poly_g / --trim_poly_x and its filters; it is the project's own and claims none of fastp's bytes.
+ * The rule, per read of n bases (integers only):
+ *   1. Letters are folded to upper case; a byte that is none of A C G T matches no letter.
+ *   2. The tail (poly_mask: bit 0 = A, 1 = C, 2 = G, 3 = T; 0 = no tail trim).  For a letter X of the mask and a tail length L in 1..n,
+ *      mism(L) is the number of the last L bases that are not X.  L is valid if L >= poly_min, the base at n - L is X (the tail begins
+ *      on its letter) and mism(L) <= min(5, L / 8).  The largest valid L over all letters is cut: n - L bases and qualities remain.  Two
+ *      letters cannot share a valid L.  A tail may step over a mismatch onto an earlier X: ten times ACGT and ten G are cut to 38.
+ *   3. The filters judge what the tail trim left, n bases again; the first that holds empties the read.  A read of length 0 fails none.
+ *        too short:       n < min_length
+ *        too many N:      more than max_n bytes that are none of A C G T in either case (MLST_RF_NO_LIMIT: off)
+ *        low complexity:  n >= 2 and 100 * d < complexity_pct * (n - 1), d = the positions i in [0, n - 1) whose folded letters at i and
+ *                         i + 1 differ, every byte that is none of A C G T folded to N
+ *        low quality:     sum(q) < mean_qual * n, q = clamp(character - phred base, 0, 127), the base mlst_set_read_prep's
+ *   4. A read left without a base stays a read of length 0 (mlst_set_read_prep's rule 4).  Each mate of a pair is treated on its own: the
+ *      partner of a failed mate stays.
+ *   5. It runs behind mlst_set_read_prep's steps, mlst_set_read_adapters' cut and mlst_set_read_pair_overlap's cut (a tail outside the
+ *      mates' overlap does not hinder that) and in front of mlst_set_read_dedup; the prepared tables of mlst_set_read_stats are counted
+ *      behind it (also when it is the only step that ran): the filter judges the read as it is aligned.
+ * Entries it applies to, what is refused while it is on ("<entry>: the read filter is on (mlst_set_read_filter) ..."), when the setting
+ *   may change and what mlst_reset_sample does: exactly as for mlst_set_read_adapters.
+ * mlst_get_read_filter: the setting (all off with the switch off).
+ * mlst_read_filter_info: out[0] = reads whose tail was cut, out[1] = bases removed with the tails, out[2..5] = reads cut by the tail's
+ *   letter (A, C, G, T), out[6] = reads of length >= 1 that were one tail, out[7] = reads emptied as too short, out[8] = with too many N,
+ *   out[9] = of low complexity, out[10] = of low quality, out[11] = the bases those reads held behind the tail trim, out[12..15] = 0.
+ *   All zero with the switch off; an open BGZF piece is finished first.
+ * No host synchronisation is added per chunk; mlst_get_kernel_time 23 is k_rf_filter alone. */
+#define MLST_RF_NO_LIMIT 0xFFFFFFFFu
+typedef struct { uint32_t poly_mask, poly_min, min_length, max_n, complexity_pct, mean_qual; } mlst_read_filter;
+int mlst_set_read_filter(mlst_handle* h, const mlst_read_filter* f);
+int mlst_get_read_filter(mlst_handle* h, mlst_read_filter* out);
+int mlst_read_filter_info(mlst_handle* h, uint64_t out[16]);
+
 /* ---- bowtie2's MD:Z field in the text export (off by default; csrc/aln_text.h; `cli type --md`) --------------------------------------
  * mlst_set_export_md(h, 1): every record of mlst_alignments_text_* carries MD:Z:<text> between NM:i and YT:Z:UU, bowtie2's place;
  *   columns 1-11 and every other field are the bytes they are without it.  With the switch off the export writes what it wrote
@@ -942,7 +985,8 @@ int mlst_set_profiling(mlst_handle* h, int on);   /* 0 = off, 1 = events + sieve
  * csrc/fastq_tile.h, csrc/bam_tile.h; outside 6); 15 = the line table of a SAM chunk (k_fq_count, k_fq_scan, k_fq_lines, k_sam_flags), 16 =
  * k_sam_accumulate and 17 = k_sam_pileup (csrc/sam_dev.h; two entries of 15 per chunk); 18 = k_rp_qtrim (csrc/read_prep.h) and 19 = k_ra_cut
  * (csrc/read_adapt.h), each alone (inside 6); 20 = k_rs_count (csrc/read_stats.h; alone, inside 6); 21 = k_dd_insert + k_dd_sign + k_dd_mark
- * (csrc/read_dedup.h; the three launches of a chunk together, inside 6); 22 = k_po_cut (csrc/read_overlap.h; alone, inside 6); 9 = k_route, 10 =
+ * (csrc/read_dedup.h; the three launches of a chunk together, inside 6); 22 = k_po_cut (csrc/read_overlap.h; alone, inside 6); 23 = k_rf_filter
+ * (csrc/read_filter.h; alone, inside 6); 9 = k_route, 10 =
  * k_route_probe and 11 = k_route_verify, the three kernels of the routed sieve (inside 0) (events bracket the launch on the engine's
  * stream, so with several engines on one GPU they include the time a kernel queues behind another stream's kernel);
  * 7 = the sieve's execution window measured inside the kernel (wall clock at the first workgroup's start and the last

@@ -180,6 +180,31 @@ def _type_parser(sub):
                    help="--pair-overlap: at most N letters of the overlap may differ (0 to 64, default 5)")
     p.add_argument("--pair-overlap-rate", dest="pair_overlap_rate", default=None, type=float, metavar="X",
                    help="--pair-overlap: and at most floor(X * overlap) of them (0 to 0.5, default 0.2; kept as round(1000 * X) permille)")
+    p.add_argument("--trim-poly-g", dest="trim_poly_g", action="store_true",
+                   help="FASTQ input: trim a tail of G from the 3' end of every read before it is aligned, on the GPU (csrc/read_filter.h; "
+                        "the rule: metamlst_amd.fastq.poly_tail, modelled on fastp --trim_poly_g; it is the project's own and claims none of "
+                        "fastp's bytes).  Two-colour machines (NovaSeq, NextSeq) call G where a cluster gives no signal, at high quality, so "
+                        "--trim-qual does not see such a tail.  A tail is at least --poly-min bases long, begins on a G and holds at most one "
+                        "other base per eight, five at the most; the longest such tail is cut.  It runs behind --trim* / --adapter / "
+                        "--pair-overlap and in front of --dedup, each mate on its own.  Accepted and refused where --adapter is, a folder, "
+                        "several samples and --gpus N included; a read left without a base stays a read.  Unless --quiet, one line reports "
+                        "what this and the four read filters (--min-length, --max-n, --low-complexity, --min-mean-qual) did")
+    p.add_argument("--trim-poly-x", dest="trim_poly_x", action="store_true",
+                   help="FASTQ input: as --trim-poly-g, for a tail of any one letter of A, C, G and T (fastp --trim_poly_x); give one of the two")
+    p.add_argument("--poly-min", dest="poly_min", default=None, type=int, metavar="N",
+                   help="--trim-poly-g / --trim-poly-x: the shortest tail that is cut (1 to 320, default 10; at 10 about 0.005 %% of random "
+                        "150-base reads lose a G tail by chance, 0.015 %% a tail of any letter; at 5, 0.5 %%)")
+    p.add_argument("--min-length", dest="min_length", default=None, type=int, metavar="N",
+                   help="FASTQ input: remove every read that the trims left with fewer than N bases (1 to 320; fastp --length_required), on "
+                        "the GPU behind the tail trim.  A removed read stays a read without a base (indices, pairing and --read-names are "
+                        "those of the file; its mate stays) and appears in no export; see --trim-poly-g")
+    p.add_argument("--max-n", dest="max_n", default=None, type=int, metavar="N",
+                   help="FASTQ input: remove every read that holds more than N bases other than A, C, G and T (fastp --n_base_limit); see --min-length")
+    p.add_argument("--low-complexity", dest="low_complexity", default=None, type=int, metavar="PCT",
+                   help="FASTQ input: remove every read of which fewer than PCT percent of the bases differ from the next one (1 to 100; "
+                        "fastp --low_complexity_filter with --complexity_threshold PCT, whose default is 30); see --min-length")
+    p.add_argument("--min-mean-qual", dest="min_mean_qual", default=None, type=int, metavar="Q",
+                   help="FASTQ input: remove every read whose mean quality is below Q (1 to 93; fastp --average_qual); see --min-length")
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -339,6 +364,18 @@ def run_type(a, argv=None) -> int:
                 (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp),
                  "the reads of a BAM are taken as they are stored: FASTQ input only"))):
             return 1
+    read_filter = _read_filter_of(a)
+    if read_filter is not None:      # (refused before any GPU use, each with its reason)
+        if read_filter is False:
+            return 1
+        if _refused("read filter (--trim-poly-g, --trim-poly-x, --min-length, --max-n, --low-complexity, --min-mean-qual): ", (
+                (a.alignments, "with --alignments the records are what they are: the file holds alignments, not reads to trim or remove"),
+                (a.contigs, "--contigs cuts assemblies into windows, and an assembly has neither tails nor qualities"),
+                (a.long_reads, "--long-reads cuts reads into windows, and a window is cut from the record as it stands"),
+                (a.long_bam_reads, "--long-bam-reads cuts reads into windows, and a window is cut from the record as it stands"),
+                (not a.alignments and any(_is_reads_bam(f) for smp in samples for f in smp),
+                 "the reads of a BAM are taken as they are stored: FASTQ input only"))):
+            return 1
     if getattr(a, "read_stats", False):      # (refused before any GPU use, each with its reason)
         if _refused("--read-stats: ", (
                 (a.alignments, "with --alignments the file holds alignments, not the reads of a FASTQ file"),
@@ -445,7 +482,7 @@ def run_type(a, argv=None) -> int:
         eng.set_read_tiling(*(long_reads or long_bam))
     if a.read_names:      # (FASTQ input only: text, host-inflated .gz and BGZF all reach the device as text, where the names are kept)
         eng.set_read_names(True)
-    _apply_read_chain(eng, a, read_prep, adapters, pair_overlap)      # (the same entries; before a rank's first read index base)
+    _apply_read_chain(eng, a, read_prep, adapters, pair_overlap, read_filter)      # (the same entries; before a rank's first read index base)
     # the built host index is kept next to the database (as the reference keeps <idx>.1.bt2: metamlst-index.py:224-225) unless a
     # species filter made this index a one-off or MLST_INDEX_CACHE=0
     ref_cache = (a.database + ".mlstref") if (not a.filter and os.environ.get("MLST_INDEX_CACHE", "1") != "0") else ""
@@ -467,7 +504,7 @@ def run_type(a, argv=None) -> int:
             e2.set_bgzf_verify(a.verify_crc)
             if long_reads or long_bam:
                 e2.set_read_tiling(*(long_reads or long_bam))
-            _apply_read_chain(e2, a, read_prep, adapters, pair_overlap)      # (the switches refused for several samples are off)
+            _apply_read_chain(e2, a, read_prep, adapters, pair_overlap, read_filter)      # (the switches refused for several samples are off)
             if a.depth_cap:
                 e2.set_depth_cap(a.depth_cap)
             engines.append(e2)
@@ -478,13 +515,16 @@ def run_type(a, argv=None) -> int:
         from .multigpu import type_many_samples
         prep_info = {"shortened": 0, "bases_removed": 0, "emptied": 0} if read_prep and not a.quiet else None
         adapt_info = {"trimmed": 0, "bases_removed": 0, "emptied": 0, "per_adapter": [0] * len(adapters["adapters"])} if adapters and not a.quiet else None
+        filter_info = _sum_filter_infos([]) if read_filter and not a.quiet else None
         rc = type_many_samples(engines, idx, database, targs, samples, rank, world, a.o, a.log, chunk_bytes,
                                printer=None if a.quiet else (lambda results: _print_results(a, results)), tile=tile, long_reads=long_reads,
-                               long_bam_reads=long_bam, read_prep_info=prep_info, read_adapters_info=adapt_info)
+                               long_bam_reads=long_bam, read_prep_info=prep_info, read_adapters_info=adapt_info, read_filter_info=filter_info)
         if prep_info is not None:
             _say_read_prep(prep_info, world)
         if adapt_info is not None:
             _say_read_adapters(adapt_info, adapters["adapters"], world)
+        if filter_info is not None:
+            print(read_filter_line(filter_info, world), flush=True)
         database.closeConnection()
         return rc
     if a.alignments:
@@ -550,6 +590,11 @@ def run_type(a, argv=None) -> int:
             dist.all_gather_object(box, eng.read_adapters_info())
             if rank == 0 and not a.quiet:
                 _say_read_adapters(_sum_adapter_infos(box), adapters["adapters"], 1)
+        if read_filter:
+            box = [None] * world
+            dist.all_gather_object(box, eng.read_filter_info())
+            if rank == 0 and not a.quiet:
+                print(read_filter_line(_sum_filter_infos(box)), flush=True)
         dist.destroy_process_group()
         return 0
     # FASTQ text goes to the GPU as is and is parsed there (mlst_submit_fastq); a reader thread stays two chunks ahead
@@ -580,6 +625,8 @@ def _finish_type_device(a, eng, idx, database, targs, paired: bool = False) -> i
         _say_read_prep(eng.read_prep_info(), 1)
     if rc == 0 and not a.quiet and _adapters_of(a, say=False):
         _say_read_adapters(eng.read_adapters_info(), eng.get_read_adapters()["adapters"], 1)
+    if rc == 0 and not a.quiet and _read_filter_of(a, say=False):
+        print(read_filter_line(eng.read_filter_info()), flush=True)
     if rc == 0 and not a.quiet and _pair_overlap_of(a, say=False):
         print(read_pair_overlap_line(eng.read_pair_overlap_info()), flush=True)
     if rc == 0 and getattr(a, "read_stats", False):
@@ -616,7 +663,7 @@ def _refused(prefix: str, rows) -> bool:
     return False
 
 
-def _apply_read_chain(eng, a, read_prep, adapters, pair_overlap) -> None:
+def _apply_read_chain(eng, a, read_prep, adapters, pair_overlap, read_filter=None) -> None:
     """The switches of the read chain as the command was given them: the reads are prepared, cut, counted and compared
     where the FASTQ text is parsed"""
     if read_prep:
@@ -629,6 +676,8 @@ def _apply_read_chain(eng, a, read_prep, adapters, pair_overlap) -> None:
         eng.set_read_dedup(True)
     if pair_overlap:
         eng.set_read_pair_overlap(True, **pair_overlap)
+    if read_filter:
+        eng.set_read_filter(**read_filter)
 
 
 def _read_prep_of(a):
@@ -698,6 +747,53 @@ def _pair_overlap_of(a, say: bool = True):
             print("--pair-overlap: %s" % e)
         return False
     return out
+
+
+def _read_filter_of(a, say: bool = True):
+    """--trim-poly-g, --trim-poly-x, --poly-min, --min-length, --max-n, --low-complexity, --min-mean-qual -> the arguments of
+    Engine.set_read_filter, None when none of them is given, False (said) when a flag is out of range, --poly-min stands alone or both
+    tail switches are given"""
+    from .fastq import check_read_filter
+    g, x, pm = bool(getattr(a, "trim_poly_g", False)), bool(getattr(a, "trim_poly_x", False)), getattr(a, "poly_min", None)
+    ml, mn, lc, mq = (getattr(a, k, None) for k in ("min_length", "max_n", "low_complexity", "min_mean_qual"))
+
+    def no(text: str):
+        if say:
+            print(text)
+        return False
+    if g and x:
+        return no("--trim-poly-x trims G tails too: give one of the two")
+    if pm is not None and not (g or x):
+        return no("--poly-min belongs to --trim-poly-g / --trim-poly-x: give the switch it applies to")
+    if not (g or x) and ml is None and mn is None and lc is None and mq is None:
+        return None
+    for flag, v, lo, hi in (("--poly-min", pm, 1, 320), ("--min-length", ml, 1, 320), ("--max-n", mn, 0, 0xFFFFFFFE), ("--low-complexity", lc, 1, 100), ("--min-mean-qual", mq, 1, 93)):
+        if v is not None and not lo <= v <= hi:
+            return no("%s takes a number from %d to %d, not %d" % (flag, lo, hi, v))
+    out = {"poly": "G" if g else "ACGT" if x else "", "poly_min": 10 if pm is None else pm, "min_length": ml or 0, "max_n": mn, "complexity": lc or 0, "mean_qual": mq or 0}
+    check_read_filter(out["poly"], out["poly_min"], out["min_length"], out["max_n"], out["complexity"], out["mean_qual"])
+    return out
+
+
+def _sum_filter_infos(infos) -> dict:
+    """Engine.read_filter_info() of several engines or ranks, added up (none: all zero)"""
+    out = {"tail_trimmed": 0, "tail_bases": 0, "per_letter": [0, 0, 0, 0], "tail_emptied": 0, "failed_short": 0, "failed_n": 0, "failed_complexity": 0,
+           "failed_quality": 0, "filtered_bases": 0}
+    for b in infos:
+        for key, v in b.items():
+            out[key] = [p + q for p, q in zip(out[key], v)] if key == "per_letter" else out[key] + v
+    return out
+
+
+def read_filter_line(info: dict, world: int = 1) -> str:
+    """The line on what the tail trim and the read filters did (info: Engine.read_filter_info() or fastq.filter_fastq's counters, summed
+    over the samples of a folder; a rank of --gpus N then speaks for its own samples)"""
+    failed = [int(info[k]) for k in ("failed_short", "failed_n", "failed_complexity", "failed_quality")]
+    rank = (" (the samples of rank %s of %d)" % (os.environ.get("RANK", "0"), world)) if world > 1 else ""
+    return ("read filter: %d poly tails trimmed (A %d, C %d, G %d, T %d), %d bases removed, %d reads left without a base; %d reads removed "
+            "(%d too short, %d with too many N, %d of low complexity, %d of low quality), %d bases"
+            % (int(info["tail_trimmed"]), *[int(v) for v in info["per_letter"]], int(info["tail_bases"]), int(info["tail_emptied"]), sum(failed), *failed,
+               int(info["filtered_bases"]))) + rank
 
 
 def read_pair_overlap_line(info: dict) -> str:

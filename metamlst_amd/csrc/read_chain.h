@@ -1,6 +1,6 @@
-// The read chain on the host ("The read chain"): what strings the six read-preparation stages of the FASTQ path together.  The kernels are
-// in csrc/read_names.h, read_prep.h, read_adapt.h, read_stats.h, read_dedup.h and read_overlap.h, the state of each stage in
-// mlst_handle (h->rn, rp, ra, rs, dd, po).  Here, once for all of them: which entries a switch closes (chain_refuse), when a switch may
+// The read chain on the host ("The read chain"): what strings the seven read-preparation stages of the FASTQ path together.  The kernels are
+// in csrc/read_names.h, read_prep.h, read_adapt.h, read_stats.h, read_dedup.h, read_overlap.h and read_filter.h, the state of each stage in
+// mlst_handle (h->rn, rp, ra, rs, dd, po, rf).  Here, once for all of them: which entries a switch closes (chain_refuse), when a switch may
 // change (chain_gate), the order of the stages over a parsed chunk (chain_apply), the counters' first use and read-back (chain_ctr,
 // chain_fetch), what a new sample and the end of the handle do (chain_reset, chain_free), and the public setters and readers.
 // A new stage is one row in chain_refuse, one line in chain_apply, chain_reset and chain_free, and its setter.
@@ -21,6 +21,7 @@ static int chain_refuse(mlst_handle* h, const char* entry) {
         {h->rs.on, "%s: read statistics are on (mlst_set_read_stats) and only the FASTQ text and BGZF entries count their reads"},
         {h->dd.on, "%s: duplicate removal is on (mlst_set_read_dedup) and only the FASTQ text and BGZF entries apply it"},
         {h->po.on, "%s: mate overlap trimming is on (mlst_set_read_pair_overlap) and only the paired FASTQ text and BGZF entries apply it"},
+        {h->rf.on, "%s: the read filter is on (mlst_set_read_filter) and only the FASTQ text and BGZF entries apply it"},
     };
     for (const auto& r : rows) if (r.on) return fail(h, MLST_E_INVALID, r.fmt, entry);
     return MLST_OK;
@@ -72,11 +73,12 @@ static int chain_reset(mlst_handle* h) {
     h->dd.units_seen = h->dd.reads = 0;
     if (h->po.d_ctr) HIPCHK(h, hipMemsetAsync(h->po.d_ctr, 0, sizeof(PoCtr), h->stream));
     h->po.pairs = 0;
+    if (h->rf.d_ctr) HIPCHK(h, hipMemsetAsync(h->rf.d_ctr, 0, sizeof(RfCtr), h->stream));
     return MLST_OK;
 }
 // (the name arena is freed with the retained-read store it is sized by: free_state)
 static void chain_free(mlst_handle* h) {
-    hipFree(h->rp.d_ctr); hipFree(h->ra.d_ctr); hipFree(h->rs.d_tab); hipFree(h->po.d_ctr);
+    hipFree(h->rp.d_ctr); hipFree(h->ra.d_ctr); hipFree(h->rs.d_tab); hipFree(h->po.d_ctr); hipFree(h->rf.d_ctr);
     hipFree(h->dd.d_mem); hipFree(h->dd.d_ctr); hipFree(h->dd.d_slot_of); hipFree(h->dd.d_key2);
 }
 
@@ -206,7 +208,7 @@ static int po_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
 }
 // The parser has left offsets and lengths of n_reads reads of h->d_fq_text and the longest length in flags[0].  The chain, in its one
 // order, queued in front of the read-back of the flags (no synchronisation added): raw statistics, quality trim, adapter cut, mate
-// overlap, prepared statistics, duplicate removal.  flags[0] is zeroed in front of every kernel that shortens reads, so the last one
+// overlap, tail trim and read filter, prepared statistics, duplicate removal.  flags[0] is zeroed in front of every kernel that shortens reads, so the last one
 // alone feeds the longest length the host reads (an atomicMax with the shorter lengths would leave the longer one standing).
 // The prepared tables are counted only behind a stage that shortens: with none, launches[1] stays 0 and mlst_read_stats_fetch hands out
 // the raw tables for them.  Never with a tile (chain_refuse)
@@ -230,7 +232,14 @@ static int chain_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
                            d_flags, h->ra.d_ctr);
     }
     if (h->po.on) { rc = po_apply(h, n_reads, d_flags, paired); if (rc) return rc; }      // (zeroes flags[0] itself; refuses unpaired and odd chunks)
-    if (h->rs.on && (trims || h->ra.on || h->po.on)) { rc = rs_launch(h, n_reads, d_flags, paired, 1); if (rc) return rc; }
+    if (h->rf.on) {      // (behind the mates' overlap: the filter judges the read as it is aligned)
+        rc = chain_ctr(h, &h->rf.d_ctr); if (rc) return rc;
+        HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
+        Prof pf(h, 23);      // (mlst_get_kernel_time 23: k_rf_filter alone)
+        hipLaunchKernelGGL(k_rf_filter, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, (const u64*)h->d_fq_qoff, h->d_lens,
+                           n_reads, h->rf.set, P.phred_base, d_flags, h->rf.d_ctr);
+    }
+    if (h->rs.on && (trims || h->ra.on || h->po.on || h->rf.on)) { rc = rs_launch(h, n_reads, d_flags, paired, 1); if (rc) return rc; }
     if (h->dd.on) { rc = dd_apply(h, n_reads, d_flags, paired); if (rc) return rc; }      // (zeroes flags[0] itself; the prepared tables stay what they are)
     return MLST_OK;
 }
@@ -465,4 +474,39 @@ extern "C" int mlst_read_pair_overlap_hist(mlst_handle* h, uint64_t* out, uint64
     if (!rc) memcpy(out, pc->hist, sizeof pc->hist);
     delete pc;
     return rc;
+}
+// poly-G / poly-X tails trimmed and reads filtered before the reads are packed (csrc/read_filter.h)
+extern "C" int mlst_set_read_filter(mlst_handle* h, const mlst_read_filter* f) {
+    if (!h) return MLST_E_INVALID;
+    RfSet want = {0, 10, 0, RF_NO_LIMIT, 0, 0};      // (off)
+    if (f) {
+        if (f->poly_mask > 15) return fail(h, MLST_E_INVALID, "mlst_set_read_filter: poly_mask %u is outside 0..15 (bits 0..3: A, C, G, T)", f->poly_mask);
+        if (f->poly_mask && (f->poly_min < 1 || f->poly_min > RF_MAX_LEN)) return fail(h, MLST_E_INVALID, "mlst_set_read_filter: poly_min %u is outside 1..%d", f->poly_min, RF_MAX_LEN);
+        if (f->min_length > RF_MAX_LEN) return fail(h, MLST_E_INVALID, "mlst_set_read_filter: min_length %u is outside 0..%d", f->min_length, RF_MAX_LEN);
+        if (f->complexity_pct > 100) return fail(h, MLST_E_INVALID, "mlst_set_read_filter: complexity_pct %u is outside 0..100", f->complexity_pct);
+        if (f->mean_qual > 93) return fail(h, MLST_E_INVALID, "mlst_set_read_filter: mean_qual %u is outside 0..93", f->mean_qual);
+        want = RfSet{f->poly_mask, f->poly_mask ? f->poly_min : 10u, f->min_length, f->max_n, f->complexity_pct, f->mean_qual};
+    }
+    const RfSet& cur = h->rf.set;
+    const bool same = want.poly_mask == cur.poly_mask && want.poly_min == cur.poly_min && want.min_length == cur.min_length && want.max_n == cur.max_n &&
+                      want.complexity_pct == cur.complexity_pct && want.mean_qual == cur.mean_qual;
+    const bool on = want.poly_mask != 0 || want.min_length != 0 || want.max_n != RF_NO_LIMIT || want.complexity_pct != 0 || want.mean_qual != 0;
+    { int rc_ = chain_gate(h, "mlst_set_read_filter", !same, on, "mlst_set_read_filter: mlst_set_read_tiling is on and a window is cut from the record as it stands"); if (rc_) return rc_; }
+    h->rf.set = want; h->rf.on = on;
+    return MLST_OK;
+}
+extern "C" int mlst_get_read_filter(mlst_handle* h, mlst_read_filter* out) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    const RfSet& S = h->rf.set;
+    out->poly_mask = S.poly_mask; out->poly_min = S.poly_min; out->min_length = S.min_length; out->max_n = S.max_n; out->complexity_pct = S.complexity_pct; out->mean_qual = S.mean_qual;
+    return MLST_OK;
+}
+extern "C" int mlst_read_filter_info(mlst_handle* h, uint64_t out[16]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    RfCtr c; { int rc_ = chain_fetch(h, h->rf.on, &h->rf.d_ctr, &c); if (rc_) return rc_; }
+    out[0] = c.tail_trimmed; out[1] = c.tail_bases;
+    for (int k = 0; k < 4; k++) { out[2 + k] = c.per_letter[k]; out[7 + k] = c.failed[k]; }
+    out[6] = c.tail_emptied; out[11] = c.filtered_bases;
+    for (int k = 12; k < 16; k++) out[k] = 0;
+    return MLST_OK;
 }

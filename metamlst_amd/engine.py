@@ -186,6 +186,9 @@ def load_library(path: str | None = None):
         "mlst_get_read_pair_overlap": (C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "mlst_read_pair_overlap_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_read_pair_overlap_hist": (C.c_int, [H, C.POINTER(C.c_uint64), C.c_uint64]),
+        "mlst_set_read_filter": (C.c_int, [H, C.POINTER(C.c_uint32)]),      # (mlst_read_filter: six uint32_t)
+        "mlst_get_read_filter": (C.c_int, [H, C.POINTER(C.c_uint32)]),
+        "mlst_read_filter_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_set_export_md": (C.c_int, [H, C.c_int]),
         "mlst_get_export_md": (C.c_int, [H, C.POINTER(C.c_int)]),
         "mlst_read_names_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
@@ -986,6 +989,41 @@ class Engine:
         self._check(self.lib.mlst_read_pair_overlap_hist(self._h, hist, 1024), "mlst_read_pair_overlap_hist")
         return {"pairs": int(out[0]), "overlapping": int(out[1]), "trimmed_pairs": int(out[2]), "reads_trimmed": int(out[3]), "bases_removed": int(out[4]),
                 "emptied": int(out[5]), "insert_hist": [int(v) for v in hist]}
+
+    def set_read_filter(self, poly="", poly_min: int = 10, min_length: int = 0, max_n=None, complexity: int = 0, mean_qual: int = 0) -> None:
+        """Trim poly-G / poly-X tails from the 3' end of every read of FASTQ text and empty the reads that fail a filter, on the GPU before
+        the reads are packed (mlst_set_read_filter; off by default; the rule: fastq.poly_tail / fastq.read_fails / fastq.filter_fastq,
+        modelled on fastp), behind set_read_prep's steps, set_read_adapters' cut and set_read_pair_overlap's, in front of set_read_dedup.
+        The engine then behaves as if it had been given filter_fastq's text.  poly: the tail letters ("G": two-colour chemistry; "ACGT":
+        every letter; "": no tail trim), poly_min: the shortest tail; min_length, max_n (None: no limit), complexity (percent of
+        neighbouring bases that differ), mean_qual: the filters, 0 / None = off.  FASTQ text and BGZF entries only -- every other way of
+        adding reads is refused while it is on; may change only while the sample holds no reads and no stream is open.  All defaults: off."""
+        letters = (poly.encode() if isinstance(poly, str) else bytes(poly)).upper()
+        if letters.strip(b"ACGT"):
+            raise ValueError("set_read_filter: tail letters %r: only A, C, G and T are taken" % letters.decode("latin-1"))
+        vals = [sum(1 << b"ACGT".index(c) for c in set(letters)), poly_min, min_length, 0xFFFFFFFF if max_n is None else max_n, complexity, mean_qual]
+        for v in vals:
+            if int(v) != v or not 0 <= int(v) < 1 << 32:
+                raise ValueError("set_read_filter: %r is no unsigned 32-bit value" % (v,))
+        if max_n is not None and int(max_n) == 0xFFFFFFFF:
+            raise ValueError("set_read_filter: max_n %r stands for no limit: give None" % (max_n,))
+        self._check(self.lib.mlst_set_read_filter(self._h, (C.c_uint32 * 6)(*[int(v) for v in vals])), "mlst_set_read_filter")
+
+    def get_read_filter(self) -> dict:
+        """{"poly": the tail letters, "poly_min", "min_length", "max_n" (None: no limit), "complexity", "mean_qual"}"""
+        p = (C.c_uint32 * 6)()
+        self._check(self.lib.mlst_get_read_filter(self._h, p), "mlst_get_read_filter")
+        return {"poly": "".join(c for k, c in enumerate("ACGT") if (int(p[0]) >> k) & 1), "poly_min": int(p[1]), "min_length": int(p[2]),
+                "max_n": None if int(p[3]) == 0xFFFFFFFF else int(p[3]), "complexity": int(p[4]), "mean_qual": int(p[5])}
+
+    def read_filter_info(self) -> dict:
+        """Since the last reset_sample, fastq.filter_fastq's counters: tail_trimmed, tail_bases, per_letter (A, C, G, T), tail_emptied,
+        failed_short, failed_n, failed_complexity, failed_quality, filtered_bases.  All zero with the switch off."""
+        out = (C.c_uint64 * 16)()
+        self._check(self.lib.mlst_read_filter_info(self._h, out), "mlst_read_filter_info")
+        return {"tail_trimmed": int(out[0]), "tail_bases": int(out[1]), "per_letter": [int(out[2 + k]) for k in range(4)], "tail_emptied": int(out[6]),
+                "failed_short": int(out[7]), "failed_n": int(out[8]), "failed_complexity": int(out[9]), "failed_quality": int(out[10]),
+                "filtered_bases": int(out[11])}
 
     def set_export_md(self, on: bool = True) -> None:
         """export_sam_text / write_sam_all write bowtie2's MD:Z field between NM:i and YT:Z, formatted on the GPU (mlst_set_export_md; off

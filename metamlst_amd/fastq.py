@@ -969,6 +969,125 @@ def pair_overlap_median(hist) -> int:
     return 0
 
 
+def check_read_filter(letters=b"", poly_min: int = 10, min_length: int = 0, max_n=None, complexity: int = 0, mean_qual: int = 0) -> int:
+    """The tail letters of Engine.set_read_filter as mlst_read_filter's poly_mask (bit 0 = A, 1 = C, 2 = G, 3 = T); ValueError for a
+    setting mlst_set_read_filter refuses: a letter outside ACGT, poly_min outside 1..320 (looked at only with letters), min_length
+    outside 0..320, complexity outside 0..100, mean_qual outside 0..93, and a max_n that is no unsigned 32-bit count (None: no limit)."""
+    letters = (letters.encode() if isinstance(letters, str) else bytes(letters)).upper()
+    if letters.strip(b"ACGT"):
+        raise ValueError("tail letters %r: only A, C, G and T are taken" % letters.decode("latin-1"))
+    rows = [("min_length", min_length, 0, 320), ("complexity", complexity, 0, 100), ("mean_qual", mean_qual, 0, 93)]
+    if letters:
+        rows.insert(0, ("poly_min", poly_min, 1, 320))
+    if max_n is not None:
+        rows.append(("max_n", max_n, 0, 0xFFFFFFFE))
+    for name, v, lo, hi in rows:
+        if int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError("%s %r is outside %d..%d" % (name, v, lo, hi))
+    return sum(1 << b"ACGT".index(c) for c in set(letters))
+
+
+def poly_tail(seq: bytes, letters=b"G", min_len: int = 10) -> tuple[int, int]:
+    """Where a tail of one letter is cut from the 3' end of the read seq: (new length, index of the letter in ACGT), or (len(seq), -1)
+    when nothing is cut.  Two-colour machines (NovaSeq, NextSeq) call G where a cluster gives no signal, so the reads of short inserts
+    and of dying clusters end in a run of G of high quality.  The rule is the project's own, modelled on fastp's --trim_poly_g /
+    --trim_poly_x; it does not claim fastp's bytes.  Integers only.
+      * The sequence is folded to upper case; a byte that is none of A C G T matches no letter.
+      * For a letter X of `letters` and a tail length L in 1..n, mism(L) is the number of the last L bases that are not X.
+      * L is valid if L >= min_len, the base at n - L is X (the tail begins on its letter) and mism(L) <= min(5, L // 8).
+      * The cut is the largest valid L over all letters: n - L bases remain.  Two letters cannot share a valid L, so there is no tie.
+      * The tail may step over a mismatch onto an earlier X: (ACGT) * 10 + G * 10 is cut to 38, not 40 -- the G of the last ACGT lies
+        one T in front of the run, and twelve bases with one mismatch are a valid tail.  That is the rule.
+    The walk from the 3' end stops at a letter's sixth mismatch: no longer tail of that letter can be valid."""
+    mask = check_read_filter(letters, min_len)
+    s = bytes(seq).translate(_DD_FOLD)
+    n = len(s)
+    best, which = 0, -1
+    for x, X in enumerate(b"ACGT"):
+        if not (mask >> x) & 1:
+            continue
+        mism = 0
+        for L in range(1, n + 1):
+            if s[n - L] != X:
+                mism += 1
+                if mism > 5:
+                    break
+            elif L >= min_len and mism <= min(5, L // 8) and L > best:
+                best, which = L, x
+    return n - best, which
+
+
+def read_fails(seq: bytes, quals: bytes, min_length: int = 0, max_n=None, complexity: int = 0, mean_qual: int = 0) -> int:
+    """Which filter the read (sequence and Phred+33 quality characters, n of each) fails: 0 = none, else the first that holds of
+      1. too short:      0 < n < min_length;
+      2. too many N:     more than max_n bytes that are none of A C G T in either case (None: no limit);
+      3. low complexity: n >= 2 and 100 * d < complexity * (n - 1), d = the positions i in [0, n - 1) whose folded letters at i and i + 1
+                         differ, every byte that is none of A C G T folded to N (fastp's measure, in integers);
+      4. low quality:    sum(q) < mean_qual * n, q = clamp(character - 33, 0, 127).
+    A read of length 0 fails nothing.  Integers only."""
+    check_read_filter(b"", 10, min_length, max_n, complexity, mean_qual)
+    s = bytes(seq).translate(_DD_FOLD)
+    n = len(s)
+    if len(quals) != n:
+        raise ValueError("sequence and quality lengths differ")
+    if n == 0:
+        return 0
+    if n < min_length:
+        return 1
+    if max_n is not None and sum(c == 78 for c in s) > max_n:
+        return 2
+    if n >= 2 and 100 * sum(s[i] != s[i + 1] for i in range(n - 1)) < complexity * (n - 1):
+        return 3
+    if sum(min(max(c - 33, 0), 127) for c in bytes(quals)) < mean_qual * n:
+        return 4
+    return 0
+
+
+FILTER_REASONS = ("failed_short", "failed_n", "failed_complexity", "failed_quality")      # read_fails' 1..4
+
+
+def filter_fastq(text: bytes, letters=b"", poly_min: int = 10, min_length: int = 0, max_n=None, complexity: int = 0, mean_qual: int = 0) -> tuple[bytes, dict]:
+    """The FASTQ text the engine behaves as if it had been given under Engine.set_read_filter(letters, poly_min, min_length, max_n,
+    complexity, mean_qual), and the counters of Engine.read_filter_info().  This is the rule mlst_set_read_filter applies on the device
+    (csrc/read_filter.h); it serves the tests and whoever wants the filtered file -- the command never calls it.  Per record, header and
+    '+' line untouched, line ends LF:
+      1. poly_tail(sequence, letters, poly_min) of the bases and quality characters remain (letters empty: no tail trim).
+      2. read_fails judges the read as it stands then; a read that fails stays a record with empty sequence and quality lines (rule 5 of
+         dedup_fastq), and so does a read that was one tail.
+      3. Each mate of a pair is treated on its own (filter each file): the partner of a failed mate stays.
+    Its place in the chain: behind trim_pair_overlap(trim_adapters(prep_fastq(...))) and in front of dedup_fastq.  Under --phred64
+    prep_fastq stands in front and has rewritten the quality characters to +33 already.
+    Counters: tail_trimmed (reads whose tail was cut), tail_bases, per_letter (reads cut, by A, C, G, T), tail_emptied (reads of
+    length >= 1 that were one tail), failed_short, failed_n, failed_complexity, failed_quality (reads emptied, by the first reason),
+    filtered_bases (the bases those reads held behind the tail trim)."""
+    check_read_filter(letters, poly_min, min_length, max_n, complexity, mean_qual)
+    lines = bytes(text).split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    if len(lines) % 4:
+        raise ValueError("FASTQ text holds %d lines: not a whole number of 4-line records" % len(lines))
+    out = []
+    info = {"tail_trimmed": 0, "tail_bases": 0, "per_letter": [0, 0, 0, 0], "tail_emptied": 0, "failed_short": 0, "failed_n": 0,
+            "failed_complexity": 0, "failed_quality": 0, "filtered_bases": 0}
+    for k in range(0, len(lines), 4):
+        h, s, p, ql = (x[:-1] if x.endswith(b"\r") else x for x in lines[k:k + 4])
+        if len(s) != len(ql):
+            raise ValueError("FASTQ record with different sequence and quality lengths: %r" % h[:60])
+        cut, which = poly_tail(s, letters, poly_min) if letters else (len(s), -1)
+        if which >= 0:
+            info["tail_trimmed"] += 1
+            info["tail_bases"] += len(s) - cut
+            info["per_letter"][which] += 1
+            info["tail_emptied"] += cut == 0
+        why = read_fails(s[:cut], ql[:cut], min_length, max_n, complexity, mean_qual)
+        if why:
+            info[FILTER_REASONS[why - 1]] += 1
+            info["filtered_bases"] += cut
+            cut = 0
+        out.append(b"%s\n%s\n%s\n%s\n" % (h, s[:cut], p, ql[:cut]))
+    return b"".join(out), info
+
+
 DEDUP_LEVELS = (1, 2, 3, 4, 5, 10, 50, 500)      # the lower edges of the eight levels: keys that occur 1, 2, 3, 4, 5-9, 10-49, 50-499, >= 500 times
 _DD_FOLD = bytes(c if c in b"ACGT" else (c & 0xDF if (c & 0xDF) in b"ACGT" else 78) for c in range(256))      # a letter as the engine aligns it (78: 'N')
 

@@ -215,7 +215,8 @@ def deal_samples(sizes: list[int], world: int) -> list[int]:
 
 def type_many_samples(engines, idx, database, targs, samples: list[list[str]], rank: int, world: int, out_dir: str, log: bool,
                       chunk_bytes: int, printer=None, timing: dict | None = None, tile=None, long_reads=None,
-                      long_bam_reads=None, read_prep_info: dict | None = None, read_adapters_info: dict | None = None) -> int:
+                      long_bam_reads=None, read_prep_info: dict | None = None, read_adapters_info: dict | None = None,
+                      read_filter_info: dict | None = None) -> int:
     """Multi-sample mode (BASELINE configs[3]: "RCCL gather of per-species ST tables"; the reference's real use is many
     samples into one folder, one metamlst.py run each, metamlst-merge.py:93-107 reads the folder).  Whole samples are
     dealt to the ranks -- no collective on the data path --, every rank sends its samples through the pipelined typing
@@ -228,7 +229,8 @@ def type_many_samples(engines, idx, database, targs, samples: list[list[str]], r
     samples are BAMs of unpaired reads, cut into windows the same way.  read_prep_info: a dict that gathers the counters of
     Engine.read_prep_info() over this rank's samples (the engines carry the setting of Engine.set_read_prep already: it is per read,
     so neither the dealing of samples nor the sharding of one sample sees it).  read_adapters_info: the same for
-    Engine.read_adapters_info() (Engine.set_read_adapters; "per_adapter" is added adapter by adapter)."""
+    Engine.read_adapters_info() (Engine.set_read_adapters; "per_adapter" is added adapter by adapter).  read_filter_info: the same for
+    Engine.read_filter_info() (Engine.set_read_filter; "per_letter" is added letter by letter)."""
     import threading
     import time
     from .cli import submit_sample_files
@@ -274,6 +276,11 @@ def type_many_samples(engines, idx, database, targs, samples: list[list[str]], r
                 with prep_lock:
                     for key, v in got.items():
                         read_adapters_info[key] = [x + y for x, y in zip(read_adapters_info[key], v)] if key == "per_adapter" else read_adapters_info.get(key, 0) + v
+            if read_filter_info is not None:
+                got = e.read_filter_info()
+                with prep_lock:
+                    for key, v in got.items():
+                        read_filter_info[key] = [x + y for x, y in zip(read_filter_info[key], v)] if key == "per_letter" else read_filter_info.get(key, 0) + v
         except CorruptInput as ex:
             print(ex, file=sys.stderr, flush=True)
             corrupt.add(job[0])
