@@ -215,8 +215,7 @@ def deal_samples(sizes: list[int], world: int) -> list[int]:
 
 def type_many_samples(engines, idx, database, targs, samples: list[list[str]], rank: int, world: int, out_dir: str, log: bool,
                       chunk_bytes: int, printer=None, timing: dict | None = None, tile=None, long_reads=None,
-                      long_bam_reads=None, read_prep_info: dict | None = None, read_adapters_info: dict | None = None,
-                      read_filter_info: dict | None = None) -> int:
+                      long_bam_reads=None, chain_infos: dict | None = None) -> int:
     """Multi-sample mode (BASELINE configs[3]: "RCCL gather of per-species ST tables"; the reference's real use is many
     samples into one folder, one metamlst.py run each, metamlst-merge.py:93-107 reads the folder).  Whole samples are
     dealt to the ranks -- no collective on the data path --, every rank sends its samples through the pipelined typing
@@ -226,13 +225,11 @@ def type_many_samples(engines, idx, database, targs, samples: list[list[str]], r
     byte what one run per sample writes.  tile = (read_len, stride, min_len): the samples are assemblies (FASTA files), cut into
     windows on the GPU (cli.submit_contigs).  long_reads = (read_len, stride): FASTQ records longer than read_len are cut into windows
     on the GPU (Engine.set_read_tiling, made sure of per engine by cli.submit_sample_files).  long_bam_reads = (read_len, stride): the
-    samples are BAMs of unpaired reads, cut into windows the same way.  read_prep_info: a dict that gathers the counters of
-    Engine.read_prep_info() over this rank's samples (the engines carry the setting of Engine.set_read_prep already: it is per read,
-    so neither the dealing of samples nor the sharding of one sample sees it).  read_adapters_info: the same for
-    Engine.read_adapters_info() (Engine.set_read_adapters; "per_adapter" is added adapter by adapter).  read_filter_info: the same for
-    Engine.read_filter_info() (Engine.set_read_filter; "per_letter" is added letter by letter)."""
+    samples are BAMs of unpaired reads, cut into windows the same way.  chain_infos: read_chain.zeros(chain), {stage key: counters}: it
+    gathers those stages' counters over this rank's samples (the engines carry their settings already: they are per read)."""
     import threading
     import time
+    from . import read_chain
     from .cli import submit_sample_files
     from .pipeline import TypingPipeline
     from .typing import log_table, sample_name, type_sample
@@ -266,21 +263,10 @@ def type_many_samples(engines, idx, database, targs, samples: list[list[str]], r
             # (a BAM's "reads taken" line: unless --quiet, as for a single sample; feeder threads print whole lines)
             submit_sample_files(e, job[1], False, chunk_bytes, report=None if printer is None else (lambda line: print(line, flush=True)), tile=tile,
                                 long_reads=long_reads, long_bam_reads=long_bam_reads)
-            if read_prep_info is not None:      # (the counters are the sample's: the engine's next sample zeroes them)
-                got = e.read_prep_info()
+            if chain_infos:      # (the counters are the sample's: the engine's next sample zeroes them)
+                got = read_chain.infos(e, chain_infos)
                 with prep_lock:
-                    for key, v in got.items():
-                        read_prep_info[key] = read_prep_info.get(key, 0) + v
-            if read_adapters_info is not None:
-                got = e.read_adapters_info()
-                with prep_lock:
-                    for key, v in got.items():
-                        read_adapters_info[key] = [x + y for x, y in zip(read_adapters_info[key], v)] if key == "per_adapter" else read_adapters_info.get(key, 0) + v
-            if read_filter_info is not None:
-                got = e.read_filter_info()
-                with prep_lock:
-                    for key, v in got.items():
-                        read_filter_info[key] = [x + y for x, y in zip(read_filter_info[key], v)] if key == "per_letter" else read_filter_info.get(key, 0) + v
+                    chain_infos.update(read_chain.add_infos(chain_infos, got))
         except CorruptInput as ex:
             print(ex, file=sys.stderr, flush=True)
             corrupt.add(job[0])
