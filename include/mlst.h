@@ -614,7 +614,7 @@ int mlst_read_dedup_info(mlst_handle* h, uint64_t out[16]);
  *   behaves as if it had been given the cut text (metamlst_amd.fastq.pair_overlap / trim_pair_overlap state the rule in Python and write
  *   that text).  Off: nothing is queued, nothing is allocated, and the kernels that run are those that ran before the switch existed.
  *   MLST_E_INVALID for min_overlap outside 8..320, max_mismatches outside 0..64, error_permille outside 0..500 (fastp's defaults:
- *   30, 5, 200).  The rule is modelled on fastp's overlap analysis (no indels); it is the project's own and claims none of fastp's bytes.
+ *   30, 5, 200), and while mlst_set_read_window holds a front cut (see there).  The rule is modelled on fastp's overlap analysis (no indels); it is the project's own and claims none of fastp's bytes.
  * The rule, per pair (mate 1 of n1 letters, mate 2 of n2):
  *   1. Letters are folded as mlst_set_read_dedup folds them: A C G T in either case stand for themselves, every other byte is N.  c2 is
  *      the reverse complement of mate 2; the complement of N is N.
@@ -695,6 +695,46 @@ typedef struct { uint32_t poly_mask, poly_min, min_length, max_n, complexity_pct
 int mlst_set_read_filter(mlst_handle* h, const mlst_read_filter* f);
 int mlst_get_read_filter(mlst_handle* h, mlst_read_filter* out);
 int mlst_read_filter_info(mlst_handle* h, uint64_t out[16]);
+
+/* ---- sliding-window quality cuts (off by default; csrc/read_window.h; `cli type --cut-front W,Q / --cut-right W,Q / --cut-tail W,Q`) ----
+ * mlst_set_read_window(h, &w): mlst_set_read_prep's trim_qual is a running sum from the 3' end: it tolerates a dip in the middle of a
+ *   read that a window mean catches, and it never touches the 5' end.  The three operations here are the quality step of the usual
+ *   preprocessing recipes (fastp --cut_front / --cut_right / --cut_tail; Trimmomatic LEADING:Q = front 1,Q, TRAILING:Q = tail 1,Q,
+ *   SLIDINGWINDOW:W:Q = right W,Q; MINLEN is mlst_set_read_filter's min_length).  They are done on the device before the reads are
+ *   packed, and the engine then behaves as if it had been given the cut text (metamlst_amd.fastq.window_cut / cut_windows state the rule
+ *   in Python and write that text).  NULL or a struct with every w = 0 switches the stage off: nothing is queued, nothing is allocated,
+ *   and the kernels that run are those that ran before the switch existed.  An operation with w = 0 is off (its q is not looked at and is
+ *   kept as 0).  MLST_E_INVALID, with a sentence that names the field and its range, for a w outside 0..320 and for a q outside 1..93
+ *   where w != 0.  The rule is modelled on fastp's three operations; it is the project's own and claims neither fastp's nor
+ *   Trimmomatic's bytes.
+ * The rule, per read (integers only).  q[0..n) are the Phred values as steps 1-3 of mlst_set_read_prep leave them:
+ *   clamp(character - phred base, 0, 127).  Each operation X has its window W_X and its threshold Q_X; pass(a, w) is
+ *   sum(q[a .. a + w)) >= Q * w.  In this order:
+ *   1. front.  If n > 0: w = min(W, n); f = the smallest s in [0, n - w] with pass(s, w); none: f = n, the read is left without a base.
+ *      Off: f = 0.
+ *   2. right, on [f, n).  If n - f > 0: w = min(W, n - f); s* = the smallest s in [f, n - w] with !pass(s, w); none: e = n; otherwise
+ *      e = s* + k, k = the number of leading values of that window that are >= Q (the good bases at the front of the first bad window
+ *      stay; k < w always).  Off: e = n.
+ *   3. tail, on [f, e).  If e - f > 0: w = min(W, e - f); t = the largest t in [f + w, e] with pass(t - w, w); none: t = f.  e = t.
+ *   4. Bases and qualities [f, e) remain.  A read left without a base stays a read of length 0 (mlst_set_read_prep's rule 4); indices,
+ *      pairing and names are the file's.  Each mate of a pair is cut on its own.
+ *   5. It runs directly behind mlst_set_read_prep's steps and in front of mlst_set_read_adapters' cut (quality before adapters: cutadapt's
+ *      and fastp's order); the prepared tables of mlst_set_read_stats are counted behind it (also when it is the only step that ran).
+ *   Not done: Trimmomatic's per-base MAXINFO, fastp's skipping of N bases behind a front cut.
+ * One combination is refused, in either order, with MLST_E_INVALID and its reason: front_w != 0 together with
+ *   mlst_set_read_pair_overlap.  The overlap places the insert's end by trim5 alone (I = o + n2 + trim5: both mates lost the same
+ *   number of 5' bases), and a front cut per read would make it cut true insert bases.  right and tail combine with it freely.
+ * Entries it applies to, what is refused while it is on ("<entry>: the quality windows are on (mlst_set_read_window) ..."), when the
+ *   setting may change and what mlst_reset_sample does: exactly as for mlst_set_read_filter.
+ * mlst_get_read_window: the setting (every field 0 with the switch off).
+ * mlst_read_window_info: out[0] = reads whose length changed, out[1] = reads cut by front, out[2] = the bases it removed (all n of a
+ *   read it emptied), out[3] / out[4] = the same for right, out[5] / out[6] for tail, out[7] = reads of length >= 1 left without a base.
+ *   All zero with the switch off; an open BGZF piece is finished first.
+ * No host synchronisation is added per chunk; mlst_get_kernel_time 24 is k_rw_cut alone. */
+typedef struct { uint32_t front_w, front_q, right_w, right_q, tail_w, tail_q; } mlst_read_window;   /* w = 0: that operation is off */
+int mlst_set_read_window(mlst_handle* h, const mlst_read_window* w);   /* NULL or all-zero = off */
+int mlst_get_read_window(mlst_handle* h, mlst_read_window* out);
+int mlst_read_window_info(mlst_handle* h, uint64_t out[8]);
 
 /* ---- bowtie2's MD:Z field in the text export (off by default; csrc/aln_text.h; `cli type --md`) --------------------------------------
  * mlst_set_export_md(h, 1): every record of mlst_alignments_text_* carries MD:Z:<text> between NM:i and YT:Z:UU, bowtie2's place;
@@ -986,7 +1026,7 @@ int mlst_set_profiling(mlst_handle* h, int on);   /* 0 = off, 1 = events + sieve
  * k_sam_accumulate and 17 = k_sam_pileup (csrc/sam_dev.h; two entries of 15 per chunk); 18 = k_rp_qtrim (csrc/read_prep.h) and 19 = k_ra_cut
  * (csrc/read_adapt.h), each alone (inside 6); 20 = k_rs_count (csrc/read_stats.h; alone, inside 6); 21 = k_dd_insert + k_dd_sign + k_dd_mark
  * (csrc/read_dedup.h; the three launches of a chunk together, inside 6); 22 = k_po_cut (csrc/read_overlap.h; alone, inside 6); 23 = k_rf_filter
- * (csrc/read_filter.h; alone, inside 6); 9 = k_route, 10 =
+ * (csrc/read_filter.h; alone, inside 6); 24 = k_rw_cut (csrc/read_window.h; alone, inside 6); 9 = k_route, 10 =
  * k_route_probe and 11 = k_route_verify, the three kernels of the routed sieve (inside 0) (events bracket the launch on the engine's
  * stream, so with several engines on one GPU they include the time a kernel queues behind another stream's kernel);
  * 7 = the sieve's execution window measured inside the kernel (wall clock at the first workgroup's start and the last

@@ -8,6 +8,7 @@
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam-all -d DB  (also <out>/<sample>.all.sam: every alignment, as bowtie2 -a would leave it)
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam-all --read-names -d DB  (QNAME = the reads' own names, kept on the GPU)
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-sam --write-sam-all --md -d DB  (both exports with bowtie2's MD:Z field)
+    python -m metamlst_amd.cli type  SAMPLE.fastq --cut-front 1,3 --cut-tail 1,3 --cut-right 4,15 --min-length 36 -d DB  (Trimmomatic's quality recipe, on the GPU)
     python -m metamlst_amd.cli type  SAMPLE.fastq --write-reads -d DB    (also <out>/<sample>.loci.fastq: the reads that align to the loci, as bowtie2 --al)
     python -m metamlst_amd.cli merge FOLDER -d DB [-z 5] [--filter ...] [--meta ...] [--idField ...] [--aligner auto|gpu|muscle]   (metamlst-merge.py:35-49)
     python -m metamlst_amd.cli index -d DB [-s seqs.fasta,...] [-t typings.txt,...] [-q dump.fa] [--list]   (metamlst-index.py:24-33)
@@ -26,7 +27,7 @@ import time
 from functools import reduce
 
 from . import db as mdb, read_chain
-from .read_chain import _read_filter_of, _sum_filter_infos, read_dedup_line, read_filter_line, read_pair_overlap_line, read_stats_lines  # noqa: F401
+from .read_chain import _read_filter_of, _sum_filter_infos, read_dedup_line, read_filter_line, read_pair_overlap_line, read_stats_lines, read_window_line  # noqa: F401
 from .engine import CorruptInput, Engine, crc_checked, default_params
 from .fastq import is_bgzf, mates_share_names, pair_chunks, prefetch, text_chunks, tile_fasta
 from .index import load_index
@@ -115,7 +116,7 @@ def _type_parser(sub):
                         "bases can be rebuilt from the record alone (samtools calmd -e, pysam get_reference_sequence).  --write-sam-all "
                         "formats it on the GPU.  Accepted and refused where the export flags are; it combines with --read-names.  The "
                         ".nfo and the --log file do not change")
-    read_chain.add_arguments(p)      # (the flags of the six read chain stages: --trim5 ... --min-mean-qual)
+    read_chain.add_arguments(p)      # (the flags of the seven read chain stages: --trim5 ... --min-mean-qual)
     p.add_argument("--max-retained", default=0, type=int, metavar="READS", help="capacity of the on-locus read store (default 4 M)")
     p.add_argument("--max-items", default=0, type=int, metavar="ITEMS", help="capacity of the (read, locus, strand) work-item list (default 8 M)")
     p.add_argument("--max-pair-results", default=0, type=int, metavar="PAIRS", help="capacity of the (item, allele) result arena (default 256 M)")
@@ -254,7 +255,7 @@ def run_type(a, argv=None) -> int:
                 (reads_bam, "the names of a reads BAM are not carried to the exports: FASTQ input only"),
                 (not (a.write_sam or a.write_sam_all or a.write_reads), "it names the reads of an export: give --write-sam or --write-sam-all"))):
             return 1
-    chain = read_chain.parse(a, samples, reads_bam, world)      # (the six stages: refused before any GPU use, each with its reason)
+    chain = read_chain.parse(a, samples, reads_bam, world)      # (the seven stages: refused before any GPU use, each with its reason)
     if chain is None:
         return 1
     if a.md and not (a.write_sam or a.write_sam_all):      # (with an export flag it is accepted and refused where that flag is: below)

@@ -3699,6 +3699,7 @@ __global__ void k_fill_u64(u64* p, u64 n, u64 v) {
 #include "read_dedup.h"
 #include "read_overlap.h"
 #include "read_filter.h"
+#include "read_window.h"
 #include "read_stats.h"
 #include "aln_text.h"
 #include "reads_text.h"
@@ -3807,7 +3808,7 @@ struct mlst_handle {
     GraphSlot g_submit, g_typing; bool use_graphs = true;
     std::vector<EvPair> events;
     std::vector<hipEvent_t> ev_pool;
-    double k_ms[24] = {0}; u64 k_n[24] = {0};      // see mlst_get_kernel_time
+    double k_ms[25] = {0}; u64 k_n[25] = {0};      // see mlst_get_kernel_time
     double wall_khz = 100000.0;                  // wall_clock64 rate (hipDeviceAttributeWallClockRate)
     struct BamStream* bam = nullptr;             // BAM input (mlst_bam_open / mlst_submit_bam_bgzf), allocated by the first stream
     u32 bam_force_miss = 0; u64 bam_max_entries = 0;      // mlst_debug_bam_split, mlst_bam_set_capacity
@@ -3875,6 +3876,9 @@ struct mlst_handle {
     // poly-G / poly-X tails trimmed and reads filtered before the reads are packed (mlst_set_read_filter; csrc/read_filter.h): the switch
     // (on: the setting is not all off), the setting, the counters on the device -- allocated by the first submission under the switch
     struct { bool on = false; RfSet set = {0, 10, 0, RF_NO_LIMIT, 0, 0}; RfCtr* d_ctr = nullptr; } rf;
+    // sliding-window quality cuts before the reads are packed (mlst_set_read_window; csrc/read_window.h): the switch (on: an operation has
+    // a window), the setting, the counters on the device -- allocated by the first submission under the switch
+    struct { bool on = false; RwSet set = {0, 0, 0, 0, 0, 0}; RwCtr* d_ctr = nullptr; } rw;
 };
 
 static std::string g_create_err;
@@ -7748,13 +7752,13 @@ extern "C" int mlst_get_items(mlst_handle* h, mlst_item* out, uint64_t cap, uint
 
 extern "C" int mlst_set_profiling(mlst_handle* h, int on) { if (!h) return MLST_E_INVALID; drain_events(h); h->profiling = on == 1; h->window = on != 0; return MLST_OK; }
 extern "C" int mlst_get_kernel_time(mlst_handle* h, int which, double* total_ms, uint64_t* launches) {
-    if (!h || which < 0 || which >= 24) return MLST_E_INVALID;
+    if (!h || which < 0 || which >= 25) return MLST_E_INVALID;
     hipSetDevice(h->device); drain_events(h);
     if (total_ms) *total_ms = h->k_ms[which];
     if (launches) *launches = h->k_n[which];
     return MLST_OK;
 }
-extern "C" int mlst_reset_kernel_time(mlst_handle* h) { if (!h) return MLST_E_INVALID; drain_events(h); for (int i = 0; i < 24; i++) { h->k_ms[i] = 0; h->k_n[i] = 0; } return MLST_OK; }
+extern "C" int mlst_reset_kernel_time(mlst_handle* h) { if (!h) return MLST_E_INVALID; drain_events(h); for (int i = 0; i < 25; i++) { h->k_ms[i] = 0; h->k_n[i] = 0; } return MLST_OK; }
 extern "C" int mlst_get_index_bytes(mlst_handle* h, uint64_t out[4]) {
     if (!h || !out) return MLST_E_INVALID;
     out[0] = h->bytes_arena + h->bytes_hap; out[1] = h->bytes_sieve; out[2] = h->bytes_table; out[3] = (u64)(h->bitmap_fill * 1e6); return MLST_OK;

@@ -1,6 +1,6 @@
-// The read chain on the host ("The read chain"): what strings the seven read-preparation stages of the FASTQ path together.  The kernels are
-// in csrc/read_names.h, read_prep.h, read_adapt.h, read_stats.h, read_dedup.h, read_overlap.h and read_filter.h, the state of each stage in
-// mlst_handle (h->rn, rp, ra, rs, dd, po, rf).  Here, once for all of them: which entries a switch closes (chain_refuse), when a switch may
+// The read chain on the host ("The read chain"): what strings the eight read-preparation stages of the FASTQ path together.  The kernels are
+// in csrc/read_names.h, read_prep.h, read_window.h, read_adapt.h, read_stats.h, read_dedup.h, read_overlap.h and read_filter.h, the state of
+// each stage in mlst_handle (h->rn, rp, rw, ra, rs, dd, po, rf).  Here, once for all of them: which entries a switch closes (chain_refuse), when a switch may
 // change (chain_gate), the order of the stages over a parsed chunk (chain_apply), the counters' first use and read-back (chain_ctr,
 // chain_fetch), what a new sample and the end of the handle do (chain_reset, chain_free), and the public setters and readers.
 // A new stage is one row in chain_refuse, one line in chain_apply, chain_reset and chain_free, and its setter.
@@ -22,6 +22,7 @@ static int chain_refuse(mlst_handle* h, const char* entry) {
         {h->dd.on, "%s: duplicate removal is on (mlst_set_read_dedup) and only the FASTQ text and BGZF entries apply it"},
         {h->po.on, "%s: mate overlap trimming is on (mlst_set_read_pair_overlap) and only the paired FASTQ text and BGZF entries apply it"},
         {h->rf.on, "%s: the read filter is on (mlst_set_read_filter) and only the FASTQ text and BGZF entries apply it"},
+        {h->rw.on, "%s: the quality windows are on (mlst_set_read_window) and only the FASTQ text and BGZF entries apply them"},
     };
     for (const auto& r : rows) if (r.on) return fail(h, MLST_E_INVALID, r.fmt, entry);
     return MLST_OK;
@@ -74,11 +75,12 @@ static int chain_reset(mlst_handle* h) {
     if (h->po.d_ctr) HIPCHK(h, hipMemsetAsync(h->po.d_ctr, 0, sizeof(PoCtr), h->stream));
     h->po.pairs = 0;
     if (h->rf.d_ctr) HIPCHK(h, hipMemsetAsync(h->rf.d_ctr, 0, sizeof(RfCtr), h->stream));
+    if (h->rw.d_ctr) HIPCHK(h, hipMemsetAsync(h->rw.d_ctr, 0, sizeof(RwCtr), h->stream));
     return MLST_OK;
 }
 // (the name arena is freed with the retained-read store it is sized by: free_state)
 static void chain_free(mlst_handle* h) {
-    hipFree(h->rp.d_ctr); hipFree(h->ra.d_ctr); hipFree(h->rs.d_tab); hipFree(h->po.d_ctr); hipFree(h->rf.d_ctr);
+    hipFree(h->rp.d_ctr); hipFree(h->ra.d_ctr); hipFree(h->rs.d_tab); hipFree(h->po.d_ctr); hipFree(h->rf.d_ctr); hipFree(h->rw.d_ctr);
     hipFree(h->dd.d_mem); hipFree(h->dd.d_ctr); hipFree(h->dd.d_slot_of); hipFree(h->dd.d_key2);
 }
 
@@ -207,7 +209,7 @@ static int po_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
     return MLST_OK;
 }
 // The parser has left offsets and lengths of n_reads reads of h->d_fq_text and the longest length in flags[0].  The chain, in its one
-// order, queued in front of the read-back of the flags (no synchronisation added): raw statistics, quality trim, adapter cut, mate
+// order, queued in front of the read-back of the flags (no synchronisation added): raw statistics, quality trim, quality windows, adapter cut, mate
 // overlap, tail trim and read filter, prepared statistics, duplicate removal.  flags[0] is zeroed in front of every kernel that shortens reads, so the last one
 // alone feeds the longest length the host reads (an atomicMax with the shorter lengths would leave the longer one standing).
 // The prepared tables are counted only behind a stage that shortens: with none, launches[1] stays 0 and mlst_read_stats_fetch hands out
@@ -224,6 +226,13 @@ static int chain_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
         hipLaunchKernelGGL(k_rp_qtrim, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, h->d_fq_soff, h->d_fq_qoff, h->d_lens, n_reads, P,
                            d_flags, h->rp.d_ctr);
     }
+    if (h->rw.on) {      // (quality before adapters: cutadapt's and fastp's order; the first stage behind k_rp_qtrim that moves a read's start)
+        rc = chain_ctr(h, &h->rw.d_ctr); if (rc) return rc;
+        HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
+        Prof pf(h, 24);      // (mlst_get_kernel_time 24: k_rw_cut alone)
+        hipLaunchKernelGGL(k_rw_cut, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, h->d_fq_soff, h->d_fq_qoff, h->d_lens, n_reads, h->rw.set,
+                           P.phred_base, d_flags, h->rw.d_ctr);
+    }
     if (h->ra.on) {
         rc = chain_ctr(h, &h->ra.d_ctr); if (rc) return rc;
         HIPCHK(h, hipMemsetAsync(d_flags, 0, 4, h->stream));
@@ -239,7 +248,7 @@ static int chain_apply(mlst_handle* h, u64 n_reads, u32* d_flags, int paired) {
         hipLaunchKernelGGL(k_rf_filter, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, (const u8*)h->d_fq_text, (const u64*)h->d_fq_soff, (const u64*)h->d_fq_qoff, h->d_lens,
                            n_reads, h->rf.set, P.phred_base, d_flags, h->rf.d_ctr);
     }
-    if (h->rs.on && (trims || h->ra.on || h->po.on || h->rf.on)) { rc = rs_launch(h, n_reads, d_flags, paired, 1); if (rc) return rc; }
+    if (h->rs.on && (trims || h->rw.on || h->ra.on || h->po.on || h->rf.on)) { rc = rs_launch(h, n_reads, d_flags, paired, 1); if (rc) return rc; }
     if (h->dd.on) { rc = dd_apply(h, n_reads, d_flags, paired); if (rc) return rc; }      // (zeroes flags[0] itself; the prepared tables stay what they are)
     return MLST_OK;
 }
@@ -435,6 +444,9 @@ extern "C" int mlst_read_dedup_info(mlst_handle* h, uint64_t out[16]) {
     for (int k = 0; k < 8; k++) out[8 + k] = c.levels[k];
     return MLST_OK;
 }
+// the one combination of two stages that is refused, in both orders (mlst_set_read_pair_overlap, mlst_set_read_window)
+#define RW_PO_TEXT "a front cut (mlst_set_read_window, front_w != 0) and mate overlap trimming (mlst_set_read_pair_overlap) do not combine: the overlap places " \
+                   "the insert's end by trim5 alone (I = o + n2 + trim5: both mates lost the same number of 5' bases), and a front cut per read would make it cut true insert bases"
 // adapter read-through cut from the overlap of the mates (csrc/read_overlap.h)
 extern "C" int mlst_set_read_pair_overlap(mlst_handle* h, int on, uint32_t min_overlap, uint32_t max_mismatches, uint32_t error_permille) {
     if (!h) return MLST_E_INVALID;
@@ -442,6 +454,7 @@ extern "C" int mlst_set_read_pair_overlap(mlst_handle* h, int on, uint32_t min_o
         if (min_overlap < 8 || min_overlap > PO_MAX_LEN) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: min_overlap %u is outside 8..%d", min_overlap, PO_MAX_LEN);
         if (max_mismatches > 64) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: max_mismatches %u is outside 0..64", max_mismatches);
         if (error_permille > 500) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: error_permille %u is outside 0..500", error_permille);
+        if (h->rw.set.front_w) return fail(h, MLST_E_INVALID, "mlst_set_read_pair_overlap: %s", RW_PO_TEXT);
     }
     const bool same = (on != 0) == h->po.on && (!on || (min_overlap == h->po.set.min_overlap && max_mismatches == h->po.set.max_mism && error_permille == h->po.set.permille));
     { int rc_ = chain_gate(h, "mlst_set_read_pair_overlap", !same, on != 0, "mlst_set_read_pair_overlap: mlst_set_read_tiling is on and takes unpaired text, whose windows have no mate"); if (rc_) return rc_; }
@@ -508,5 +521,39 @@ extern "C" int mlst_read_filter_info(mlst_handle* h, uint64_t out[16]) {
     for (int k = 0; k < 4; k++) { out[2 + k] = c.per_letter[k]; out[7 + k] = c.failed[k]; }
     out[6] = c.tail_emptied; out[11] = c.filtered_bases;
     for (int k = 12; k < 16; k++) out[k] = 0;
+    return MLST_OK;
+}
+// sliding-window quality cuts before the reads are packed (csrc/read_window.h)
+extern "C" int mlst_set_read_window(mlst_handle* h, const mlst_read_window* w) {
+    if (!h) return MLST_E_INVALID;
+    RwSet want = {0, 0, 0, 0, 0, 0};      // (off)
+    if (w) {
+        const struct { const char* name; u32 w, q; } ops[] = {{"front", w->front_w, w->front_q}, {"right", w->right_w, w->right_q}, {"tail", w->tail_w, w->tail_q}};
+        for (const auto& o : ops) {
+            if (o.w > RW_MAX_W) return fail(h, MLST_E_INVALID, "mlst_set_read_window: %s_w %u is outside 0..%d", o.name, o.w, RW_MAX_W);
+            if (o.w && (o.q < 1 || o.q > 93)) return fail(h, MLST_E_INVALID, "mlst_set_read_window: %s_q %u is outside 1..93", o.name, o.q);
+        }
+        want = RwSet{w->front_w, w->front_w ? w->front_q : 0u, w->right_w, w->right_w ? w->right_q : 0u, w->tail_w, w->tail_w ? w->tail_q : 0u};
+    }
+    if (want.front_w && h->po.on) return fail(h, MLST_E_INVALID, "mlst_set_read_window: %s", RW_PO_TEXT);
+    const RwSet& cur = h->rw.set;
+    const bool same = want.front_w == cur.front_w && want.front_q == cur.front_q && want.right_w == cur.right_w && want.right_q == cur.right_q &&
+                      want.tail_w == cur.tail_w && want.tail_q == cur.tail_q;
+    const bool on = (want.front_w | want.right_w | want.tail_w) != 0;
+    { int rc_ = chain_gate(h, "mlst_set_read_window", !same, on, "mlst_set_read_window: mlst_set_read_tiling is on and a window is cut from the record as it stands"); if (rc_) return rc_; }
+    h->rw.set = want; h->rw.on = on;
+    return MLST_OK;
+}
+extern "C" int mlst_get_read_window(mlst_handle* h, mlst_read_window* out) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    const RwSet& S = h->rw.set;
+    out->front_w = S.front_w; out->front_q = S.front_q; out->right_w = S.right_w; out->right_q = S.right_q; out->tail_w = S.tail_w; out->tail_q = S.tail_q;
+    return MLST_OK;
+}
+extern "C" int mlst_read_window_info(mlst_handle* h, uint64_t out[8]) {
+    if (!h || !out) return fail(h, MLST_E_INVALID, "NULL argument");
+    RwCtr c; { int rc_ = chain_fetch(h, h->rw.on, &h->rw.d_ctr, &c); if (rc_) return rc_; }
+    out[0] = c.shortened; out[1] = c.front_reads; out[2] = c.front_bases; out[3] = c.right_reads; out[4] = c.right_bases; out[5] = c.tail_reads; out[6] = c.tail_bases;
+    out[7] = c.emptied;
     return MLST_OK;
 }

@@ -189,6 +189,9 @@ def load_library(path: str | None = None):
         "mlst_set_read_filter": (C.c_int, [H, C.POINTER(C.c_uint32)]),      # (mlst_read_filter: six uint32_t)
         "mlst_get_read_filter": (C.c_int, [H, C.POINTER(C.c_uint32)]),
         "mlst_read_filter_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
+        "mlst_set_read_window": (C.c_int, [H, C.POINTER(C.c_uint32)]),      # (mlst_read_window: six uint32_t)
+        "mlst_get_read_window": (C.c_int, [H, C.POINTER(C.c_uint32)]),
+        "mlst_read_window_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
         "mlst_set_export_md": (C.c_int, [H, C.c_int]),
         "mlst_get_export_md": (C.c_int, [H, C.POINTER(C.c_int)]),
         "mlst_read_names_info": (C.c_int, [H, C.POINTER(C.c_uint64)]),
@@ -1024,6 +1027,36 @@ class Engine:
         return {"tail_trimmed": int(out[0]), "tail_bases": int(out[1]), "per_letter": [int(out[2 + k]) for k in range(4)], "tail_emptied": int(out[6]),
                 "failed_short": int(out[7]), "failed_n": int(out[8]), "failed_complexity": int(out[9]), "failed_quality": int(out[10]),
                 "filtered_bases": int(out[11])}
+
+    def set_read_window(self, front=None, right=None, tail=None) -> None:
+        """Cut every read of FASTQ text by sliding-window mean quality on the GPU before the reads are packed (mlst_set_read_window; off by
+        default; the rule: fastq.window_cut / fastq.cut_windows, modelled on fastp's cut_front / cut_right / cut_tail), directly behind
+        set_read_prep's steps and in front of set_read_adapters' cut.  The engine then behaves as if it had been given cut_windows' text.
+        Each operation is (W, Q) -- a window of 1..320 values whose mean must reach Q, 1..93 -- or None = off: front drops bases from the
+        5' end up to the first passing window, right cuts at the first failing window behind that (its leading bases >= Q stay), tail
+        drops bases from the 3' end down to the last passing window.  W = 1 is Trimmomatic's LEADING / TRAILING, right=(4, 15) its
+        SLIDINGWINDOW:4:15.  A front cut is refused together with set_read_pair_overlap.  FASTQ text and BGZF entries only -- every other
+        way of adding reads is refused while it is on; may change only while the sample holds no reads and no stream is open."""
+        from .fastq import check_read_window
+        try:
+            vals = check_read_window(front, right, tail)
+        except ValueError as e:
+            raise ValueError("set_read_window: %s" % e) from None
+        self._check(self.lib.mlst_set_read_window(self._h, (C.c_uint32 * 6)(*vals)), "mlst_set_read_window")
+
+    def get_read_window(self) -> dict:
+        """{"front", "right", "tail"}: each [W, Q], or None for an operation that is off"""
+        p = (C.c_uint32 * 6)()
+        self._check(self.lib.mlst_get_read_window(self._h, p), "mlst_get_read_window")
+        return {name: [int(p[2 * k]), int(p[2 * k + 1])] if int(p[2 * k]) else None for k, name in enumerate(("front", "right", "tail"))}
+
+    def read_window_info(self) -> dict:
+        """Since the last reset_sample, fastq.cut_windows' counters: shortened, front_reads, front_bases, right_reads, right_bases,
+        tail_reads, tail_bases, emptied.  All zero with the switch off."""
+        from .fastq import WINDOW_COUNTERS
+        out = (C.c_uint64 * 8)()
+        self._check(self.lib.mlst_read_window_info(self._h, out), "mlst_read_window_info")
+        return {name: int(out[k]) for k, name in enumerate(WINDOW_COUNTERS)}
 
     def set_export_md(self, on: bool = True) -> None:
         """export_sam_text / write_sam_all write bowtie2's MD:Z field between NM:i and YT:Z, formatted on the GPU (mlst_set_export_md; off

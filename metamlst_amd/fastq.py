@@ -1088,6 +1088,117 @@ def filter_fastq(text: bytes, letters=b"", poly_min: int = 10, min_length: int =
     return b"".join(out), info
 
 
+WINDOW_COUNTERS = ("shortened", "front_reads", "front_bases", "right_reads", "right_bases", "tail_reads", "tail_bases", "emptied")      # mlst_read_window_info's order
+
+
+def check_read_window(front=None, right=None, tail=None) -> list:
+    """The three operations of Engine.set_read_window as mlst_read_window's six numbers [front_w, front_q, right_w, right_q, tail_w,
+    tail_q] (0, 0 for an operation that is None: off); ValueError for what mlst_set_read_window refuses and for what is no operation:
+    anything but None or a pair (W, Q) of integers, W outside 1..320, Q outside 1..93."""
+    out = []
+    for name, op in (("front", front), ("right", right), ("tail", tail)):
+        if op is None:
+            out += [0, 0]
+            continue
+        try:
+            w, q = op
+            ok = int(w) == w and int(q) == q
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("%s %r: an operation is (W, Q), two whole numbers, or None" % (name, op))
+        if not 1 <= int(w) <= 320:
+            raise ValueError("%s window %r is outside 1..320" % (name, w))
+        if not 1 <= int(q) <= 93:
+            raise ValueError("%s quality %r is outside 1..93" % (name, q))
+        out += [int(w), int(q)]
+    return out
+
+
+def _window_steps(q, front, right, tail) -> tuple[int, int, int]:      # (f, e behind right, e behind tail) of window_cut
+    n = len(q)
+    f, e = 0, n
+    P = [0] * (n + 1)      # P[i] = sum(q[:i]): the sum of a window [a, a + w) is P[a + w] - P[a]
+    for i, v in enumerate(q):
+        P[i + 1] = P[i] + v
+    if front is not None and n > 0:
+        W, Q = front
+        w = min(W, n)
+        f = next((s for s in range(n - w + 1) if P[s + w] - P[s] >= Q * w), n)
+    if right is not None and n - f > 0:
+        W, Q = right
+        w = min(W, n - f)
+        bad = next((s for s in range(f, n - w + 1) if P[s + w] - P[s] < Q * w), None)
+        if bad is not None:
+            k = 0
+            while q[bad + k] >= Q:      # (one value of a failing window is below Q: k < w)
+                k += 1
+            e = bad + k
+    er = e
+    if tail is not None and e - f > 0:
+        W, Q = tail
+        w = min(W, e - f)
+        e = next((t for t in range(e, f + w - 1, -1) if P[t] - P[t - w] >= Q * w), f)
+    return f, er, e
+
+
+def window_cut(q, front=None, right=None, tail=None) -> tuple[int, int]:
+    """Where the sliding-window quality cuts leave the read with the Phred values q[0..n): (f, e), values [f, e) remain.  The rule is the
+    project's own, in integers, modelled on fastp's cut_front / cut_right / cut_tail; it claims neither fastp's nor Trimmomatic's bytes.
+    Each operation is (W, Q), W in 1..320, Q in 1..93, or None = off; pass(a, w) is sum(q[a : a + w]) >= Q * w.  In this order:
+      1. front.  If n > 0: w = min(W, n); f = the smallest s in [0, n - w] with pass(s, w); none: f = n, the read is left without a base.
+         Off: f = 0.
+      2. right, on [f, n).  If n - f > 0: w = min(W, n - f); s* = the smallest s in [f, n - w] with not pass(s, w); none: e = n; otherwise
+         e = s* + k, k = the number of leading values of that window that are >= Q (the good bases at the front of the first bad
+         window stay; k < w always).  Off: e = n.
+      3. tail, on [f, e).  If e - f > 0: w = min(W, e - f); t = the largest t in [f + w, e] with pass(t - w, w); none: t = f.  e = t.
+    W = 1 gives Trimmomatic's LEADING:Q / TRAILING:Q (bases below Q are dropped from that end); right=(4, 15) is the model of
+    SLIDINGWINDOW:4:15.  A read that front empties answers (n, n)."""
+    check_read_window(front, right, tail)
+    f, _, e = _window_steps(list(q), front, right, tail)
+    return f, e
+
+
+def cut_windows(text: bytes, front=None, right=None, tail=None, phred64: bool = False) -> tuple[bytes, dict]:
+    """The FASTQ text the engine behaves as if it had been given under Engine.set_read_window(front, right, tail), and the counters of
+    Engine.read_window_info().  This is the rule mlst_set_read_window applies on the device (csrc/read_window.h, window_cut per read); it
+    serves the tests and whoever wants the cut file -- the command never calls it.  Per record, header and '+' line untouched, line ends
+    LF: q[i] = clamp(character - base, 0, 127), base 64 under phred64, else 33, exactly as step 1 of prep_fastq; bases and quality
+    characters [f, e) of window_cut(q, ...) remain (under phred64 the characters are written back as q[i] + 33, as prep_fastq writes
+    them; else they stay the file's); a read left without a base stays a record with two empty lines.  Each mate of a pair is cut on its
+    own (cut each file).  Its place in the chain: directly behind prep_fastq -- which has rewritten Phred+64 text to +33 already, so
+    phred64 stays False there -- and in front of trim_adapters: filter_fastq(trim_pair_overlap(trim_adapters(cut_windows(prep_fastq(...)))))
+    , then dedup_fastq.
+    Counters: shortened (reads whose length changed), front_reads / front_bases, right_reads / right_bases, tail_reads / tail_bases
+    (reads cut by the operation and the bases it removed; a read emptied by front adds all n of its bases to front_bases), emptied
+    (reads of length >= 1 left without a base)."""
+    check_read_window(front, right, tail)
+    base = 64 if phred64 else 33
+    lines = bytes(text).split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    if len(lines) % 4:
+        raise ValueError("FASTQ text holds %d lines: not a whole number of 4-line records" % len(lines))
+    out = []
+    info = dict.fromkeys(WINDOW_COUNTERS, 0)
+    for k in range(0, len(lines), 4):
+        h, s, p, ql = (x[:-1] if x.endswith(b"\r") else x for x in lines[k:k + 4])
+        if len(s) != len(ql):
+            raise ValueError("FASTQ record with different sequence and quality lengths: %r" % h[:60])
+        n = len(s)
+        q = [min(max(c - base, 0), 127) for c in ql]
+        f, er, e = _window_steps(q, front, right, tail)
+        for name, cut in (("front", f), ("right", n - er), ("tail", er - e)):
+            if cut:
+                info[name + "_reads"] += 1
+                info[name + "_bases"] += cut
+        if e - f != n:
+            info["shortened"] += 1
+            info["emptied"] += e == f
+        out.append(b"%s\n%s\n%s\n%s\n" % (h, s[f:e], p, bytes(v + 33 for v in q[f:e]) if phred64 else ql[f:e]))
+    return b"".join(out), info
+
+
 DEDUP_LEVELS = (1, 2, 3, 4, 5, 10, 50, 500)      # the lower edges of the eight levels: keys that occur 1, 2, 3, 4, 5-9, 10-49, 50-499, >= 500 times
 _DD_FOLD = bytes(c if c in b"ACGT" else (c & 0xDF if (c & 0xDF) in b"ACGT" else 78) for c in range(256))      # a letter as the engine aligns it (78: 'N')
 

@@ -1,4 +1,4 @@
-"""The read chain as `cli type` drives it (the engine's half is csrc/read_chain.h): the six stages that change or
+"""The read chain as `cli type` drives it (the engine's half is csrc/read_chain.h): the seven stages that change or
 describe the reads of FASTQ text, each stated ONCE -- its flags, how they become settings, where it is refused and in which words,
 how it goes onto an Engine and comes back as counters, and the line it prints.  STAGES is the table: its order is that of the flags
 in `type --help` and of the setters (apply); REFUSAL_ORDER and REPORT_ORDER are the two other orders a user sees.  Around it: what the
@@ -72,6 +72,65 @@ class ReadPrep(Stage):
 
     def lines(self, info, cfg, paired=False, world=1):
         return ["read preparation: %d reads shortened, %d bases removed, %d reads left without a base" % (info["shortened"], info["bases_removed"], info["emptied"]) + _rank(world)]
+
+
+class ReadWindow(Stage):
+    key, setter, counters = "window", "set_read_window", "read_window_info"
+    prefix = "quality windows (--cut-front, --cut-right, --cut-tail): "
+    refusals = {"alignments": "with --alignments the records are what they are: the file holds alignments, not reads to cut",
+                "contigs": "--contigs cuts assemblies into windows, and an assembly has no qualities", **_WINDOW,
+                "reads_bam": "a reads BAM stores raw Phred and its own strand, and its reads are not cut: FASTQ input only",
+                "many": "several samples or a folder are typed without them (the rule is per read: summing the counters of the samples is the follow-up)",
+                "gpus": "one GPU: the counters of the ranks of --gpus N are not summed yet (the follow-up)"}
+    OPS = (("front", "--cut-front", "cut_front"), ("right", "--cut-right", "cut_right"), ("tail", "--cut-tail", "cut_tail"))
+
+    def add_arguments(self, p):
+        p.add_argument("--cut-front", dest="cut_front", default=None, metavar="W,Q",
+                       help="FASTQ input: drop bases from the 5' end of every read up to the first window of W bases whose mean quality "
+                            "reaches Q, on the GPU (csrc/read_window.h; the rule: metamlst_amd.fastq.window_cut / cut_windows, modelled on fastp "
+                            "--cut_front; it is the project's own and claims neither fastp's nor Trimmomatic's bytes).  W is 1 to 320, Q 1 to "
+                            "93; W = 1 is Trimmomatic's LEADING:Q.  A read without a passing window is left without a base.  The three "
+                            "quality windows (--cut-front, --cut-right, --cut-tail) run in that order behind --trim5 / --trim3 / --trim-qual "
+                            "and in front of --adapter, each mate on its own; with --min-length they are Trimmomatic's quality recipe "
+                            "(LEADING:3 TRAILING:3 SLIDINGWINDOW:4:15 MINLEN:36 = --cut-front 1,3 --cut-tail 1,3 --cut-right 4,15 --min-length "
+                            "36).  One sample on one GPU: plain, .gz and bgzip'd FASTQ, `a.fq,b.fq`, -2; refused with --alignments, --contigs, "
+                            "--long-reads, --long-bam-reads, a reads BAM, a folder or several samples, and --gpus N; --cut-front is refused "
+                            "with --pair-overlap, which places the insert's end by --trim5 alone.  A read left without a base stays a read, "
+                            "and the exports carry the cut SEQ / QUAL.  Unless --quiet, one line reports what the three did")
+        p.add_argument("--cut-right", dest="cut_right", default=None, metavar="W,Q",
+                       help="FASTQ input: cut every read at the first window of W bases, from the 5' end on, whose mean quality is below Q; "
+                            "the bases at the front of that window that reach Q stay (fastp --cut_right, the model of Trimmomatic's "
+                            "SLIDINGWINDOW:W:Q).  It catches a dip in the middle of a read, which --trim-qual's running sum tolerates; see --cut-front")
+        p.add_argument("--cut-tail", dest="cut_tail", default=None, metavar="W,Q",
+                       help="FASTQ input: drop bases from the 3' end of every read down to the last window of W bases whose mean quality "
+                            "reaches Q (fastp --cut_tail; W = 1 is Trimmomatic's TRAILING:Q); see --cut-front")
+
+    def parse(self, a):
+        out = {}
+        for name, flag, dest in self.OPS:
+            text = getattr(a, dest, None)
+            if text is None:
+                out[name] = None
+                continue
+            try:
+                w, q = (int(x) for x in text.split(","))
+            except ValueError:
+                raise ValueError("%s W,Q takes two numbers, not %r" % (flag, text)) from None
+            if not 1 <= w <= 320:
+                raise ValueError("%s W,Q: a window holds 1 to 320 bases, not %d" % (flag, w))
+            if not 1 <= q <= 93:
+                raise ValueError("%s W,Q: a quality is 1 to 93, not %d" % (flag, q))
+            out[name] = (w, q)
+        return out if any(v is not None for v in out.values()) else None
+
+    def refuse_own(self, a, samples):
+        if getattr(a, "cut_front", None) is not None and getattr(a, "pair_overlap", False):
+            return ("--cut-front goes with no --pair-overlap, which places the insert's end by --trim5 alone (both mates lost the same number of "
+                    "5' bases): a front cut per read would make it cut true insert bases (--cut-right and --cut-tail combine with it)")
+        return None
+
+    def lines(self, info, cfg, paired=False, world=1):
+        return [read_window_line(info)]
 
 
 class Adapters(Stage):
@@ -290,9 +349,9 @@ class ReadFilter(Stage):
         return out
 
 
-PREP, ADAPTERS, STATS, DEDUP, OVERLAP, FILTER = STAGES = (ReadPrep(), Adapters(), ReadStats(), Dedup(), PairOverlap(), ReadFilter())      # the table
-REFUSAL_ORDER = (PREP, ADAPTERS, FILTER, STATS, DEDUP, OVERLAP)      # which stage speaks first when several refuse
-REPORT_ORDER = (PREP, ADAPTERS, FILTER, OVERLAP, STATS, DEDUP)      # the lines behind a sample
+PREP, WINDOW, ADAPTERS, STATS, DEDUP, OVERLAP, FILTER = STAGES = (ReadPrep(), ReadWindow(), Adapters(), ReadStats(), Dedup(), PairOverlap(), ReadFilter())      # the table
+REFUSAL_ORDER = (PREP, WINDOW, ADAPTERS, FILTER, STATS, DEDUP, OVERLAP)      # which stage speaks first when several refuse
+REPORT_ORDER = (PREP, WINDOW, ADAPTERS, FILTER, OVERLAP, STATS, DEDUP)      # the lines behind a sample
 SUMMING = [s for s in STAGES if "many" not in s.refusals and "gpus" not in s.refusals]      # their counters add up over the samples of a folder and the ranks of --gpus N
 _read_filter_of = FILTER.parse
 
@@ -370,6 +429,12 @@ def read_filter_line(info: dict, world: int = 1) -> str:
             "(%d too short, %d with too many N, %d of low complexity, %d of low quality), %d bases"
             % (int(info["tail_trimmed"]), *[int(v) for v in info["per_letter"]], int(info["tail_bases"]), int(info["tail_emptied"]), sum(failed), *failed,
                int(info["filtered_bases"]))) + _rank(world)
+
+
+def read_window_line(info: dict) -> str:
+    """The line on what --cut-front / --cut-right / --cut-tail did (info: Engine.read_window_info() or fastq.cut_windows' counters)"""
+    return ("quality windows: %d reads cut (front %d reads / %d bases, right %d reads / %d bases, tail %d reads / %d bases), %d reads left without a base"
+            % tuple(int(info[k]) for k in ("shortened", "front_reads", "front_bases", "right_reads", "right_bases", "tail_reads", "tail_bases", "emptied")))
 
 
 def read_pair_overlap_line(info: dict) -> str:
